@@ -3,6 +3,12 @@
 bs 512 per GPU, bf16) on N MI355X -- BASELINE.json's metric.  One JSON line on stdout (rank 0).
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--mixer fft|permut|dwt_embed|dwt_token] [--eager] [--dp-sequence]
+                    [--full] [--dump-outputs DIR]
+
+A plain run sets up, warms up, times the K steps and prints the headline.  --full adds everything else, after the timed steps: the
+roofline pass and per-kernel figures, the eager form of the step, the other mixers, the every-row last layer, the data-parallel rank
+sequence, the reference loop verbatim, the Base/224 student and the CPU baseline (each can be left out with its --no-* option).
+--dump-outputs DIR writes what the timed step computed in its last step as float32 .npy files (see dump_outputs()).
 
 A step = forward + CrossEntropy + backward + (gradient all-reduce) + AdamW on one batch resident in HBM
 (reference loop: spectre_vit/repl/train.py:216-238).  N > 1: one rank per GPU; a rank replays two HIP graphs around ONE RCCL
@@ -43,22 +49,32 @@ def parse_args(argv=None):
                     help="headline = eager launches (default at 1 GPU: the step replayed from ONE HIP graph, spectre_vit.graph."
                          "GraphedTrainStep, with the eager time reported beside it; multi-GPU runs are always eager)")
     ap.add_argument("--graph", action="store_true", help="(kept for compatibility: graph replay is the single-GPU default)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, run every other measurement of the line (the legs below); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the loss, logits, parameters and gradients of the last step to DIR/<name>.npy")
     ap.add_argument("--variants", default=None,
-                    help="comma list of other mixers to time for a few steps each and report under \"variants\" "
+                    help="(--full) comma list of other mixers to time for a few steps each and report under \"variants\" "
                          "(default at 1 GPU with the fft mixer: permut,dwt_embed; 'none' disables)")
-    ap.add_argument("--cpu-steps", type=int, default=3, help="timed steps of the CPU baseline leg (bs = --batch)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--cpu-steps", type=int, default=3, help="(--full) timed steps of the CPU baseline leg (bs = --batch)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="(--full) skip the roofline / per-kernel pass")
     ap.add_argument("--dp-sequence", action="store_true",
                     help="one GPU: the headline is the launch sequence of a data-parallel rank (graph A -> all-reduce in a one-rank RCCL "
                          "group -> graph B) instead of the single graph")
     ap.add_argument("--dp-graph", action="store_true", help="N GPUs, permut mixer: use the two-graph rank step as well (default: eager, overlapped)")
-    ap.add_argument("--no-dp-sequence", action="store_true", help="skip the dp_sequence leg of the single-GPU line")
-    ap.add_argument("--no-script-leg", action="store_true", help="skip the as_script leg (the reference loop verbatim) of the single-GPU line")
-    ap.add_argument("--no-base224", action="store_true", help="skip the Base/224 student leg (BASELINE config 5, one GPU) of the default single-GPU line")
+    ap.add_argument("--no-dp-sequence", action="store_true", help="(--full) skip the dp_sequence leg of the single-GPU line")
+    ap.add_argument("--no-script-leg", action="store_true", help="(--full) skip the as_script leg (the reference loop verbatim) of the single-GPU line")
+    ap.add_argument("--no-base224", action="store_true", help="(--full) skip the Base/224 student leg (BASELINE config 5, one GPU) of the default single-GPU line")
     ap.add_argument("--no-every-row", action="store_true",
-                    help="skip the second graph-replayed measurement with the last layer's feed-forward half over every row (profiling runs)")
-    return ap.parse_args(argv)
+                    help="(--full) skip the second graph-replayed measurement with the last layer's feed-forward half over every row (profiling runs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:   # a plain run: the headline alone
+        args.no_roofline = args.no_cpu_baseline = args.no_every_row = args.no_dp_sequence = args.no_script_leg = args.no_base224 = True
+        args.variants = "none"
+    return args
 
 
 def _free_port():
@@ -270,6 +286,7 @@ class Job:
         self.reducer.zero_grad()
         with torch.autocast("cuda", dtype=torch.bfloat16, enabled=self.use_bf16):
             out = self.model(self.img)
+        self._out = out
         loss = self.crit(out, self.labels)
         loss.backward(self.one)   # a kept 1.0: backward() without it fills a fresh one every step (a launch)
         self.reducer.finish()
@@ -279,10 +296,45 @@ class Job:
             self.opt.step()  # (FusedAdamW's launch is bracketed by the C-ABI hook like every other kernel)
         return loss
 
+    @property
+    def out(self):
+        """the logits of the last step"""
+        return self.gstep.out if self.gstep is not None else self._out
+
     def close(self):
         if self.gstep is not None:
             self.gstep.close()
             self.gstep = None
+
+
+DUMP_BYTES = 60 * 2 ** 20   # every file of --dump-outputs together stays under 64 MB
+
+
+def dump_outputs(job, loss, out_dir):
+    """--dump-outputs: what the timed step computed in its last step, as float32 .npy files -- loss, logits (batch x classes), and
+    every trainable parameter after the update (params) with the gradient it was updated by (grads), both flattened in
+    named_parameters() order.  When the two flat vectors would not fit in DUMP_BYTES, both keep the same fixed, seeded sample of
+    positions (ascending), so two builds compare element for element.  Returns {name: shape}."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    params = [p for p in job.model.parameters() if p.requires_grad]
+    with torch.no_grad():
+        w = torch.cat([p.detach().reshape(-1).float() for p in params])
+        g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1).float() for p in params])
+        arrays = {"loss": loss.detach().float().reshape(()), "logits": job.out.detach().float()}
+        room = (DUMP_BYTES - sum(a.numel() * 4 for a in arrays.values())) // 8
+        if w.numel() > room:
+            idx = np.sort(np.random.default_rng(0).choice(w.numel(), room, replace=False))
+            idx = torch.from_numpy(idx).to(w.device)
+            w, g = w[idx], g[idx]
+        arrays.update(params=w, grads=g)
+        shapes = {}
+        for name, a in arrays.items():
+            a = a.cpu().numpy().astype(np.float32)
+            np.save(os.path.join(out_dir, name + ".npy"), a)
+            shapes[name] = list(a.shape)
+    return shapes
 
 
 def timed_region(job, sync, steps, warmup, eager=False):
@@ -484,6 +536,9 @@ def main():
             job = Job(args, args.mixer, dev, rank, launch=launch, stand_in=stand_in)
     elapsed, loss = timed_region(job, sync, args.steps, args.warmup)
     final_loss = float(loss.item())
+    dumped = None
+    if args.dump_outputs and rank == 0:   # before anything else runs a step: the ranks hold the same weights after the exchange
+        dumped = dump_outputs(job, loss, args.dump_outputs)
     # roofline pass: the SAME launch sequence as the timed region (in the graph modes: the captured sequence issued by the host, with the
     # layer weight gradients held and batched exactly as in the graph), same process, right after it, with HIP events recorded on the
     # launch stream around EVERY C-ABI launch.  Kept out of the headline timing because ~70 event pairs per step perturb it.  Every rank
@@ -512,7 +567,7 @@ def main():
             hip_ops.set_kernel_timer(None)
             hip_ops.TIME_HELD = False
             job.timer = None
-    if launch != "eager" and world == 1 and post_error is None:
+    if args.full and launch != "eager" and world == 1 and post_error is None:
         # the same launch sequence with the host issuing every launch: what the graph removes
         try:
             esteps = max(5, min(args.steps, 20))
@@ -569,6 +624,8 @@ def main():
             rec["gradient_exchange"] = ({"bytes": int(job.reducer.flat.numel() * 4), "calls_per_step": 1,
                                          "form": "one all-reduce (mean) of the flat fp32 gradient buffer between graph A and graph B"}
                                         if launch == "dp_graph" else None)
+        if dumped is not None:
+            rec["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if eager_fig is not None:
             rec["eager"] = eager_fig
         if post_error is not None:
@@ -604,7 +661,7 @@ def main():
         rec["config"]["last_layer_feed_forward"] = ("CLS rows only -- exact dead-row elimination: the model reads only the CLS row of the stack's output (reference spectre.py:198), so "
                                                   "the last layer's row-wise half (and its mixer's row 0) is computed for that row alone; logits, loss and EVERY parameter "
                                                   "gradient are those of the every-row computation (tests/test_gpu_bench_shapes.py runs both forms against the oracle); "
-                                                  "the every-row step is timed beside it under \"every_row_of_last_layer\" (SPV_FULL_LAST_LAYER=1 selects it)"
+                                                  "with --full the every-row step is timed beside it under \"every_row_of_last_layer\" (SPV_FULL_LAST_LAYER=1 selects it)"
                                                   if hip_ops.LAST_LAYER_CLS_ONLY else "every row")
         def guarded(fn, *a, **kw):
             """a side leg must never cost the headline its line: an exception becomes the leg's record"""

@@ -43,3 +43,24 @@ def test_parent_does_not_import_torch_before_spawning():
     assert "\nimport torch" not in head and "\nfrom torch" not in head
     body = src[src.index("def main():"):]
     assert body.index("self_launch(args, argv)") < body.index("import torch")
+
+
+def test_bench_plain_run_dumps_the_same_outputs_twice(tmp_path):
+    """--dump-outputs: the last timed step's loss, logits, parameters and gradients as float32 .npy files; with the same arguments the
+    inputs are the same from run to run (on the CPU stand-in the outputs are then bit-identical too)."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"d{i}"
+        r = _run(None, "--steps", "3", "--warmup", "1", "--batch", "16", "--dump-outputs", str(out))
+        assert r.returncode == 0, r.stderr[-3000:]
+        rec = json.loads(r.stdout)
+        assert rec["steps"] == 3 and rec["ms_per_step"] > 0 and set(rec["dumped_outputs"]["arrays"]) == {"loss", "logits", "params", "grads"}
+        dumps.append({k: np.load(out / f"{k}.npy") for k in rec["dumped_outputs"]["arrays"]})
+    assert all(v.dtype == np.float32 for v in dumps[0].values()) and dumps[0]["logits"].shape == (16, 100)
+    assert all(np.array_equal(dumps[0][k], dumps[1][k]) for k in dumps[0])
+
+
+def test_bench_rejects_zero_steps():
+    r = _run(None, "--steps", "0")
+    assert r.returncode != 0 and "--steps" in r.stderr

@@ -218,7 +218,7 @@ def test_bench_multi_rank_control_flow(tmp_path):
     env = dict(os.environ, SPV_BENCH_REHEARSAL="1")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--batch", "64", "--full"]
     r = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -240,7 +240,7 @@ def test_bench_single_gpu_line_has_variants_and_cpu_baseline():
     env = dict(os.environ)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SPV_BENCH_REHEARSAL"):
         env.pop(k, None)
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--batch", "64", "--cpu-steps", "1"]
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "6", "--warmup", "2", "--batch", "64", "--cpu-steps", "1", "--full"]
     r = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     # stdout is the ONE JSON line and nothing else (RCCL prints a version banner to stdout when the dp_sequence leg creates its
@@ -257,3 +257,29 @@ def test_bench_single_gpu_line_has_variants_and_cpu_baseline():
     assert rec["as_script"]["ms_per_step"] > 0 and rec["every_row_of_last_layer"]["ms_per_step"] > 0
     assert not [k for k in rec["kernels"] if k.get("frac", 0) > 1.0], [k for k in rec["kernels"] if k.get("frac", 0) > 1.0]
     assert rec["roofline"]["kernel"] in {k["kernel"] for k in rec["kernels"]}
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_is_the_headline_and_dumps_outputs(tmp_path):
+    """a plain run (no --full) times the headline alone, and --dump-outputs writes what the timed graph-replayed step computed in its
+    last step: loss, logits, every parameter after the update and its gradient, float32 and finite."""
+    import json
+    import subprocess
+    import numpy as np
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ)
+    for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "SPV_BENCH_REHEARSAL"):
+        env.pop(k, None)
+    out = tmp_path / "dump"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--steps", "4", "--warmup", "2", "--batch", "64", "--dump-outputs", str(out)]
+    r = subprocess.run(cmd, env=env, cwd=root, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+    assert r.returncode == 0, r.stderr[-2000:]
+    assert len(r.stdout.strip().splitlines()) == 1, r.stdout[:2000]
+    rec = json.loads(r.stdout)
+    assert rec["steps"] == 4 and rec["ms_per_step"] > 0 and rec["config"]["launch"].startswith("one HIP graph")
+    extras = {"roofline", "kernels", "eager", "variants", "every_row_of_last_layer", "dp_sequence", "as_script", "base224_student", "cpu_baseline"}
+    assert not extras & set(rec), extras & set(rec)
+    a = {k: np.load(out / f"{k}.npy") for k in ("loss", "logits", "params", "grads")}
+    assert all(v.dtype == np.float32 and np.isfinite(v).all() for v in a.values())
+    assert a["logits"].shape == (64, 100) and a["params"].shape == a["grads"].shape and a["params"].size > 10 ** 6
+    assert abs(float(a["loss"]) - rec["final_loss"]) <= 1e-4 and np.abs(a["grads"]).max() > 0

@@ -10,7 +10,7 @@ for i in $(seq 1 $R); do
   for E in "$A" "$B"; do
     base="SPV_LAB=1"
     if [ -f "$LABLIB" ] && [[ "$E" != *SPV_LIB_PATH* ]]; then base="$base SPV_LIB_PATH=$LABLIB"; fi
-    v=$(env $base $E python3 "$ROOT/bench.py" --no-cpu-baseline --variants none --no-roofline --no-every-row --no-dp-sequence --no-script-leg --steps 40 --warmup 10 "$@" 2>/dev/null | python3 -c "import sys,json; r=json.loads(sys.stdin.read()); print(r['ms_per_step'], r['eager']['ms_per_step'])")
+    v=$(env $base $E python3 "$ROOT/bench.py" --full --no-cpu-baseline --variants none --no-roofline --no-every-row --no-dp-sequence --no-script-leg --steps 40 --warmup 10 "$@" 2>/dev/null | python3 -c "import sys,json; r=json.loads(sys.stdin.read()); print(r['ms_per_step'], r['eager']['ms_per_step'])")
     echo "$E : graph/eager ms $v"
   done
 done

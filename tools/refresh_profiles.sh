@@ -8,8 +8,8 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd /tmp
-LEGS="--no-cpu-baseline --no-every-row --no-dp-sequence --no-script-leg --no-base224 --variants none"
-echo "== default line (what the driver runs)"; python3 "$ROOT/bench.py" > "$OUT/${TAG}_default_bench_line.json" 2> "$OUT/default_bench.err" || echo "default bench failed"
+LEGS="--full --no-cpu-baseline --no-every-row --no-dp-sequence --no-script-leg --no-base224 --variants none"
+echo "== full default line"; python3 "$ROOT/bench.py" --full > "$OUT/${TAG}_default_bench_line.json" 2> "$OUT/default_bench.err" || echo "default bench failed"
 for MIX in fft permut dwt_embed; do
   echo "== bench $MIX"; python3 "$ROOT/bench.py" --mixer $MIX $LEGS > "$OUT/${TAG}_${MIX}_bs512_bench.json" 2> "$OUT/${MIX}_bench.err" || echo "bench $MIX failed"
   echo "== stats $MIX"

@@ -12,7 +12,7 @@ if [ $# -gt 0 ]; then
   [ $rc -ne 0 ] && exit $rc
 fi
 cd /tmp
-L="--no-cpu-baseline --no-every-row --no-dp-sequence --no-script-leg --no-base224 --variants none"
+L="--full --no-cpu-baseline --no-every-row --no-dp-sequence --no-script-leg --no-base224 --variants none"
 python3 "$R/bench.py" --mixer $MIX $L > "$R/gpurun_out/${TAG}_${MIX}.json" 2> "$R/gpurun_out/${TAG}_${MIX}.err" || { echo "bench failed"; tail -5 "$R/gpurun_out/${TAG}_${MIX}.err"; exit 1; }
 rm -rf /tmp/prof_$MIX
 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/prof_$MIX -o p -- python3 "$R/bench.py" --mixer $MIX --steps 20 --warmup 5 --no-roofline $L > "$R/gpurun_out/${TAG}_trace.log" 2>&1
