@@ -48,7 +48,13 @@ enum {
     SPV_PATH_GEMM_STRIP_POOL = 11, /* gemm_nt_strip_kernel<*, 2 / 3>: data gradient + pooled-broadcast term (spv_gemm_nt_pool_bwd) */
     SPV_PATH_GEMM_ROWS = 13,     /* gemm_nt_rows_kernel: few-rows NT GEMM, one 32 x 32 tile per workgroup, no split-K (the CLS-only last layer) */
     SPV_PATH_PERMUT_ROW0 = 12,   /* spv_permut_row0_fwd / _bwd: MHPermutMix at token row 0 (the CLS-only last layer) */
-    SPV_PATH_COUNT = 16
+    SPV_PATH_SPECTRUM = 14,      /* spv_spectrum_log1p (SpectreBranch feature extractor) */
+    SPV_PATH_CONV_FWD = 15,      /* spv_conv3x3_fwd */
+    SPV_PATH_CONV_DGRAD = 16,    /* spv_conv3x3_dgrad */
+    SPV_PATH_CONV_WGRAD = 17,    /* spv_conv3x3_wgrad */
+    SPV_PATH_TOKEN_POOL = 18,    /* spv_token_pool_fwd */
+    SPV_PATH_TOKEN_UNPOOL = 19,  /* spv_token_pool_bwd */
+    SPV_PATH_COUNT = 24
 };
 long long spv_path_count(int which);
 const char* spv_last_error(void);
@@ -414,6 +420,33 @@ int spv_cross_entropy_fwd(const float* logits, const int64_t* labels, float* lse
                           int classes, void* stream);
 int spv_cross_entropy_bwd(const float* logits, const int64_t* labels, const float* lse, const float* grad_out,
                           float* dlogits, int rows, int classes, void* stream);
+
+/* ---- SpectreBranch feature extractor (spectre_vit/models/spectre_branch/spectre_branch.py:122-173) ----------------------------
+ * Stage maps are channels-last (B, H, W, C), dense.  The 3x3 convolution (valid, stride 1, spectre_branch.py:133) is an im2col GEMM
+ * on spv_gemm_nt with K ordered (c, ky, kx), the order of the PyTorch weight [Cout][Cin][3][3]; Kp = 9 Cin rounded up to 8.
+ *
+ * spv_spectrum_log1p: out[b][u][v][c] = log1p(|rfft2(img[b][c])[u][v]|), v < W/2 + 1 (spectre_branch.py:151); img fp32 NCHW, out in
+ * `dtype`.  One workgroup per plane, the plane's row transform in LDS: spv_spectrum_floats(H, W) floats, at most 16384. */
+int spv_spectrum_floats(int H, int W);
+int spv_spectrum_log1p(const float* img, void* out, int B, int C, int H, int W, int dtype, void* stream);
+/* y[(b,ho,wo)][co] = bias[co] + sum_k cols[(b,ho,wo)][k] w[co][k]: w [Cout][Kp] (zero past 9 Cin), cols a workspace of
+ * B (H-2) (W-2) Kp elements of `dtype`, y [B (H-2) (W-2)][Cout] in `dtype`. */
+int spv_conv3x3_fwd(const void* x, const void* w, const float* bias, void* y, void* cols, int B, int H, int W, int Cin, int Cout,
+                    int dtype, void* stream);
+/* dx [B H W][Cin] = the full correlation of dy [B (H-2) (W-2)][Cout] with the kernel: wd [Cin][Kd], wd[c][(co, ky, kx)] = w[co][c][ky][kx],
+ * Kd = 9 Cout rounded up to 8 (zero past 9 Cout); cols a workspace of B H W Kd elements. */
+int spv_conv3x3_dgrad(const void* dy, const void* wd, void* dx, void* cols, int B, int H, int W, int Cin, int Cout, int dtype,
+                      void* stream);
+/* dw [Cout][9 Cin] fp32 (the parameter's layout) = dy^T . im2col(x), a reduction over the M = B (H-2) (W-2) positions, split in
+ * `splits` K-slices (workspace >= splits Cout 9 Cin floats) and folded in a fixed order.  Workspaces: dyt Cout Mp and colst 9 Cin Mp
+ * elements of `dtype`, Mp = M rounded up to 8.  The bias gradient is spv_colsum of dy. */
+int spv_conv3x3_wgrad(const void* dy, const void* x, float* dw, void* dyt, void* colst, float* workspace, int splits, int B, int H,
+                      int W, int Cin, int Cout, int dtype, void* stream);
+/* AdaptiveAvgPool1d(T) over the flattened H W = L positions of y [B][L][C] (spectre_branch.py:144), token-major: out [B][T][ldo],
+ * window t = [floor(t L / T), ceil((t + 1) L / T)), columns C..ldo-1 written zero.  L < T is allowed (windows overlap). */
+int spv_token_pool_fwd(const void* y, void* out, int B, int L, int C, int T, int ldo, int dtype, void* stream);
+/* its transpose: dy [B][L][C] = sum over the windows holding l of dout[b][t][c] / |window t| (+ add [B][L][C] when not NULL) */
+int spv_token_pool_bwd(const void* dout, int ldo, const void* add, void* dy, int B, int L, int C, int T, int dtype, void* stream);
 
 #ifdef __cplusplus
 }

@@ -20,7 +20,8 @@ c_vp, c_i, c_i64, c_u64, c_f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ct
 
 # indices of include/spv.h's SPV_PATH_* enum (dispatch census, test aid)
 PATH = dict(gemm_strip=0, gemm_strip_acc=1, gemm_tn=2, tail_lc=3, tail_up=4, tail_ln=5, fnet_mfma=6, gather_lds=7, gemm_tn_dma=8, gemm_tn_wide=9,
-            gemm_tn_batch=10, gemm_strip_pool=11, permut_row0=12, gemm_rows=13)
+            gemm_tn_batch=10, gemm_strip_pool=11, permut_row0=12, gemm_rows=13,
+            spectrum=14, conv_fwd=15, conv_dgrad=16, conv_wgrad=17, token_pool=18, token_unpool=19)
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/spv.h one to one
 SIGNATURES = {
@@ -103,11 +104,18 @@ SIGNATURES = {
     "spv_adamw_multi": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp],
     "spv_fwht": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp],
     "spv_axpby": [c_vp, c_vp, c_vp, c_f, c_f, c_i64, c_i, c_vp],
+    "spv_spectrum_floats": [c_i, c_i],
+    "spv_spectrum_log1p": [c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp],
+    "spv_conv3x3_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
+    "spv_conv3x3_dgrad": [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
+    "spv_conv3x3_wgrad": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
+    "spv_token_pool_fwd": [c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
+    "spv_token_pool_bwd": [c_vp, c_i, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp],
 }
 _RESTYPES = {"spv_last_error": ctypes.c_char_p, "spv_path_count": ctypes.c_longlong, "spv_rowop_partial_floats": c_i64, "spv_fnet_workspace_floats": c_i64,
              "spv_fnet_twiddle_floats": c_i64, "spv_tail_ln_partial_floats": c_i64, "spv_permut_table_words": c_i64, "spv_small_sl_partial_floats": c_i64,
              "spv_cross_entropy_workspace_floats": c_i64}
-_NO_STATUS = set(_RESTYPES) | {"spv_version", "spv_fnet_ln_supported", "spv_fnet_cls_supported", "spv_tail_ln_supported", "spv_tail_up_supported", "spv_small_sl_supported", "spv_tail_bwd_parts", "spv_embed_bwd_groups", "spv_haar_ln_supported", "spv_permut_pool_supported"}
+_NO_STATUS = set(_RESTYPES) | {"spv_version", "spv_fnet_ln_supported", "spv_fnet_cls_supported", "spv_tail_ln_supported", "spv_tail_up_supported", "spv_small_sl_supported", "spv_tail_bwd_parts", "spv_embed_bwd_groups", "spv_haar_ln_supported", "spv_permut_pool_supported", "spv_spectrum_floats"}
 
 class FoldJob(ctypes.Structure):
     """spv_fold_job (include/spv.h): the fold of a tail backward's partial column sums, handed to spv_gemm_tn_fold"""

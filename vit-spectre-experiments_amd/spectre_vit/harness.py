@@ -27,6 +27,7 @@ from spectre_vit.distillation import SyntheticTeacher, distillation_loss
 from spectre_vit.dp import GradReducer, broadcast_module
 from spectre_vit.loss import CrossEntropyLoss
 from spectre_vit.models.spectre.spectre import SpectreViT
+from spectre_vit.models.spectre_branch.spectre_branch import SpectreBranch
 
 CIFAR_MEAN = (0.5071, 0.4867, 0.4408)  # train.py:109-112
 CIFAR_STD = (0.2675, 0.2565, 0.2761)
@@ -41,8 +42,14 @@ def seed_everything(seed: int):
         torch.cuda.manual_seed_all(seed)
 
 
-def build_model(c, mixer="permut", device="cuda"):
-    """train.py:48-59"""
+def build_model(c, mixer="permut", device="cuda", model="spectre"):
+    """train.py:48-59; model="spectre_branch" builds reference spectre_branch.py's SpectreBranch from the same config fields"""
+    if model == "spectre_branch":
+        return SpectreBranch(img_size=c.img_size, patch_size=c.patch_size, in_channels=c.in_channels, num_classes=c.num_classes,
+                             embed_dim=c.embed_dim, num_encoders=c.num_encoders, num_heads=c.num_heads, hidden_dim=c.hidden_dim,
+                             dropout=c.dropout, activation=c.activation).to(device)
+    if model != "spectre":
+        raise ValueError(f"unknown model {model!r} (spectre, spectre_branch)")
     return SpectreViT(img_size=c.img_size, patch_size=c.patch_size, in_channels=c.in_channels, num_classes=c.num_classes,
                       embed_dim=c.embed_dim, num_encoders=c.num_encoders, num_heads=c.num_heads, hidden_dim=c.hidden_dim,
                       dropout=c.dropout, activation=c.activation, mixer=mixer).to(device)
@@ -80,7 +87,7 @@ class SyntheticCifar:
 
 
 def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
-          use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False):
+          use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre"):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
@@ -97,7 +104,10 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         dist.init_process_group("nccl")
     device = torch.device("cuda", local_rank)
     seed_everything(seed)
-    model = build_model(c, mixer, device)
+    model_name = model
+    if model_name == "spectre_branch" and uint8_input:
+        raise ValueError("the SpectreBranch spectrum takes fp32 images: the uint8 NHWC input path is not built for it")
+    model = build_model(c, mixer, device, model_name)
     broadcast_module(model)
     batch_size = batch_size or c.batch_size
     train_set = SyntheticCifar(n_train, c, device, seed=seed)
@@ -206,6 +216,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="spectre_vit/configs/spectre_vit_cifar100.py")
     ap.add_argument("--mixer", default="permut")
+    ap.add_argument("--model", default="spectre", choices=("spectre", "spectre_branch"),
+                    help="spectre: SpectreViT (with --mixer); spectre_branch: SpectreBranch (spectre_branch.py)")
     ap.add_argument("--epochs", type=int, default=1)
     ap.add_argument("--steps-per-epoch", type=int, default=None)
     ap.add_argument("--batch-size", type=int, default=None)
@@ -213,7 +225,8 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the training step from HIP graphs (spectre_vit.graph)")
     ap.add_argument("--out", default="runs/spectre_vit")
     a = ap.parse_args()
-    train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph)
+    train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph,
+          model=a.model)
 
 
 if __name__ == "__main__":
