@@ -54,6 +54,8 @@ enum {
     SPV_PATH_CONV_WGRAD = 17,    /* spv_conv3x3_wgrad */
     SPV_PATH_TOKEN_POOL = 18,    /* spv_token_pool_fwd */
     SPV_PATH_TOKEN_UNPOOL = 19,  /* spv_token_pool_bwd */
+    SPV_PATH_ATTN_ROW0_FWD = 20, /* spv_attention_row0_fwd (the attention mixer's CLS-only last layer) */
+    SPV_PATH_ATTN_ROW0_BWD = 21, /* spv_attention_row0_bwd */
     SPV_PATH_COUNT = 24
 };
 long long spv_path_count(int which);
@@ -385,6 +387,18 @@ int spv_attention_fwd(const void* qkv, void* ctx, void* probs, int seqs, int len
                       float p_drop, uint64_t seed, void* stream);
 int spv_attention_bwd(const void* dctx, const void* qkv, const void* probs, void* dscores, void* dqkv, int seqs, int len,
                       int heads, int head_dim, int dtype, float p_drop, uint64_t seed, void* stream);
+/* The same attention for query row 0 only (SpectreViT(mixer="attention"): its last layer's output is read at the CLS row alone):
+ * ctx0[b, h] = dropout(softmax(q0[b, h] . K[b, :, h]^T / sqrt(head_dim))) . V[b, :, h], with the dropout mask spv_attention_fwd
+ * applies at query row 0 of the same (sample, head) for the same seed.  q0 / ctx0 / dctx0 / dq0 [batch, E] dense (E = heads *
+ * head_dim); K, V [batch, len, E] at row stride ldkv elements (a packed [batch, len, 2E] k|v projection: ldkv = 2E); dK, dV at row
+ * stride ldd, written densely (every key row); probs [batch, heads, len] fp32 = the softmax before the mask (written by the forward
+ * unless NULL, read by the backward).  E a multiple of 8 (bf16) / 4 (fp32) and <= 256 times that, ldkv / ldd likewise, K / V / dK /
+ * dV 16-byte aligned, heads * len <= 8192.  Deterministic: every output element has one writer, no atomics. */
+int spv_attention_row0_fwd(const void* q0, const void* k, const void* v, int ldkv, void* ctx0, float* probs, int batch, int len,
+                           int heads, int head_dim, int dtype, float p_drop, uint64_t seed, void* stream);
+int spv_attention_row0_bwd(const void* dctx0, const void* q0, const void* k, const void* v, int ldkv, const float* probs, void* dq0,
+                           void* dk, void* dv, int ldd, int batch, int len, int heads, int head_dim, int dtype, float p_drop,
+                           uint64_t seed, void* stream);
 
 /* ---- generic helpers used by the module mirror ------------------------------------------------------
  * GELU (TransformerEncoderLayer MLP, vit.py:30-36), column sums (bias / position-embedding gradients;

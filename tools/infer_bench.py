@@ -2,7 +2,7 @@
 """Inference latency / throughput of the mirrored models -- counterpart of the reference's spectre_vit/repl/test.py:30-62
 (which times forward passes without synchronising the device; here every sample is bracketed by HIP events).
 
-    python tools/infer_bench.py [--mixer fft|permut|dwt_embed|dwt_token] [--model spectre|vit] [--batches 1,8,64,512]
+    python tools/infer_bench.py [--mixer fft|permut|dwt_embed|dwt_token|attention] [--model spectre|vit] [--batches 1,8,64,512]
 """
 import argparse
 import json

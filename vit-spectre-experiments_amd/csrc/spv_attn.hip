@@ -943,3 +943,289 @@ extern "C" int spv_attention_bwd(const void* dctx, const void* qkv, const void* 
 }
 
 int spv_seed_ptr_set_attn(const unsigned long long* p) { return spv_seed_symbol_set(p); }
+
+// ------------------------------------------------------------------------------------------------------------------
+// Single-query-row attention: the CLS-only last layer of SpectreViT(mixer="attention").  The model reads row 0 of the last layer's
+// output and nothing else, so that layer needs the attention of query row 0 only -- against every key and value row.
+//   forward   ctx0[b, h] = dropout(softmax(q0[b, h] . K[b, :, h]^T / sqrt(hd))) . V[b, :, h]
+//   backward  dq0, and the dense dK / dV (every key row gets a gradient)
+// One workgroup per sample; it reads the sample's K and V rows whole (16-byte loads), so one head's short runs (2 hd bytes) inside the
+// packed [B, N, 2E] projection output do not cost a wave each.  Phases, each a pass over LDS or over the sample's rows:
+//   1 (score) lanes over (key row, head) pairs: s[h][n] = q0[h] . K[n, h] (forward) / dp[h][n] = dctx0[h] . V[n, h] (backward)
+//   2 (softmax) one wave per head over n: the probabilities (saved, unmasked, fp32) and their dropout-masked copy
+//   3 (rows) lanes over 16-byte column groups x row slices: ctx0 = P V (forward); dq0 = dS K, dK = dS q0, dV = P dctx0 (backward),
+//     the row-slice partial sums of ctx0 / dq0 folded in a fixed order in LDS.  No atomics: every output element has one writer.
+// The dropout mask is the attention core's at query row 0 of the same (sample, head): dropout_row_key(live_seed(seed),
+// attn_row(b * heads + h, len, 0)), column = key index.
+namespace {
+
+constexpr int R0T = 256;        // threads per workgroup
+constexpr int R0_MAX_HN = 8192; // heads * len: the backward keeps two [heads][len] fp32 rows of the sample in LDS
+
+template <typename T> struct R0V { static constexpr int CV = 16 / (int)sizeof(T); };   // elements per 16-byte group
+
+__device__ __forceinline__ void r0_ld16(const float* p, float (&v)[4]) {
+    const float4 t = *reinterpret_cast<const float4*>(p);
+    v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+}
+__device__ __forceinline__ void r0_ld16(const bf16_t* p, float (&v)[8]) {
+    const uint4 t = *reinterpret_cast<const uint4*>(p);
+    const unsigned w[4] = {t.x, t.y, t.z, t.w};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        v[2 * i] = __uint_as_float(w[i] << 16);
+        v[2 * i + 1] = __uint_as_float(w[i] & 0xffff0000u);
+    }
+}
+__device__ __forceinline__ void r0_st16(float* p, const float (&v)[4]) { *reinterpret_cast<float4*>(p) = make_float4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ void r0_st16(bf16_t* p, const float (&v)[8]) {
+    uint4 t;
+    t.x = pack_bf16x2(v[0], v[1]);
+    t.y = pack_bf16x2(v[2], v[3]);
+    t.z = pack_bf16x2(v[4], v[5]);
+    t.w = pack_bf16x2(v[6], v[7]);
+    *reinterpret_cast<uint4*>(p) = t;
+}
+
+// phase 1: out[h * len + n] = sum_d a[h * hd + d] * rows[n * ld + h * hd + d] (a: fp32 in LDS), lanes over (n, h) pairs
+template <typename T>
+__device__ __forceinline__ void r0_head_dots(const float* a, const T* __restrict__ rows, int ld, float* out, int len, int heads, int hd) {
+    constexpr int CV = R0V<T>::CV;
+    const bool vec = hd % CV == 0;
+    for (int idx = threadIdx.x; idx < len * heads; idx += R0T) {
+        const int n = idx / heads, h = idx % heads;
+        const T* r = rows + (size_t)n * ld + h * hd;
+        const float* q = a + h * hd;
+        float acc = 0.0f;
+        if (vec) {
+            for (int d = 0; d < hd; d += CV) {
+                float v[CV];
+                r0_ld16(r + d, v);
+#pragma unroll
+                for (int c = 0; c < CV; ++c) acc = fmaf(q[d + c], v[c], acc);
+            }
+        } else {
+            for (int d = 0; d < hd; ++d) acc = fmaf(q[d], io<T>::ld(r + d), acc);
+        }
+        out[h * len + n] = acc;
+    }
+}
+
+// the fixed-order fold of phase 3: red[r][e] (r < rp) -> sum over r, for e = threadIdx.x (+ R0T ...)
+__device__ __forceinline__ float r0_fold(const float* red, int rp, int E, int e) {
+    float s = 0.0f;
+    for (int r = 0; r < rp; ++r) s += red[r * E + e];
+    return s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(R0T) void attn_row0_fwd_kernel(const T* __restrict__ q0, const T* __restrict__ kg, const T* __restrict__ vg,
+                                                             int ldkv, T* __restrict__ ctx0, float* __restrict__ probs, int len, int heads,
+                                                             int hd, float p_drop, uint64_t seed) {
+    constexpr int CV = R0V<T>::CV;
+    extern __shared__ __attribute__((aligned(16))) float r0_lds[];
+    const int E = heads * hd, G = E / CV, rp = R0T / G;
+    float* qs = r0_lds;               // [E]   q0 * 1/sqrt(hd)
+    float* ps = qs + E;               // [heads][len] scores, then masked probabilities
+    float* red = ps + heads * len;    // [rp][E] row-slice partial sums
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t sbase = (size_t)b * len * ldkv;
+    const float scale = rsqrtf((float)hd);
+    for (int e = tid; e < E; e += R0T) qs[e] = io<T>::ld(q0 + (size_t)b * E + e) * scale;
+    __syncthreads();
+    r0_head_dots(qs, kg + sbase, ldkv, ps, len, heads, hd);
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    const float inv_keep = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
+    for (int h = wave; h < heads; h += R0T / 64) {
+        float* row = ps + h * len;
+        float mx = -INFINITY;
+        for (int n = lane; n < len; n += 64) mx = fmaxf(mx, row[n]);
+        mx = wave_max(mx);
+        float sum = 0.0f;
+        for (int n = lane; n < len; n += 64) {
+            const float e = __expf(row[n] - mx);
+            row[n] = e;
+            sum += e;
+        }
+        sum = wave_sum(sum);
+        const float inv = 1.0f / sum;
+        const unsigned rkey = p_drop > 0.0f ? dropout_row_key(live_seed(seed), attn_row(b * heads + h, len, 0)) : 0u;
+        for (int n = lane; n < len; n += 64) {
+            const float p = row[n] * inv;
+            if (probs) probs[((size_t)b * heads + h) * len + n] = p;
+            row[n] = p_drop > 0.0f ? p * dropout_scale(rkey, (unsigned)n, p_drop, inv_keep) : p;
+        }
+    }
+    __syncthreads();
+    const int g = tid % G, r = tid / G;
+    if (r < rp) {
+        const int e0 = g * CV;
+        int hc[CV];
+#pragma unroll
+        for (int c = 0; c < CV; ++c) hc[c] = (e0 + c) / hd * len;
+        float acc[CV];
+#pragma unroll
+        for (int c = 0; c < CV; ++c) acc[c] = 0.0f;
+        for (int n = r; n < len; n += rp) {
+            float v[CV];
+            r0_ld16(vg + sbase + (size_t)n * ldkv + e0, v);
+#pragma unroll
+            for (int c = 0; c < CV; ++c) acc[c] = fmaf(ps[hc[c] + n], v[c], acc[c]);
+        }
+#pragma unroll
+        for (int c = 0; c < CV; ++c) red[r * E + e0 + c] = acc[c];
+    }
+    __syncthreads();
+    for (int e = tid; e < E; e += R0T) io<T>::st(ctx0 + (size_t)b * E + e, r0_fold(red, rp, E, e));
+}
+
+template <typename T>
+__global__ __launch_bounds__(R0T) void attn_row0_bwd_kernel(const T* __restrict__ dctx0, const T* __restrict__ q0, const T* __restrict__ kg,
+                                                             const T* __restrict__ vg, int ldkv, const float* __restrict__ probs,
+                                                             T* __restrict__ dq0, T* __restrict__ dk, T* __restrict__ dv, int ldd, int len,
+                                                             int heads, int hd, float p_drop, uint64_t seed) {
+    constexpr int CV = R0V<T>::CV;
+    extern __shared__ __attribute__((aligned(16))) float r0_lds[];
+    const int E = heads * hd, G = E / CV, rp = R0T / G;
+    float* gs = r0_lds;               // [E]   dctx0
+    float* qs = gs + E;               // [E]   q0
+    float* dss = qs + E;              // [heads][len] dP, then dS (scaled)
+    float* pms = dss + heads * len;   // [heads][len] masked probabilities
+    float* red = pms + heads * len;   // [rp][E]
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const size_t sbase = (size_t)b * len * ldkv, dbase = (size_t)b * len * ldd;
+    const float scale = rsqrtf((float)hd);
+    for (int e = tid; e < E; e += R0T) {
+        gs[e] = io<T>::ld(dctx0 + (size_t)b * E + e);
+        qs[e] = io<T>::ld(q0 + (size_t)b * E + e);
+    }
+    __syncthreads();
+    r0_head_dots(gs, vg + sbase, ldkv, dss, len, heads, hd);
+    __syncthreads();
+    const int lane = tid & 63, wave = tid >> 6;
+    const float inv_keep = p_drop > 0.0f ? 1.0f / (1.0f - p_drop) : 1.0f;
+    for (int h = wave; h < heads; h += R0T / 64) {
+        float* drow = dss + h * len;
+        float* prow = pms + h * len;
+        const float* pg = probs + ((size_t)b * heads + h) * len;
+        const unsigned rkey = p_drop > 0.0f ? dropout_row_key(live_seed(seed), attn_row(b * heads + h, len, 0)) : 0u;
+        float dot = 0.0f;
+        for (int n = lane; n < len; n += 64) {
+            const float m = p_drop > 0.0f ? dropout_scale(rkey, (unsigned)n, p_drop, inv_keep) : 1.0f;
+            const float p = pg[n], dp = drow[n] * m;
+            drow[n] = dp;
+            prow[n] = p * m;
+            dot += p * dp;
+        }
+        dot = wave_sum(dot);
+        for (int n = lane; n < len; n += 64) drow[n] = pg[n] * (drow[n] - dot) * scale;
+    }
+    __syncthreads();
+    const int g = tid % G, r = tid / G;
+    if (r < rp) {
+        const int e0 = g * CV;
+        int hc[CV];
+        float qv[CV], gv[CV], acc[CV];
+#pragma unroll
+        for (int c = 0; c < CV; ++c) {
+            hc[c] = (e0 + c) / hd * len;
+            qv[c] = qs[e0 + c];
+            gv[c] = gs[e0 + c];
+            acc[c] = 0.0f;
+        }
+        for (int n = r; n < len; n += rp) {
+            float kv[CV], o[CV];
+            r0_ld16(kg + sbase + (size_t)n * ldkv + e0, kv);
+#pragma unroll
+            for (int c = 0; c < CV; ++c) {
+                const float ds = dss[hc[c] + n];
+                acc[c] = fmaf(ds, kv[c], acc[c]);
+                o[c] = ds * qv[c];
+            }
+            r0_st16(dk + dbase + (size_t)n * ldd + e0, o);
+#pragma unroll
+            for (int c = 0; c < CV; ++c) o[c] = pms[hc[c] + n] * gv[c];
+            r0_st16(dv + dbase + (size_t)n * ldd + e0, o);
+        }
+#pragma unroll
+        for (int c = 0; c < CV; ++c) red[r * E + e0 + c] = acc[c];
+    }
+    __syncthreads();
+    for (int e = tid; e < E; e += R0T) io<T>::st(dq0 + (size_t)b * E + e, r0_fold(red, rp, E, e));
+}
+
+int r0_check(const char* name, int batch, int len, int heads, int hd, int dtype, int ld, const char* ldname, float p_drop,
+             const void* const* vecs, int nvec) {
+    SPV_CHECK(batch > 0 && len > 0 && heads > 0 && hd > 0, "%s: empty problem batch=%d len=%d heads=%d head_dim=%d", name, batch, len,
+              heads, hd);
+    SPV_CHECK(dtype == SPV_F32 || dtype == SPV_BF16, "%s: bad dtype %d", name, dtype);
+    const int cv = dtype == SPV_BF16 ? 8 : 4, E = heads * hd;
+    SPV_CHECK(E % cv == 0, "%s: heads * head_dim = %d must be a multiple of %d (16-byte column groups)", name, E, cv);
+    SPV_CHECK(E <= R0T * cv, "%s: heads * head_dim = %d > %d", name, E, R0T * cv);
+    SPV_CHECK((long long)heads * len <= R0_MAX_HN, "%s: heads * len = %lld > %d", name, (long long)heads * len, R0_MAX_HN);
+    SPV_CHECK(ld >= E && ld % cv == 0, "%s: %s=%d must be >= %d and a multiple of %d", name, ldname, ld, E, cv);
+    SPV_CHECK(p_drop >= 0.0f && p_drop < 1.0f, "%s: p_drop=%f outside [0, 1)", name, p_drop);
+    for (int i = 0; i < nvec; ++i)
+        SPV_CHECK(vecs[i] && ((uintptr_t)vecs[i] & 15) == 0, "%s: K / V / dK / dV pointers must be non-NULL and 16-byte aligned", name);
+    return 0;
+}
+
+size_t r0_lds_fwd(int len, int heads, int hd, int cv) {
+    const int E = heads * hd;
+    return ((size_t)E + (size_t)heads * len + (size_t)(R0T / (E / cv)) * E) * sizeof(float);
+}
+size_t r0_lds_bwd(int len, int heads, int hd, int cv) {
+    const int E = heads * hd;
+    return ((size_t)2 * E + (size_t)2 * heads * len + (size_t)(R0T / (E / cv)) * E) * sizeof(float);
+}
+
+}  // namespace
+
+extern "C" int spv_attention_row0_fwd(const void* q0, const void* k, const void* v, int ldkv, void* ctx0, float* probs, int batch, int len,
+                                      int heads, int head_dim, int dtype, float p_drop, uint64_t seed, void* stream) {
+    const char* name = "spv_attention_row0_fwd";
+    const void* vecs[2] = {k, v};
+    if (r0_check(name, batch, len, heads, head_dim, dtype, ldkv, "ldkv", p_drop, vecs, 2)) return 1;
+    SPV_CHECK(q0 && ctx0, "%s: q0 / ctx0 must be non-NULL", name);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int cv = dtype == SPV_BF16 ? 8 : 4;
+    const size_t lds = r0_lds_fwd(len, heads, head_dim, cv);
+    if (dtype == SPV_BF16) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_row0_fwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(attn_row0_fwd_kernel<bf16_t>, dim3(batch), dim3(R0T), lds, st, (const bf16_t*)q0, (const bf16_t*)k, (const bf16_t*)v,
+                           ldkv, (bf16_t*)ctx0, probs, len, heads, head_dim, p_drop, seed);
+    } else {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_row0_fwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(attn_row0_fwd_kernel<float>, dim3(batch), dim3(R0T), lds, st, (const float*)q0, (const float*)k, (const float*)v,
+                           ldkv, (float*)ctx0, probs, len, heads, head_dim, p_drop, seed);
+    }
+    SPV_LAUNCH_CHECK(name);
+    SPV_COUNT_PATH(SPV_PATH_ATTN_ROW0_FWD);
+    return 0;
+}
+
+extern "C" int spv_attention_row0_bwd(const void* dctx0, const void* q0, const void* k, const void* v, int ldkv, const float* probs, void* dq0,
+                                      void* dk, void* dv, int ldd, int batch, int len, int heads, int head_dim, int dtype, float p_drop,
+                                      uint64_t seed, void* stream) {
+    const char* name = "spv_attention_row0_bwd";
+    const void* vecs[4] = {k, v, dk, dv};
+    if (r0_check(name, batch, len, heads, head_dim, dtype, ldkv, "ldkv", p_drop, vecs, 4)) return 1;
+    const int cv = dtype == SPV_BF16 ? 8 : 4;
+    SPV_CHECK(ldd >= heads * head_dim && ldd % cv == 0, "%s: ldd=%d must be >= %d and a multiple of %d", name, ldd, heads * head_dim, cv);
+    SPV_CHECK(dctx0 && q0 && probs && dq0, "%s: dctx0 / q0 / probs / dq0 must be non-NULL", name);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const size_t lds = r0_lds_bwd(len, heads, head_dim, cv);
+    if (dtype == SPV_BF16) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_row0_bwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(attn_row0_bwd_kernel<bf16_t>, dim3(batch), dim3(R0T), lds, st, (const bf16_t*)dctx0, (const bf16_t*)q0, (const bf16_t*)k,
+                           (const bf16_t*)v, ldkv, probs, (bf16_t*)dq0, (bf16_t*)dk, (bf16_t*)dv, ldd, len, heads, head_dim, p_drop, seed);
+    } else {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&attn_row0_bwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        hipLaunchKernelGGL(attn_row0_bwd_kernel<float>, dim3(batch), dim3(R0T), lds, st, (const float*)dctx0, (const float*)q0, (const float*)k,
+                           (const float*)v, ldkv, probs, (float*)dq0, (float*)dk, (float*)dv, ldd, len, heads, head_dim, p_drop, seed);
+    }
+    SPV_LAUNCH_CHECK(name);
+    SPV_COUNT_PATH(SPV_PATH_ATTN_ROW0_BWD);
+    return 0;
+}

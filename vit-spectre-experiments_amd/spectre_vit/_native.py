@@ -21,7 +21,7 @@ c_vp, c_i, c_i64, c_u64, c_f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ct
 # indices of include/spv.h's SPV_PATH_* enum (dispatch census, test aid)
 PATH = dict(gemm_strip=0, gemm_strip_acc=1, gemm_tn=2, tail_lc=3, tail_up=4, tail_ln=5, fnet_mfma=6, gather_lds=7, gemm_tn_dma=8, gemm_tn_wide=9,
             gemm_tn_batch=10, gemm_strip_pool=11, permut_row0=12, gemm_rows=13,
-            spectrum=14, conv_fwd=15, conv_dgrad=16, conv_wgrad=17, token_pool=18, token_unpool=19)
+            spectrum=14, conv_fwd=15, conv_dgrad=16, conv_wgrad=17, token_pool=18, token_unpool=19, attn_row0_fwd=20, attn_row0_bwd=21)
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/spv.h one to one
 SIGNATURES = {
@@ -96,6 +96,8 @@ SIGNATURES = {
     "spv_dropout": [c_vp, c_vp, c_i64, c_f, c_u64, c_i, c_vp],
     "spv_attention_fwd": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_u64, c_vp],
     "spv_attention_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_u64, c_vp],
+    "spv_attention_row0_fwd": [c_vp, c_vp, c_vp, c_i, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_u64, c_vp],
+    "spv_attention_row0_bwd": [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_u64, c_vp],
     "spv_gelu_fwd": [c_vp, c_vp, c_i64, c_i, c_vp],
     "spv_gelu_bwd": [c_vp, c_vp, c_vp, c_i64, c_i, c_vp],
     "spv_colsum": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp],

@@ -597,7 +597,7 @@ def start_held_wgrads():
 def _hold_wgrad(dh, x, dw, sink, rows, n, k, fold, fold_sunk):
     """hold a layer weight gradient for the batch launch at the end of this backward pass (see _held_wgrads).  False: not held."""
     global _held_task
-    if not (_WGRAD_HOLD and _hold_ok() and sink is not None and dw.data_ptr() == sink.view.data_ptr() and (fold is None or fold_sunk)):
+    if not (_WGRAD_HOLD and _hold_ok() and _in_sink(dw, sink) and (fold is None or fold_sunk)):
         return False
     task = _graph_task_id()
     if task < 0:
@@ -610,6 +610,14 @@ def _hold_wgrad(dh, x, dw, sink, rows, n, k, fold, fold_sunk):
     f = None if fold is None else (fold[0], tuple(o.data_ptr() for o in fold[1]), fold[2], fold[3])   # raw sink addresses, as _hold_fold
     _held_wgrads.append((dh, x, dw.data_ptr(), rows, n, k, f))
     return True
+
+
+def _in_sink(dw, sink):
+    """dw is the parameter's sink slot or a row range of it (memory that outlives the node: it may be written at the end of the pass)"""
+    if sink is None:
+        return False
+    base = sink.view.data_ptr()
+    return base <= dw.data_ptr() and dw.data_ptr() + dw.numel() * dw.element_size() <= base + sink.view.numel() * sink.view.element_size()
 
 
 def flush_held_folds():
@@ -660,12 +668,13 @@ def _sunk(outs, sinks):
     return all(sk is not None and o.data_ptr() == sk.view.data_ptr() for o, sk in zip(outs, sinks))
 
 
-def _weight_grad(dh, x, rows, n, k, sink=None, fold=None, fold_sunk=False):
+def _weight_grad(dh, x, rows, n, k, sink=None, fold=None, fold_sunk=False, out=None):
     """dW[n,k] = dh[rows,n]^T . x[rows,k], split-K over rows.  bf16: TN kernel straight from the row-major activations
     (transposing LDS reads); fp32 (parity path): NT kernel over explicit transposes.  fold (a _fold_job, only when
-    _fold_rides): the same layer's dgamma / dbeta / dbias fold, run as extra workgroups of the split-K reduce."""
+    _fold_rides): the same layer's dgamma / dbeta / dbias fold, run as extra workgroups of the split-K reduce.
+    out: a contiguous [n, k] row range of a larger gradient to write instead (held like the whole slot when it lies in `sink`)."""
     dev = dh.device
-    dw = _grad_buf(sink, (n, k), dev)
+    dw = out if out is not None else _grad_buf(sink, (n, k), dev)
     tiles = ((n + 127) // 128) * ((k + 127) // 128)
     # ~2 workgroups per CU: measured optimum on the 768 x 512 x 33280 weight gradient (21 splits: 51 us; 12: 69; 42: 56; 64: 64)
     splits = max(1, min(512 // tiles, (rows + 511) // 512 if tiles >= 8 else (rows + 63) // 64))
@@ -1545,6 +1554,123 @@ class AttentionFn(torch.autograd.Function):
         _native.call("spv_attention_bwd", _p(d), _p(q), _p(probs), _p(ds), _p(dqkv), seqs, length, heads, hd, _dt(q), p_drop, seed,
                      _stream())
         return dqkv, None, None
+
+
+def attn_row0_ok(x, heads):
+    """the single-query-row kernels take x (B, N, E) with `heads` heads (include/spv.h spv_attention_row0_fwd)"""
+    E, cv = x.shape[-1], (8 if x.dtype == torch.bfloat16 else 4)
+    return E % heads == 0 and E % cv == 0 and E <= 256 * cv and heads * x.shape[1] <= 8192
+
+
+def _row0_fwd(q0, kv, heads, p_drop, seed):
+    """ctx0 (B, E) and the saved probabilities (B, heads, N) fp32 of query row 0 against kv (B, N, 2E) = [k | v]"""
+    B, N, E2 = kv.shape
+    E = E2 // 2
+    ctx0 = torch.empty((B, E), dtype=q0.dtype, device=q0.device)
+    probs = torch.empty((B, heads, N), dtype=torch.float32, device=q0.device)
+    _native.call("spv_attention_row0_fwd", _p(q0), _p(kv), _p(kv) + E * kv.element_size(), E2, _p(ctx0), _p(probs), B, N, heads,
+                 E // heads, _dt(q0), float(p_drop), seed, _stream())
+    return ctx0, probs
+
+
+def _row0_bwd(dctx0, q0, kv, probs, heads, p_drop, seed):
+    """(dq0 (B, E), dkv (B, N, 2E) = [dk | dv], every key row written)"""
+    B, N, E2 = kv.shape
+    E = E2 // 2
+    dq0 = torch.empty_like(q0)
+    dkv = torch.empty_like(kv)
+    _native.call("spv_attention_row0_bwd", _p(dctx0), _p(q0), _p(kv), _p(kv) + E * kv.element_size(), E2, _p(probs), _p(dq0), _p(dkv),
+                 _p(dkv) + E * dkv.element_size(), E2, B, N, heads, E // heads, _dt(q0), float(p_drop), seed, _stream())
+    return dq0, dkv
+
+
+def _grad_in(g, like):
+    """an incoming gradient in the compute dtype and dense (zeros when autograd hands None)"""
+    if g is None:
+        return torch.zeros_like(like)
+    return g.to(like.dtype).contiguous()
+
+
+class AttentionRow0Fn(torch.autograd.Function):
+    """ctx0 = dropout(softmax(q0 k^T / sqrt(hd))) v for query row 0 only: q0 (B, E), kv (B, N, 2E) = [k | v] -> (B, E).  The same
+    numbers, dropout mask included, as row 0 of AttentionFn over [q | k | v] with the same seed."""
+
+    @staticmethod
+    def forward(ctx, q0, kv, heads, p_drop):
+        _require_gpu(q0, kv)
+        q0, kv = q0.contiguous(), kv.contiguous()
+        seed = _new_seed() if p_drop > 0.0 else 0
+        ctx0, probs = _row0_fwd(q0, kv, heads, p_drop, seed)
+        ctx.save_for_backward(q0, kv, probs)
+        ctx.meta = (heads, float(p_drop), seed)
+        return ctx0
+
+    @staticmethod
+    def backward(ctx, dctx0):
+        q0, kv, probs = ctx.saved_tensors
+        heads, p_drop, seed = ctx.meta
+        dq0, dkv = _row0_bwd(_grad_in(dctx0, q0), q0, kv, probs, heads, p_drop, seed)
+        return dq0, dkv, None, None
+
+
+class AttnClsFn(torch.autograd.Function):
+    """The attention mixer's part of a CLS-only last layer (SelfAttentionMixer.forward_cls): x (B, N, E) -> (attention context of
+    query row 0 (B, E), x[:, 0, :] (B, E)).  K and V are projected over every row with rows E..3E of in_proj_weight (one GEMM, N = 2E),
+    Q at the CLS rows only with rows 0..E; the out-projection is the caller's (a plain Linear over B rows).  Backward: ONE dense input
+    gradient, and in_proj's gradient as one (3E, E) tensor whose two row blocks are written by the two weight-gradient GEMMs."""
+
+    @staticmethod
+    def forward(ctx, x, w_in, b_in, heads, p_drop):
+        _require_gpu(x, w_in)
+        B, N, E = x.shape
+        xc = x.contiguous()
+        dt = xc.dtype
+        x2 = xc.view(B * N, E)
+        x0 = xc[:, 0, :].contiguous()
+        wc, wt = _shadows.get(w_in, dt)   # (the cached copies of the whole parameter, sliced: the cache is keyed on the parameter)
+        bq = bk = None
+        if b_in is not None:
+            bq, bk = b_in[:E], b_in[E:]
+        kv = torch.empty((B, N, 2 * E), dtype=dt, device=xc.device)
+        _gemm(x2, wc[E:], bk, kv, B * N, 2 * E, E, E, E, 2 * E)
+        q0 = torch.empty((B, E), dtype=dt, device=xc.device)
+        _gemm(x0, wc[:E], bq, q0, B, E, E, E, E, E)
+        seed = _new_seed() if p_drop > 0.0 else 0
+        ctx0, probs = _row0_fwd(q0, kv, heads, p_drop, seed)
+        ctx.save_for_backward(x2, x0, q0, kv, probs)
+        ctx.wt = wt
+        ctx.sinks = (_sink(w_in), _sink(b_in) if b_in is not None else None)
+        ctx.meta = (B, N, E, heads, float(p_drop), seed, b_in is not None)
+        return ctx0, x0
+
+    @staticmethod
+    def backward(ctx, dctx0, dx0):
+        x2, x0, q0, kv, probs = ctx.saved_tensors
+        B, N, E, heads, p_drop, seed, has_bias = ctx.meta
+        dev = x2.device
+        dq0, dkv = _row0_bwd(_grad_in(dctx0, q0), q0, kv, probs, heads, p_drop, seed)
+        dkv2 = dkv.view(B * N, 2 * E)
+        dw = db = None
+        if ctx.needs_input_grad[1]:
+            dw = _grad_buf(ctx.sinks[0], (3 * E, E), dev)
+            _weight_grad(dq0, x0, B, E, E, ctx.sinks[0], out=dw[:E])
+            _weight_grad(dkv2, x2, B * N, 2 * E, E, ctx.sinks[0], out=dw[E:])
+        if has_bias and ctx.needs_input_grad[2]:
+            db = _grad_buf(ctx.sinks[1], (3 * E,), dev)
+            part = torch.empty((min(B * N, 512) * 2 * E,), dtype=torch.float32, device=dev)
+            _native.call("spv_colsum", _p(dq0), _p(db), _p(part), B, E, _dt(dq0), _stream())
+            _native.call("spv_colsum", _p(dkv2), _p(db) + 4 * E, _p(part), B * N, 2 * E, _dt(dkv2), _stream())
+        dx = None
+        if ctx.needs_input_grad[0]:
+            wt = ctx.wt
+            dx = torch.empty((B, N, E), dtype=x2.dtype, device=dev)
+            # dx = dkv . W_kv over every row, then row 0 += dq0 . W_q + the CLS row's own gradient
+            _gemm(dkv2, wt[:, E:], None, dx, B * N, E, 2 * E, 2 * E, wt.shape[1], E)
+            _gemm(dq0, wt, None, dx, B, E, E, E, wt.shape[1], N * E, accumulate=1)
+            if dx0 is not None:
+                dx[:, 0, :] += dx0.to(dx.dtype)
+        join_side_stream()
+        return dx, dw, db, None, None
 
 
 # ------------------------------------------------------------------------------------------------

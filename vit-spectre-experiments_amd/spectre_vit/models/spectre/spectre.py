@@ -3,8 +3,9 @@
 Class names, constructor arguments, forward signatures and state_dict keys follow the reference
 (SURVEY.md 8b); the arithmetic runs in libspv_hip.so.  One labelled extension: ``mixer=`` on
 SpectreViT / SpectreEncoderLayer selects the token mixer ("permut" = the reference's HEAD default
-MHPermutMix, "fft" = FNet Re(fft2), "dwt_embed" / "dwt_token" = Haar DWT) -- the modes the reference's
-docstring lists (spectre.py:30-36) and BASELINE.json benchmarks.
+MHPermutMix, "fft" = FNet Re(fft2), "dwt_embed" / "dwt_token" = Haar DWT, "attention" = self-attention over
+the tokens with nn.MultiheadAttention's parameters) -- the modes the reference's docstring lists
+(spectre.py:29-35; its undefined "fft_mh" aside) and BASELINE.json benchmarks.
 """
 import torch
 import torch.nn as nn
@@ -12,9 +13,9 @@ from torch.nn.modules.transformer import _get_activation_fn, _get_clones
 
 from spectre_vit import hip_ops
 from spectre_vit.models.spectre.layers import MHPermutMix, SpectreLinear
-from spectre_vit.modules.mixers import FNetMixer, HaarDWTMixer
+from spectre_vit.modules.mixers import FNetMixer, HaarDWTMixer, SelfAttentionMixer
 
-MIXERS = ("permut", "fft", "dwt_embed", "dwt_token")
+MIXERS = ("permut", "fft", "dwt_embed", "dwt_token", "attention")
 
 
 class Transpose(nn.Module):
@@ -28,7 +29,7 @@ class Transpose(nn.Module):
         return x.transpose(self.dims[0], self.dims[1])
 
 
-def _make_mixer(mixer, d_model, seq_length, nhead, dwt_levels, dwt_mode="passthrough"):
+def _make_mixer(mixer, d_model, seq_length, nhead, dwt_levels, dwt_mode="passthrough", dropout=0.0):
     if mixer == "permut":
         return MHPermutMix(d_model, seq_length, nhead, d_model)
     if mixer == "fft":
@@ -37,6 +38,8 @@ def _make_mixer(mixer, d_model, seq_length, nhead, dwt_levels, dwt_mode="passthr
         return HaarDWTMixer("embed", dwt_levels, dwt_mode)
     if mixer == "dwt_token":
         return HaarDWTMixer("token", dwt_levels, dwt_mode)
+    if mixer == "attention":
+        return SelfAttentionMixer(d_model, nhead, dropout)
     raise ValueError(f"mixer must be one of {MIXERS}, got {mixer!r}")
 
 
@@ -49,7 +52,7 @@ class SpectreEncoderLayer(nn.Module):
         bias = True
         layer_norm_eps = 1e-5
         self.mixer = mixer
-        self.mix_layer = _make_mixer(mixer, d_model, seq_length, nhead, dwt_levels, dwt_mode)
+        self.mix_layer = _make_mixer(mixer, d_model, seq_length, nhead, dwt_levels, dwt_mode, dropout)
         self.linear1 = SpectreLinear(d_model, dim_feedforward)
         self.linear3 = SpectreLinear(dim_feedforward, d_model)
 
@@ -80,6 +83,12 @@ class SpectreEncoderLayer(nn.Module):
             if hip_ops.fnet_cls_ok(xc):
                 # row 0 of Re(fft2(x)) is one FFT of the token sum: the mixer half as one pass over x, its backward one write
                 return self._ff(hip_ops.FNetClsFn.apply(xc, self.norm1.weight, self.norm1.bias))
+        if self.mixer == "attention":
+            xc = hip_ops.cast(x, hip_ops.compute_dtype(x))
+            if hip_ops.attn_row0_ok(xc, self.mix_layer.num_heads):
+                # K and V over every row, the query, the attention and everything after it at the CLS rows only
+                m0, x0 = self.mix_layer.forward_cls(xc)
+                return self._ff(hip_ops.add_layernorm(m0, x0, self.norm1.weight, self.norm1.bias, 0))
         if self.mixer == "dwt_embed":
             # the Haar transform along the embedding axis is row-wise too: the whole layer runs at the CLS rows
             x0 = hip_ops.TakeClsFn.apply(hip_ops.cast(x, hip_ops.compute_dtype(x)))
@@ -205,13 +214,14 @@ class SpectreViT(nn.Module):
         cand = self.__dict__.get("_shadow_candidates")
         if cand is None or cand[0] != len(self.encoder_blocks.layers):
             # the module walk costs the host 0.1 ms per step (the eager, data-parallel path is host-bound): done once per stack
-            mods = [mod for layer in self.encoder_blocks.layers for mod in layer.modules() if isinstance(mod, SpectreLinear)]
+            mods = [mod for layer in self.encoder_blocks.layers for mod in layer.modules() if isinstance(mod, (SpectreLinear, SelfAttentionMixer))]
             cand = self.__dict__["_shadow_candidates"] = (len(self.encoder_blocks.layers), mods)
         ws = []
         for mod in cand[1]:
-            w = mod.local_head[0].weight   # (looked up every time: a caller may have replaced the parameter)
-            if w.requires_grad and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0:
-                ws.append(w)
+            # (looked up every time: a caller may have replaced the parameter)
+            for w in ((mod.in_proj_weight, mod.out_proj.weight) if isinstance(mod, SelfAttentionMixer) else (mod.local_head[0].weight,)):
+                if w.requires_grad and w.shape[0] % 8 == 0 and w.shape[1] % 8 == 0:
+                    ws.append(w)
         return ws
 
     def _observed(self):

@@ -1,8 +1,10 @@
-"""Parameter-free spectral token mixers with the (B, N, D) -> (B, N, D) ``mix_layer`` contract.
+"""Token mixers with the (B, N, D) -> (B, N, D) ``mix_layer`` contract.
 
-The reference names them in SpectreEncoderLayer's docstring (spectre_vit/models/spectre/spectre.py:30-36:
-fft_bare, dwt_embed, dwt_token) but wires none of them at HEAD; BASELINE.json's configs 2-4 ask for them.
+The reference names them in SpectreEncoderLayer's docstring (spectre_vit/models/spectre/spectre.py:29-35:
+fft_bare, dwt_embed, dwt_token, attention) but wires none of them at HEAD; BASELINE.json's configs 2-4 ask for the
+parameter-free spectral ones.  SelfAttentionMixer is the control they are compared against.
 """
+import torch
 import torch.nn as nn
 
 from spectre_vit import hip_ops
@@ -37,3 +39,44 @@ class HaarDWTMixer(nn.Module):
     def forward(self, x):
         x = hip_ops.cast(x, hip_ops.compute_dtype(x))
         return hip_ops.HaarDWTFn.apply(x, 2 if self.axis == "embed" else 1, self.levels, self.mode == "zero")
+
+
+class SelfAttentionMixer(nn.Module):
+    """Self-attention over the token axis ("Native ViT Self-Attention", reference spectre.py:29-35): the arithmetic of
+    ``nn.MultiheadAttention(d_model, nhead, dropout=dropout, bias=True, batch_first=True)(x, x, x, need_weights=False)[0]`` --
+    no mask, scale 1/sqrt(d_model / nhead), every row (the CLS row included) attends to every row, dropout on the attention
+    probabilities in training.  Parameters carry nn.MultiheadAttention's names, shapes, init and RNG order (in_proj_weight,
+    in_proj_bias, out_proj.weight, out_proj.bias), so a state_dict loads strictly into either module."""
+
+    def __init__(self, d_model: int, nhead: int, dropout: float = 0.0):
+        super().__init__()
+        if nhead <= 0 or d_model % nhead:
+            raise ValueError(f"SelfAttentionMixer: nhead={nhead} must divide d_model={d_model}")
+        self.embed_dim = d_model
+        self.num_heads = nhead
+        self.head_dim = d_model // nhead
+        self.dropout = float(dropout)
+        self.in_proj_weight = nn.Parameter(torch.empty(3 * d_model, d_model))
+        self.in_proj_bias = nn.Parameter(torch.empty(3 * d_model))
+        self.out_proj = nn.Linear(d_model, d_model)   # its weight and bias draws come first, as in nn.MultiheadAttention.__init__
+        nn.init.xavier_uniform_(self.in_proj_weight)
+        nn.init.zeros_(self.in_proj_bias)
+        nn.init.zeros_(self.out_proj.bias)
+
+    def _p(self):
+        return self.dropout if self.training else 0.0
+
+    def forward(self, x):
+        x = hip_ops.cast(x, hip_ops.compute_dtype(x))
+        qkv = hip_ops.linear(x, self.in_proj_weight, self.in_proj_bias)   # packed [B, N, 3E] = q | k | v
+        ctx = hip_ops.AttentionFn.apply(qkv, self.num_heads, self._p())
+        return hip_ops.linear(ctx, self.out_proj.weight, self.out_proj.bias)
+
+    def forward_cls(self, x):
+        """(row 0 of forward(x), x[:, 0, :]), each (B, E): K and V over every row, Q, the attention and the out-projection at the CLS
+        rows only (hip_ops.AttnClsFn; x in the compute dtype)"""
+        ctx0, x0 = hip_ops.AttnClsFn.apply(x, self.in_proj_weight, self.in_proj_bias, self.num_heads, self._p())
+        return hip_ops.linear(ctx0, self.out_proj.weight, self.out_proj.bias), x0
+
+    def extra_repr(self):
+        return f"embed_dim={self.embed_dim}, num_heads={self.num_heads}, dropout={self.dropout}"
