@@ -43,7 +43,7 @@ enum {
     SPV_PATH_FNET_MFMA = 6,      /* fnet_mfma_kernel (bf16, dim 512) */
     SPV_PATH_GATHER_LDS = 7,     /* LDS-staged MHPermutMix gather */
     SPV_PATH_GEMM_TN_WIDE = 9,   /* gemm_tn_wide_kernel (256 x 128 tile; M % 256 == 0, N % 128 == 0) */
-    SPV_PATH_GEMM_TN_DMA = 8,    /* gemm_tn_dma_kernel (LDS-DMA ring; M, N % 128 == 0, K % 64 == 0) */
+    /* index 8 is unused */
     SPV_PATH_GEMM_TN_BATCH = 10, /* gemm_tn_batch_kernel: up to eight weight gradients in one launch (spv_gemm_tn_batch) */
     SPV_PATH_GEMM_STRIP_POOL = 11, /* gemm_nt_strip_kernel<*, 2 / 3>: data gradient + pooled-broadcast term (spv_gemm_nt_pool_bwd) */
     SPV_PATH_GEMM_ROWS = 13,     /* gemm_nt_rows_kernel: few-rows NT GEMM, one 32 x 32 tile per workgroup, no split-K (the CLS-only last layer) */

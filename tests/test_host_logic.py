@@ -99,6 +99,29 @@ def test_product_never_imports_oracle():
                 assert "oracle" not in open(os.path.join(dp, f)).read().replace("oracle/", "").lower() or f == "__init__.py", f
 
 
+def test_product_reads_no_environment_switch():
+    """The library reads no environment variable; the package reads SPV_LIB_PATH, SPV_FULL_LAST_LAYER and the launcher's variables."""
+    pkg = os.path.join(ROOT, "vit-spectre-experiments_amd")
+    csrc = os.path.join(pkg, "csrc")
+    for f in sorted(os.listdir(csrc)):
+        if f.endswith((".hip", ".h")):
+            text = open(os.path.join(csrc, f)).read()
+            assert "getenv" not in text and "SPV_LAB" not in text, f
+    allowed = {"SPV_LIB_PATH", "SPV_FULL_LAST_LAYER", "RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"}
+    launcher = {"RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"}
+    for dp, _, fs in os.walk(os.path.join(pkg, "spectre_vit")):
+        for f in fs:
+            if not f.endswith(".py"):
+                continue
+            text = open(os.path.join(dp, f)).read()
+            assert "getenv" not in text and "SPV_LAB" not in text, f
+            uses = len(re.findall(r"\benviron\b", text))
+            names = re.findall(r"""\benviron\s*(?:\.\s*(?:get|setdefault|pop)\s*\(|\[)\s*["']([A-Za-z0-9_]+)["']""", text)
+            assert uses == len(names), f"{f}: an os.environ use that does not name its variable"
+            for name in names:
+                assert name in allowed and (f == "harness.py" or name not in launcher), f"{f} reads {name}"
+
+
 def test_oracle_normalize_u8_matches_totensor_normalize():
     """train.py:102-112: ToTensor (HWC uint8 -> CHW float / 255) then Normalize(mean, std), restated with torch ops."""
     import numpy as np

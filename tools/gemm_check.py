@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""NT GEMM check + timing at the layer shapes (development tool).  Env SPV_GEMM_KB forces the direct-to-LDS kernel (tile-shape variants live in tools/gemm_lab.hip).
+"""NT GEMM check + timing at the layer shapes (development tool; tile-shape variants live in tools/gemm_lab.hip).
 
     python tools/gemm_check.py [M N K ...]
 """
@@ -38,8 +38,7 @@ def run(M, N, K, acc=0, iters=30):
     e1.record()
     torch.cuda.synchronize()
     us = e0.elapsed_time(e1) * 1e3 / iters
-    print(f"gemm {M}x{N}x{K} acc={acc}: rel err {err:.2e}  {us:8.2f} us  {2.0 * M * N * K / us * 1e-6:7.1f} TFLOP/s "
-          f"[KB={os.environ.get('SPV_GEMM_KB', '-')}]", flush=True)
+    print(f"gemm {M}x{N}x{K} acc={acc}: rel err {err:.2e}  {us:8.2f} us  {2.0 * M * N * K / us * 1e-6:7.1f} TFLOP/s", flush=True)
     assert err < 2e-2, err
 
 

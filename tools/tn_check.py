@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""Weight-gradient (TN) GEMM at the layer shapes: LDS-DMA kernel vs the register-staged one vs fp64, and GPU time per launch
-including the split-K reduce (development tool; run on the GPU box).   SPV_TN_DMA=0 selects the old kernel."""
+"""Weight-gradient (TN) GEMM at the layer shapes against fp64, and GPU time per launch including the split-K reduce (development
+tool; needs the GPU)."""
 import os
 import sys
 
@@ -33,10 +33,8 @@ def main():
             C = torch.zeros(M, N, device=dev)
             ws = torch.empty(max(splits, 1) * M * N, device=dev)
             fn = lambda: _native.call("spv_gemm_tn", p(A), p(Bm), p(C), M, N, K, M, N, N, 0, 0, splits, p(ws) if splits > 1 else 0, st)  # noqa: E731
-            before = _native.call("spv_path_count", _native.PATH["gemm_tn_dma"])
             fn()
             torch.cuda.synchronize()
-            dma = _native.call("spv_path_count", _native.PATH["gemm_tn_dma"]) - before
             err = ""
             if ref is not None:
                 got = C.cpu().numpy().astype(np.float64)
@@ -51,7 +49,7 @@ def main():
             e1.record()
             torch.cuda.synchronize()
             us = e0.elapsed_time(e1) * 1e3 / iters
-            print(f"tn {M}x{N}x{K} splits={splits} dma={dma}: {us:8.2f} us  {2.0 * M * N * K / us * 1e-6:7.1f} TFLOP/s ({2.0 * M * N * K / us * 1e-6 / 25:5.1f} % of 2.5 PF)  {err}", flush=True)
+            print(f"tn {M}x{N}x{K} splits={splits}: {us:8.2f} us  {2.0 * M * N * K / us * 1e-6:7.1f} TFLOP/s ({2.0 * M * N * K / us * 1e-6 / 25:5.1f} % of 2.5 PF)  {err}", flush=True)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,5 @@
 """Batched weight gradients (spv_gemm_tn_batch) at the step's shapes: correctness vs fp32 matmul + time per launch by split count.
-    SPV_LAB=1 SPV_LIB_PATH=.../libspv_hip_lab.so SPV_TNB_WIDE=0|1 python tools/tnb_bench.py"""
+    python tools/tnb_bench.py"""
 import ctypes, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [os.path.join(ROOT, "vit-spectre-experiments_amd"), ROOT]
@@ -46,4 +46,4 @@ for splits in [int(s) for s in os.environ.get("SPLITS", "3,4,5,6,7,8,10").split(
         torch.cuda.synchronize()
         ts.append(e0.elapsed_time(e1) / 30 * 1e3)
     tf = 2.0 * rows * floats / ts[0] / 1e6
-    print(f"short={nshort} wide={os.environ.get('SPV_TNB_WIDE', '1')} splits {splits}: gemm {ts[0]:.1f} us ({tf:.0f} TFLOP/s, {tf / 2500:.3f} of peak)  reduce {ts[1]:.1f} us  max err {err:.2e}", flush=True)
+    print(f"short={nshort} splits {splits}: gemm {ts[0]:.1f} us ({tf:.0f} TFLOP/s, {tf / 2500:.3f} of peak)  reduce {ts[1]:.1f} us  max err {err:.2e}", flush=True)

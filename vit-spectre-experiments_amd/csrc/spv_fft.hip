@@ -951,11 +951,9 @@ extern "C" int spv_fnet_mix(const void* x, void* y, const void* add_in, const fl
     SPV_CHECK(dtype == SPV_F32 || dtype == SPV_BF16, "spv_fnet_mix: bad dtype %d", dtype);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int bf = dtype == SPV_BF16;
-    static const bool no_v2 = SPV_LAB_SET("SPV_FNET_NO_V2");  // tuning / A-B aid
-    if (bf && dim == V2D && tokens >= 2 && tokens <= 65 && !no_v2) {
+    if (bf && dim == V2D && tokens >= 2 && tokens <= 65) {
         SPV_CHECK(twiddle != nullptr, "spv_fnet_mix: twiddle table required");
-        static const int stagger_env = SPV_LAB_INT("SPV_FNET_STAGGER", -1);
-        const int v2_stagger = stagger_env >= 0 ? stagger_env : (batch >= 512 ? 1 : 0);  // x 8128 cycles (~3.5 us)
+        const int v2_stagger = batch >= 512 ? 1 : 0;  // x 8128 cycles (~3.5 us)
         const int rows = std::max(2 * ((tokens + 1) / 2), 2 * (tokens / 2 + 1));
         const size_t lds = (size_t)rows * V2RS;
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fnet_mfma_kernel<0>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1029,8 +1027,7 @@ extern "C" int spv_haar_dwt(const void* x, void* y, int batch, int tokens, int d
     for (int i = 0; i < levels; ++i) {
         const int l = inverse ? levels - 1 - i : i;
         void* dst = ((levels - 1 - i) % 2 == 0) ? y : scratch;
-        static const bool generic = SPV_LAB_SET("SPV_HAAR_GENERIC");   // A/B switch
-        if (!generic && axis == 2 && dtype == SPV_BF16 && dim % 8 == 0 && lens[l] % 16 == 0 &&
+        if (axis == 2 && dtype == SPV_BF16 && dim % 8 == 0 && lens[l] % 16 == 0 &&
             (((uintptr_t)src | (uintptr_t)dst) & 15) == 0) {
             const int64_t rows = (int64_t)batch * tokens;
             const int g2 = (int)std::min<int64_t>((rows * (dim / 8) + 255) / 256, 8192);
@@ -1051,14 +1048,9 @@ extern "C" int spv_haar_dwt(const void* x, void* y, int batch, int tokens, int d
 
 // ---- mixer + LayerNorm-1 + residual as one kernel each way (bf16, dim 512, tokens <= 65: the shapes of fnet_mfma_kernel)
 extern "C" int spv_fnet_ln_supported(int tokens, int dim, int dtype) {
-    static const bool off = SPV_LAB_SET("SPV_FNET_NO_V2") || SPV_LAB_SET("SPV_FNET_NO_FUSE");
-    return (!off && dtype == SPV_BF16 && dim == V2D && tokens >= 2 && tokens <= 65) ? 1 : 0;
+    return (dtype == SPV_BF16 && dim == V2D && tokens >= 2 && tokens <= 65) ? 1 : 0;
 }
 
-static int fnet_ln_stagger(int batch) {
-    static const int env = SPV_LAB_INT("SPV_FNET_LN_STAGGER", 0);  // x 8128 cycles (+ 256: by threadgroup slot instead of grid half); tuning aid
-    return batch >= 512 ? env : 0;
-}
 static size_t fnet_v2_lds(int tokens) { return (size_t)std::max(2 * ((tokens + 1) / 2), 2 * (tokens / 2 + 1)) * V2RS; }
 
 extern "C" int spv_fnet_ln_fwd(const void* x, void* prenorm, void* out, const float* gamma, const float* beta, float* mean, float* rstd,
@@ -1072,7 +1064,7 @@ extern "C" int spv_fnet_ln_fwd(const void* x, void* prenorm, void* out, const fl
     SPV_COUNT_PATH(SPV_PATH_FNET_MFMA);
     hipLaunchKernelGGL(fnet_mfma_kernel<1>, dim3(batch), dim3(512), fnet_v2_lds(tokens), st, static_cast<const bf16_t*>(x),
                        static_cast<bf16_t*>(out), reinterpret_cast<const uint4*>(twiddle + v2_frag_off(tokens)), reinterpret_cast<const uint4*>(twiddle + v2_extra_off(tokens)),
-                       twiddle + v2_tw_off(tokens), tokens, fnet_ln_stagger(batch), static_cast<const bf16_t*>(nullptr), ln);
+                       twiddle + v2_tw_off(tokens), tokens, 0, static_cast<const bf16_t*>(nullptr), ln);
     SPV_LAUNCH_CHECK("spv_fnet_ln_fwd");
     return 0;
 }
@@ -1090,7 +1082,7 @@ extern "C" int spv_fnet_ln_bwd(const void* dout, const void* prenorm, const floa
     SPV_COUNT_PATH(SPV_PATH_FNET_MFMA);
     hipLaunchKernelGGL(fnet_mfma_kernel<2>, dim3(batch), dim3(512), fnet_v2_lds(tokens) + 2 * V2D * sizeof(float), st,
                        static_cast<const bf16_t*>(dout), static_cast<bf16_t*>(dx), reinterpret_cast<const uint4*>(twiddle + v2_frag_off(tokens)),
-                       reinterpret_cast<const uint4*>(twiddle + v2_extra_off(tokens)), twiddle + v2_tw_off(tokens), tokens, fnet_ln_stagger(batch), static_cast<const bf16_t*>(dout), ln);
+                       reinterpret_cast<const uint4*>(twiddle + v2_extra_off(tokens)), twiddle + v2_tw_off(tokens), tokens, 0, static_cast<const bf16_t*>(dout), ln);
     SPV_LAUNCH_CHECK("spv_fnet_ln_bwd");
     // dgamma == NULL: the caller folds the partials itself (deferred: spv_reduce_multi kind 1 with parts = batch, nsum = 2, n = dim)
     if (dgamma != nullptr) hipLaunchKernelGGL(fnet_ln_fold_kernel, dim3(2 * V2D / FOLD_COLS), dim3(FOLD_COLS * FOLD_ROWS), 0, st, partials, dgamma, dbeta, batch);
@@ -1261,8 +1253,7 @@ __global__ __launch_bounds__(D / 2) void fnet_cls_bwd_kernel(const T* __restrict
 }  // namespace
 
 extern "C" int spv_fnet_cls_supported(int tokens, int dim, int dtype) {
-    static const bool off = SPV_LAB_SET("SPV_FNET_NO_CLS");
-    return (!off && (dtype == SPV_BF16 || dtype == SPV_F32) && (dim == 256 || dim == 512 || dim == 1024) && tokens >= 1) ? 1 : 0;
+    return ((dtype == SPV_BF16 || dtype == SPV_F32) && (dim == 256 || dim == 512 || dim == 1024) && tokens >= 1) ? 1 : 0;
 }
 
 extern "C" int spv_fnet_cls_fwd(const void* x, const float* gamma, const float* beta, void* out, float* m0, float* mean, float* rstd, int batch,

@@ -828,8 +828,7 @@ __global__ __launch_bounds__(512) void gemm_nt_strip_kernel(const bf16_t* __rest
 static int g_reserved_cus = 0;
 
 inline bool strip_plan(int M, int N, int K, int& MB, int& nstrips, int& groups, int& base, int& rem) {
-    static const int enabled = SPV_LAB_INT("SPV_GEMM_STRIP", 1);
-    if (!enabled || N % 256 != 0 || N > 16384 || K % 128 != 0 || K < 128 || M < 8192) return false;   // (Base width: the MHPermutMix data gradient has N = 9216)
+    if (N % 256 != 0 || N > 16384 || K % 128 != 0 || K < 128 || M < 8192) return false;   // (Base width: the MHPermutMix data gradient has N = 9216)
     nstrips = N / 256;
     const int nblk = cdiv(M, 32);
     groups = (256 - g_reserved_cus) / nstrips;
@@ -938,9 +937,6 @@ __global__ __launch_bounds__(256) void gemm_nt_rows_kernel(const bf16_t* __restr
 // 320-byte row stride the four k rows of a group land in four disjoint 16-bank ranges (conflict free).
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef unsigned tn_u32x4 __attribute__((ext_vector_type(4)));
-#ifdef SPV_LAB
-__device__ int g_tn_ablate = 0;   // set by the host from SPV_TN_ABLATE before a launch (lab build only)
-#endif
 constexpr int TROWB = 256 + 64;  // LDS bytes per k row (128 bf16 + pad)
 constexpr int TBK = 64;          // k rows per stage (16 MFMAs per wave between barriers)
 
@@ -1057,23 +1053,18 @@ __device__ __forceinline__ void tn_tile_body(const bf16_t* __restrict__ A, const
                     acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
         }
     };
-#ifdef SPV_LAB
-    const int abl = g_tn_ablate;   // lab: 1 = no LDS stores, 2 = no global loads after the prologue, 4 = no MFMAs / fragment reads (wrong results)
-#else
-    constexpr int abl = 0;
-#endif
     // one K-tile: its registers go to LDS, the set is refilled with full tile `next` (DEPTH ahead), then the MFMAs
     auto step = [&](int next, RegTile& ra, RegTile& rb) __attribute__((always_inline)) {
-        if (!(abl & 1)) store_tile(ra, rb);
+        store_tile(ra, rb);
         __syncthreads();
-        if (!(abl & 2)) load_full(next, ra, rb);
-        if (!(abl & 4)) multiply();
+        load_full(next, ra, rb);
+        multiply();
         __syncthreads();
     };
     auto step_last = [&](RegTile& ra, RegTile& rb) __attribute__((always_inline)) {   // no refill
-        if (!(abl & 1)) store_tile(ra, rb);
+        store_tile(ra, rb);
         __syncthreads();
-        if (!(abl & 4)) multiply();
+        multiply();
         __syncthreads();
     };
 
@@ -1172,117 +1163,20 @@ __global__ __launch_bounds__(256) void gemm_tn_batch_kernel(TnBatch tb, float* _
     tn_tile_body<float, DEPTH>(q.A, q.B, q.C, w.ws, q.M, q.N, w.K, q.lda, q.ldb, q.ldc, w.k_per_split, 0, q.tiles_n, w.tile, w.split);
 }
 
-#ifdef SPV_LAB   // measured 5 % slower than the one-buffer kernel: lab build only
-// The same 128 x 128 tile on TWO LDS buffers and ONE barrier per K-tile.  tn_tile_body above stores a K-tile, waits at a barrier,
-// multiplies, waits at a second barrier: inside a workgroup nothing overlaps, and its ablations put the sum of
-// exposed loads, LDS stores and MFMAs at the kernel's time.  Here the registers of K-tile t + 1 go to the OTHER buffer between the
-// k-steps of tile t (the store issue hides under that tile's MFMAs), the set is refilled with tile t + 4, and one barrier both
-// publishes tile t + 1 and frees tile t's buffer.  81 920 B of LDS: two workgroups per CU, as many as the 192 registers allow anyway.
-template <typename TO>
-__device__ __forceinline__ void tn_tile_body_db(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, TO* __restrict__ C,
-                                                float* __restrict__ ws, int M, int N, int K, int lda, int ldb, int ldc, int k_per_split,
-                                                int accumulate, int tiles_n, int tile, int split, int tiles_m = 0) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char tdb_smem[];   // 2 x 40 960 B
-    constexpr int BUF = 2 * TBK * TROWB;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int wm = wave >> 1, wn = wave & 1;
-    const bool m_fast = tiles_m > 0 && tiles_n >= 4 * tiles_m;
-    const int tm = m_fast ? tile % tiles_m : tile / tiles_n, tn = m_fast ? tile / tiles_m : tile % tiles_n;
-    const int m0 = tm * BM, n0 = tn * BN;
-    const int kbeg = split * k_per_split;
-    const int kend = min(K, kbeg + k_per_split);
-    const int srow = tid >> 4, sch = tid & 15;
-    const bool a_ok = (m0 + sch * 8) < M, b_ok = (n0 + sch * 8) < N;
-    typedef uint4 RegTile[TBK / 16];
-    RegTile ra0, rb0, ra1, rb1, ra2, rb2;
-    auto load_tile = [&](int k0, RegTile& ra, RegTile& rb) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < TBK / 16; ++i) {
-            const int k = k0 + srow + 16 * i;
-            const bool kin = k < kend;
-            ra[i] = (kin && a_ok) ? *reinterpret_cast<const uint4*>(A + (size_t)k * lda + m0 + sch * 8) : make_uint4(0, 0, 0, 0);
-            rb[i] = (kin && b_ok) ? *reinterpret_cast<const uint4*>(B + (size_t)k * ldb + n0 + sch * 8) : make_uint4(0, 0, 0, 0);
-        }
-    };
-    auto store_half = [&](unsigned char* buf, const RegTile& ra, const RegTile& rb, int half) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 2 * half; i < 2 * half + 2; ++i) {
-            *reinterpret_cast<uint4*>(buf + (srow + 16 * i) * TROWB + sch * 16) = ra[i];
-            *reinterpret_cast<uint4*>(buf + TBK * TROWB + (srow + 16 * i) * TROWB + sch * 16) = rb[i];
-        }
-    };
-    static_assert(TBK / 16 == 4, "two halves of two row groups");
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-    const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-    const int frag_off = (8 * (g >> 1) + q) * TROWB + (16 * (g & 1) + 4 * pp) * 2;
-    const int fa_off = frag_off + (wm * 64) * 2, fb_off = TBK * TROWB + frag_off + (wn * 64) * 2;
-    // one K-tile: multiply from `cur`; between its k-steps the registers of the NEXT tile go to `nxt`; then that set is refilled
-    auto step = [&](int k0, const unsigned char* cur, unsigned char* nxt, RegTile& ra, RegTile& rb) __attribute__((always_inline)) {
-        const bool more = k0 + TBK < kend;       // (ra, rb) hold tile k0 + TBK
-#pragma unroll
-        for (int ks = 0; ks < TBK / 16; ++ks) {
-            bf16x8 a[2], b[2];
-#pragma unroll
-            for (int f = 0; f < 2; ++f) {
-                a[f] = tr_frag(cur + fa_off + ks * 16 * TROWB + f * 64);
-                b[f] = tr_frag(cur + fb_off + ks * 16 * TROWB + f * 64);
-            }
-            if (ks < 2 && more) store_half(nxt, ra, rb, ks);
-#pragma unroll
-            for (int i = 0; i < 2; ++i)
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-        }
-        if (k0 + 4 * TBK < kend) load_tile(k0 + 4 * TBK, ra, rb);
-        __syncthreads();
-    };
-    load_tile(kbeg, ra0, rb0);
-    if (kbeg + TBK < kend) load_tile(kbeg + TBK, ra1, rb1);
-    if (kbeg + 2 * TBK < kend) load_tile(kbeg + 2 * TBK, ra2, rb2);
-    store_half(tdb_smem, ra0, rb0, 0);
-    store_half(tdb_smem, ra0, rb0, 1);
-    if (kbeg + 3 * TBK < kend) load_tile(kbeg + 3 * TBK, ra0, rb0);
-    __syncthreads();
-    // tile t is multiplied from buffer t & 1; the register sets rotate with period 3: (ra1, ra2, ra0) hold tiles t + 1 for t = 0, 1, 2
-    int t = 0;
-    for (int k0 = kbeg; k0 < kend; k0 += 3 * TBK, t += 3) {
-        step(k0, tdb_smem + (t & 1) * BUF, tdb_smem + ((t + 1) & 1) * BUF, ra1, rb1);
-        if (k0 + TBK < kend) step(k0 + TBK, tdb_smem + ((t + 1) & 1) * BUF, tdb_smem + (t & 1) * BUF, ra2, rb2);
-        if (k0 + 2 * TBK < kend) step(k0 + 2 * TBK, tdb_smem + (t & 1) * BUF, tdb_smem + ((t + 1) & 1) * BUF, ra0, rb0);
-    }
-    store_acc_tile<TO>(acc, tdb_smem, nullptr, C, ws, M, N, ldc, accumulate, m0, n0, split, 0, 0, 0, nullptr);
-}
-
-__global__ __launch_bounds__(256) void gemm_tn_batch_db_kernel(TnBatch tb, float* __restrict__ ws, int K, int k_per_split, int nsplit) {
-    const TnWork w = tn_batch_work(tb, ws, K, k_per_split, nsplit);
-    if (w.j < 0) return;
-    const TnBatch::P& q = tb.p[w.j];
-    tn_tile_body_db<float>(q.A, q.B, q.C, w.ws, q.M, q.N, w.K, q.lda, q.ldb, q.ldc, w.k_per_split, 0, q.tiles_n, w.tile, w.split);
-}
-
-#endif  // SPV_LAB
-
 // ---------------------------------------------------------------------------------------------------------
 // TN contraction, WIDE tile: 256 (m) x 128 (n) per 8-wave workgroup (waves 4 x 2, 64 x 64 each), otherwise gemm_tn_kernel's
-// structure (register-staged tiles three K-tiles deep, one LDS buffer, transposing fragment reads).  The weight gradients of the
+// structure (register-staged tiles three K-tiles deep, transposing fragment reads) on two LDS buffers.  The weight gradients of the
 // encoder layers (768 x 512 x 33 280) are bound by the L2 -> LDS path, not by MFMA issue: a 128 x 128 tile moves 32 KiB per
 // 2.1 MFLOP K-tile (400 MB per launch through a path that sustains ~14 TB/s chip-wide), the 256 x 128 tile 48 KiB per 4.2 MFLOP
 // (300 MB) at the same number of split-K slabs (12 tiles x 21 slices = one workgroup per CU).
 constexpr int TWM = 256;              // tile rows (m)
 constexpr int TWROWA = TWM * 2 + 64;  // LDS bytes per k row of the A tile: 576 = 64 mod 256, the four k rows of a read group land in disjoint banks
 
-template <typename TO, bool DB>
+template <typename TO>
 __device__ __forceinline__ void tn_wide_body(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, TO* __restrict__ C,
                                              float* __restrict__ ws, int M, int N, int K, int lda, int ldb, int ldc,
                                              int k_per_split, int accumulate, int tiles_n, int tile, int split) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char tw_smem[];  // TW_SMEM / TW_SMEM_DB bytes
+    extern __shared__ __attribute__((aligned(16))) unsigned char tw_smem[];  // TW_SMEM_DB bytes
     unsigned char* sA = tw_smem;
     unsigned char* sB = tw_smem + TBK * TWROWA;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -1359,128 +1253,80 @@ __device__ __forceinline__ void tn_wide_body(const bf16_t* __restrict__ A, const
         const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
         return __builtin_bit_cast(bf16x8, v);
     };
-#ifdef SPV_LAB
-    const int abl = g_tn_ablate;   // lab: 1 = no LDS stores, 2 = no global loads after the prologue, 4 = no MFMAs / fragment reads (wrong results)
-#else
-    constexpr int abl = 0;
-#endif
     // the 16 MFMAs of the K-tile in buffer `cur`; between its k-steps (STORE) the register tile (ra, rb) goes to buffer `nxt`
     auto multiply = [&](int cur, auto store_tag, int nxt, const RegA& ra, const RegB& rb) __attribute__((always_inline)) {
         constexpr bool STORE = decltype(store_tag)::value;
 #pragma unroll
         for (int ks = 0; ks < TBK / 16; ++ks) {
             bf16x8 a[2], b[2];
-            if (!(abl & 4)) {
 #pragma unroll
-                for (int f = 0; f < 2; ++f) {
-                    a[f] = fragA(fa0 + cur + ks * 16 * TWROWA + f * 64);
-                    b[f] = tr_frag(fb0 + cur + ks * 16 * TROWB + f * 64);
-                }
+            for (int f = 0; f < 2; ++f) {
+                a[f] = fragA(fa0 + cur + ks * 16 * TWROWA + f * 64);
+                b[f] = tr_frag(fb0 + cur + ks * 16 * TROWB + f * 64);
             }
-            if constexpr (STORE) {
-                if (!(abl & 1)) store_part(nxt, ra, rb, ks);
-            }
-            if (!(abl & 4)) {
+            if constexpr (STORE) store_part(nxt, ra, rb, ks);
 #pragma unroll
-                for (int i = 0; i < 2; ++i)
+            for (int i = 0; i < 2; ++i)
 #pragma unroll
-                    for (int j = 0; j < 2; ++j)
-                        acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-            }
+                for (int j = 0; j < 2; ++j)
+                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
         }
     };
     using yes = std::true_type;
     using no = std::false_type;
 
-    if constexpr (DB) {
-        // TWO LDS buffers, ONE barrier per K-tile: while tile t is multiplied out of buffer t & 1, the registers of tile t + 1 go to
-        // the other buffer between the k-steps (the 13-cycle ds_write_b128 issues hide under the MFMAs), that register set is
-        // refilled with tile t + 4, and the barrier both publishes tile t + 1 and frees tile t's buffer.  Register sets rotate with
-        // period 3 (tile j lives in set j % 3), buffers with period 2.
-        constexpr int WBUF = TBK * TWROWA + TBK * TROWB;
-        if (nfull > 0) {
-            load_full(0, a0, b0);
-            load_full(1, a1, b1);
-            load_full(2, a2, b2);
-            store_part(0, a0, b0, -1);
-            load_full(3, a0, b0);
-            __syncthreads();
-            auto step = [&](int t, RegA& ra, RegB& rb) __attribute__((always_inline)) {   // (ra, rb) hold tile t + 1
-                multiply((t & 1) * WBUF, yes{}, ((t + 1) & 1) * WBUF, ra, rb);
-                if (!(abl & 2)) load_full(t + 4, ra, rb);
-                __syncthreads();
-            };
-            auto step_noload = [&](int t, const RegA& ra, const RegB& rb) __attribute__((always_inline)) {
-                multiply((t & 1) * WBUF, yes{}, ((t + 1) & 1) * WBUF, ra, rb);
-                __syncthreads();
-            };
-            int t = 0;
-            for (; t + 4 <= nfull; t += 3) {
-                step(t, a1, b1);
-                step(t + 1, a2, b2);
-                step(t + 2, a0, b0);
-            }
-            const int left = nfull - t;   // 1, 2 or 3 tiles: t in buffer t & 1, t + 1 in (a1, b1), t + 2 in (a2, b2)
-            if (left >= 2) {
-                step_noload(t, a1, b1);
-                if (left == 3) step_noload(t + 1, a2, b2);
-            }
-            multiply(((nfull - 1) & 1) * WBUF, no{}, 0, a0, b0);
-            __syncthreads();
-        }
-        if (krem > 0) {
-            load_partial(kbeg + nfull * TBK, a0, b0);
-            store_part(0, a0, b0, -1);
-            __syncthreads();
-            multiply(0, no{}, 0, a0, b0);
-            __syncthreads();
-        }
-    } else {
-        // one buffer, two barriers per K-tile: store, barrier, refill, multiply, barrier
-        auto step = [&](int next, RegA& ra, RegB& rb) __attribute__((always_inline)) {
-            if (!(abl & 1)) store_part(0, ra, rb, -1);
-            __syncthreads();
-            if (!(abl & 2)) load_full(next, ra, rb);
-            multiply(0, no{}, 0, ra, rb);
+    // TWO LDS buffers, ONE barrier per K-tile: while tile t is multiplied out of buffer t & 1, the registers of tile t + 1 go to
+    // the other buffer between the k-steps (the 13-cycle ds_write_b128 issues hide under the MFMAs), that register set is
+    // refilled with tile t + 4, and the barrier both publishes tile t + 1 and frees tile t's buffer.  Register sets rotate with
+    // period 3 (tile j lives in set j % 3), buffers with period 2.
+    constexpr int WBUF = TBK * TWROWA + TBK * TROWB;
+    if (nfull > 0) {
+        load_full(0, a0, b0);
+        load_full(1, a1, b1);
+        load_full(2, a2, b2);
+        store_part(0, a0, b0, -1);
+        load_full(3, a0, b0);
+        __syncthreads();
+        auto step = [&](int t, RegA& ra, RegB& rb) __attribute__((always_inline)) {   // (ra, rb) hold tile t + 1
+            multiply((t & 1) * WBUF, yes{}, ((t + 1) & 1) * WBUF, ra, rb);
+            load_full(t + 4, ra, rb);
             __syncthreads();
         };
-        auto step_last = [&](const RegA& ra, const RegB& rb) __attribute__((always_inline)) {   // no refill
-            if (!(abl & 1)) store_part(0, ra, rb, -1);
-            __syncthreads();
-            multiply(0, no{}, 0, ra, rb);
+        auto step_noload = [&](int t, const RegA& ra, const RegB& rb) __attribute__((always_inline)) {
+            multiply((t & 1) * WBUF, yes{}, ((t + 1) & 1) * WBUF, ra, rb);
             __syncthreads();
         };
-        if (nfull > 0) {
-            load_full(0, a0, b0);
-            load_full(1, a1, b1);
-            load_full(2, a2, b2);
-            int t = 0;
-            for (; t + 3 <= nfull; t += 3) {
-                step(t + 3, a0, b0);
-                step(t + 4, a1, b1);
-                step(t + 5, a2, b2);
-            }
-            if (t < nfull) {
-                step_last(a0, b0);
-                if (t + 1 < nfull) step_last(a1, b1);
-            }
+        int t = 0;
+        for (; t + 4 <= nfull; t += 3) {
+            step(t, a1, b1);
+            step(t + 1, a2, b2);
+            step(t + 2, a0, b0);
         }
-        if (krem > 0) {
-            load_partial(kbeg + nfull * TBK, a0, b0);
-            step_last(a0, b0);
+        const int left = nfull - t;   // 1, 2 or 3 tiles: t in buffer t & 1, t + 1 in (a1, b1), t + 2 in (a2, b2)
+        if (left >= 2) {
+            step_noload(t, a1, b1);
+            if (left == 3) step_noload(t + 1, a2, b2);
         }
+        multiply(((nfull - 1) & 1) * WBUF, no{}, 0, a0, b0);
+        __syncthreads();
+    }
+    if (krem > 0) {
+        load_partial(kbeg + nfull * TBK, a0, b0);
+        store_part(0, a0, b0, -1);
+        __syncthreads();
+        multiply(0, no{}, 0, a0, b0);
+        __syncthreads();
     }
     store_acc_tile<TO>(acc, tw_smem, nullptr, C, ws, M, N, ldc, accumulate, m0, n0, split, 0, 0, 0, nullptr, nullptr, 0, 0, wm * 64, wn * 64);
 }
 
-constexpr int TW_SMEM = 8 * 9216;                                   // one K-tile buffer (57 344 B) < the epilogue's 8 x 9 216 B
 constexpr int TW_SMEM_DB = 2 * (TBK * TWROWA + TBK * TROWB);       // two K-tile buffers: 114 688 B
-template <typename TO, bool DB>
+template <typename TO>
 __global__ __launch_bounds__(512) void gemm_tn_wide_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, TO* __restrict__ C,
                                                            float* __restrict__ ws, int M, int N, int K, int lda, int ldb, int ldc,
                                                            int k_per_split, int accumulate, int tiles_n, int tiles_mn, int nsplit) {
     const int lin = xcd_remap(blockIdx.x, tiles_mn * nsplit);  // whole K-slices per XCD (see gemm_tn_kernel)
-    tn_wide_body<TO, DB>(A, B, C, ws, M, N, K, lda, ldb, ldc, k_per_split, accumulate, tiles_n, lin % tiles_mn, lin / tiles_mn);
+    tn_wide_body<TO>(A, B, C, ws, M, N, K, lda, ldb, ldc, k_per_split, accumulate, tiles_n, lin % tiles_mn, lin / tiles_mn);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1625,199 +1471,12 @@ __global__ __launch_bounds__(512) void gemm_tn_tall_kernel(const bf16_t* __restr
 // weight gradients: 12 tiles each).  The batched 128 x 128 kernel moves 2.45 GB through the L2 -> LDS path for the six 33 280-row
 // gradients of a step (144 us at the ~17 TB/s that path sustains chip-wide, against 75 us of MFMA issue); this tile moves 1.84 GB.
 // tb.first_tile / tiles_n count WIDE tiles here.
-template <bool DB>
 __global__ __launch_bounds__(512) void gemm_tn_batch_wide_kernel(TnBatch tb, float* __restrict__ ws, int K, int k_per_split, int nsplit) {
     const TnWork w = tn_batch_work(tb, ws, K, k_per_split, nsplit);
     if (w.j < 0) return;
     const TnBatch::P& q = tb.p[w.j];
-    tn_wide_body<float, DB>(q.A, q.B, q.C, w.ws, q.M, q.N, w.K, q.lda, q.ldb, q.ldc, w.k_per_split, 0, q.tiles_n, w.tile, w.split);
+    tn_wide_body<float>(q.A, q.B, q.C, w.ws, q.M, q.N, w.K, q.lda, q.ldb, q.ldc, w.k_per_split, 0, q.tiles_n, w.tile, w.split);
 }
-
-#ifdef SPV_LAB   // measured slower inside the training step: kept for the lab build only
-// ---------------------------------------------------------------------------------------------------------
-// TN contraction, LDS-DMA variant: the weight gradients of the encoder layers, dW[768 x 512] = dh^T . x over 33 280 rows
-// (backward of layers.py:86).  Same output tile (128 x 128) as gemm_tn_kernel, but
-//   * operands staged by global_load_lds_dwordx4 (no staging VGPRs, no ds_write) into a THREE-stage LDS ring of 64 k rows,
-//     two stages in flight, ONE barrier per K-tile behind a counted vmcnt;
-//   * 8 waves: two K-groups (k-steps {0,1} / {2,3} of every K-tile) x 2 x 2 wave tiles of 64 x 64, so every SIMD holds two
-//     waves and one wave's transposing LDS reads run under the other's MFMAs; the two partial tiles meet in LDS at the end
-//     (each wave finishes 32 of its 64 rows);
-//   * DMA writes are lane-linear (a wave instruction = 4 k rows of 256 B), so rows cannot be padded: the 16-byte chunk index is
-//     XOR-ed with (row & 3) << 2 on the per-lane SOURCE address and again on the fragment read -- the 4 k rows x 2 column blocks
-//     that one half of a ds_read_b64_tr_b16 touches then cover 8 disjoint 32-byte bank ranges = all 64 banks.
-// Needs M, N multiples of 128 and K, the split-K slices multiples of 64 (the layer shapes); anything else: gemm_tn_kernel.
-constexpr int TDK = 64;                      // k rows per stage
-constexpr int TD_STAGE = 2 * TDK * 256;      // A tile + B tile, 256 B per k row each
-constexpr int TD_NST = 3;
-constexpr int TD_SMEM = TD_NST * TD_STAGE;   // 96 KiB (the epilogue's 64 KiB exchange + 8 x 8.5 KiB stages reuse it)
-
-// (Tried and dropped: a ninth wave touching the slice's operand lines six K-tiles ahead, on the theory that every K-tile's first
-// request pays an HBM round trip -- no change, 56.5 vs 55.4 us: the loop is bound by DMA ISSUE on the 64 B/clk L1 path, below.)
-template <typename TO>
-__global__ __launch_bounds__(512) void gemm_tn_dma_kernel(const bf16_t* __restrict__ A, const bf16_t* __restrict__ B, TO* __restrict__ C,
-                                                          float* __restrict__ ws, int M, int N, int K, int lda, int ldb, int ldc,
-                                                          int k_per_split, int accumulate, int tiles_n, int tiles_mn, int nsplit) {
-    extern __shared__ __attribute__((aligned(1024))) unsigned char td_smem[];
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int kg = wave >> 2, wm = (wave >> 1) & 1, wn = wave & 1;
-    const int lin = xcd_remap(blockIdx.x, tiles_mn * nsplit);  // whole K-slices per XCD: a slice's operand rows hit in that L2
-    const int split = lin / tiles_mn, tile = lin % tiles_mn;
-    const int m0 = (tile / tiles_n) * BM, n0 = (tile % tiles_n) * BN;
-    const int kbeg = split * k_per_split;
-    const int kend = min(K, kbeg + k_per_split);
-
-    // DMA: per stage and operand 16 wave instructions of 4 k rows; this wave issues instructions 2 wave, 2 wave + 1
-    const bf16_t* asrc[2];
-    const bf16_t* bsrc[2];
-#pragma unroll
-    for (int t = 0; t < 2; ++t) {
-        const int R = 4 * (2 * wave + t) + (lane >> 4);          // k row of the stage written by this lane
-        const int c = (lane & 15) ^ ((R & 3) << 2);              // logical 16-byte chunk that belongs at this LDS position
-        asrc[t] = A + (size_t)R * lda + m0 + c * 8;
-        bsrc[t] = B + (size_t)R * ldb + n0 + c * 8;
-    }
-    auto stage = [&](int buf, int k0) __attribute__((always_inline)) {
-        unsigned char* sa = td_smem + buf * TD_STAGE + (2 * wave) * 1024;
-        unsigned char* sb = sa + TDK * 256;
-#pragma unroll
-        for (int t = 0; t < 2; ++t) {
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc[t] + (size_t)k0 * lda),
-                                             (__attribute__((address_space(3))) void*)(sa + t * 1024), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bsrc[t] + (size_t)k0 * ldb),
-                                             (__attribute__((address_space(3))) void*)(sb + t * 1024), 16, 0, 0);
-        }
-    };
-
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int i = 0; i < 2; ++i)
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.0f;
-
-    // transposing-read geometry (as gemm_tn_kernel): group g = lane >> 4 covers columns 16 (g & 1) + [0,16) of a 32-wide MFMA
-    // block and k half g >> 1; lane 4 q + p of the group supplies row q, columns 4 p .. 4 p + 3
-    const int g = lane >> 4, li = lane & 15, q = li >> 2, pp = li & 3;
-    // byte offset inside a k row of MFMA block x (32 columns), swizzled for row & 3 == q: chunk = 4 x + 2 (g & 1) + (pp >> 1)
-    auto col_off = [&](int x) { return (((4 * x + 2 * (g & 1) + (pp >> 1)) ^ (q << 2)) << 4) + ((pp & 1) << 3); };
-    int offa[2], offb[2];
-#pragma unroll
-    for (int f = 0; f < 2; ++f) {
-        offa[f] = (8 * (g >> 1) + q) * 256 + col_off(2 * wm + f);
-        offb[f] = TDK * 256 + (8 * (g >> 1) + q) * 256 + col_off(2 * wn + f);
-    }
-    using lds_tr = s16x4 __attribute__((address_space(3)))*;
-    auto frag = [&](const unsigned char* p) __attribute__((always_inline)) {
-        const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(p));
-        const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_tr)(p + 4 * 256));
-        typedef __attribute__((ext_vector_type(8))) short s16x8;
-        const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
-        return __builtin_bit_cast(bf16x8, v);
-    };
-
-    if (kbeg < kend) stage(0, kbeg);
-    if (kbeg + TDK < kend) stage(1, kbeg + TDK);
-    int buf = 0;
-    for (int k0 = kbeg; k0 < kend; k0 += TDK) {
-        // this wave's share of stage `buf` has landed (the younger stage's 4 pieces may still fly) ...
-        if (k0 + TDK < kend) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();  // ... everyone's has, and everyone is done reading the stage refilled next
-        // The four DMA pieces of K-tile t + 2 go out ONE behind every MFMA pair of K-tile t: issued together right after the barrier
-        // the eight waves' 32 pieces (32 KiB) queue on the CU's 64 B/clk L1 path and every wave stands in issue for hundreds of
-        // cycles before its first MFMA (measured: 1 800 cycles per K-tile against 512 of MFMA issue)
-        const bool dma = k0 + 2 * TDK < kend;
-        const int nbuf = buf == 0 ? 2 : buf - 1;
-        unsigned char* da = td_smem + nbuf * TD_STAGE + (2 * wave) * 1024;
-        unsigned char* db = da + TDK * 256;
-        const size_t ka = (size_t)(k0 + 2 * TDK) * lda, kb = (size_t)(k0 + 2 * TDK) * ldb;
-        const unsigned char* st = td_smem + buf * TD_STAGE;
-#pragma unroll
-        for (int s2 = 0; s2 < 2; ++s2) {
-            const int ks = 2 * kg + s2;
-            bf16x8 a[2], b[2];
-#pragma unroll
-            for (int f = 0; f < 2; ++f) {
-                a[f] = frag(st + ks * 16 * 256 + offa[f]);
-                b[f] = frag(st + ks * 16 * 256 + offb[f]);
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (dma) {
-                    if (i == 0)
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(asrc[s2] + ka),
-                                                         (__attribute__((address_space(3))) void*)(da + s2 * 1024), 16, 0, 0);
-                    else
-                        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(bsrc[s2] + kb),
-                                                         (__attribute__((address_space(3))) void*)(db + s2 * 1024), 16, 0, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int j = 0; j < 2; ++j)
-                    acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[i], b[j], acc[i][j], 0, 0, 0);
-            }
-        }
-        buf = buf == 2 ? 0 : buf + 1;
-    }
-
-    // ---- the two K-groups meet: wave (kg, wm, wn) finishes rows [32 kg, 32 kg + 32) of its 64 x 64 block, i.e. acc[kg][*] plus
-    // the partner's acc[kg][*]; each wave hands over the half it does not finish (8 KiB per wave, lane-linear)
-    __syncthreads();  // every wave is out of the K loop: the ring is free
-    {
-        float* xch = reinterpret_cast<float*>(td_smem) + (size_t)wave * 2048;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) xch[(j * 16 + r) * 64 + lane] = kg == 0 ? acc[1][j][r] : acc[0][j][r];
-    }
-    __syncthreads();
-    f32x16 fin[2];
-    {
-        const float* xch = reinterpret_cast<const float*>(td_smem) + (size_t)(wave ^ 4) * 2048;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) fin[j][r] = (kg == 0 ? acc[0][j][r] : acc[1][j][r]) + xch[(j * 16 + r) * 64 + lane];
-    }
-    __syncthreads();  // exchange area read: reuse it as the wave-private store stages
-    {
-        // 32 x 64 block of this wave -> fp32 LDS stage [32][68] -> every lane leaves with 8 consecutive columns of a row
-        constexpr int SLD = 68;
-        float* stg = reinterpret_cast<float*>(td_smem + wave * 9216);
-        const int fh = lane >> 5;
-#pragma unroll
-        for (int j = 0; j < 2; ++j)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) stg[((r & 3) + 8 * (r >> 2) + 4 * fh) * SLD + j * 32 + (lane & 31)] = fin[j][r];
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // wave-private stage: the wave's own writes are done before it reads
-#pragma unroll
-        for (int t = 0; t < 4; ++t) {
-            const int qd = lane + 64 * t;
-            const int lr = qd >> 3, c8 = qd & 7;
-            const int row = m0 + wm * 64 + kg * 32 + lr;
-            const int col0 = n0 + wn * 64 + c8 * 8;
-            const float4 lo = *reinterpret_cast<const float4*>(stg + lr * SLD + c8 * 8);
-            const float4 hi = *reinterpret_cast<const float4*>(stg + lr * SLD + c8 * 8 + 4);
-            float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-            if (ws != nullptr) {
-                float4* wp = reinterpret_cast<float4*>(ws + ((size_t)split * M + row) * N + col0);
-                wp[0] = lo;
-                wp[1] = hi;
-                continue;
-            }
-            TO* cp = C + (size_t)row * ldc + col0;
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (accumulate) v[u] += load_out<TO>(cp + u);
-                store_out<TO>(cp + u, v[u]);
-            }
-        }
-    }
-}
-#endif  // SPV_LAB
 
 template <typename TO>
 __device__ __forceinline__ void splitk_reduce_body(const float* __restrict__ ws, const float* __restrict__ bias, TO* __restrict__ C, int M, int N,
@@ -1952,11 +1611,10 @@ int launch_gemm(const void* A, const void* B, const float* bias, void* C, int M,
     float* ws = splits > 1 ? static_cast<float*>(workspace) : nullptr;
     dim3 grid(tiles_m * tiles_n * splits);
     if constexpr (sizeof(T) == 2) {
-        static const bool no_rows = SPV_LAB_SET("SPV_GEMM_NO_ROWS");   // A/B switch
         // few rows: one 32 x 32 tile per workgroup straight from the L2-resident operands (no split-K workspace, no reduce launch)
         // (K <= 1536: a wave walks its K share in batches of 8 k-steps, one L2 round trip each -- at K = 8192 that chain is 40 us against
         // 15 + 5 for split-K + reduce; <= 1024 tiles: beyond that the 32 x 32 tiles re-read the operands 4x as often as 128 x 128 ones)
-        if (!no_rows && splits == 1 && M <= 2048 && K <= 1536 && rg == 0 && bias2d == nullptr && bc == nullptr && t_drop_p == 0.0f && K % 16 == 0 &&
+        if (splits == 1 && M <= 2048 && K <= 1536 && rg == 0 && bias2d == nullptr && bc == nullptr && t_drop_p == 0.0f && K % 16 == 0 &&
             lda % 8 == 0 && ldb % 8 == 0 && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 &&
             cdiv(M, 32) * cdiv(N, 32) >= 64 && cdiv(M, 32) * cdiv(N, 32) <= 1024) {
             const int tn32 = cdiv(N, 32);
@@ -1978,14 +1636,6 @@ int launch_gemm(const void* A, const void* B, const float* bias, void* C, int M,
     hipLaunchKernelGGL((gemm_nt_strip_kernel<MBV, EPIV>), dim3(nwg), dim3(512), 0, st, static_cast<const bf16_t*>(A),       \
                        static_cast<const bf16_t*>(B), bias, static_cast<bf16_t*>(C), M, K, lda, ldb, ldc, nstrips, base, rem, nwg, \
                        static_cast<const bf16_t*>(bc), bc_pw, bc ? N / bc_pw : 0)
-            static const int acc_mb = SPV_LAB_INT("SPV_STRIP_ACC_MB", 0);  // tuning aid
-            // diagnosis only (wrong results): every A row reads row 0, i.e. A always hits in L2 -- separates "HBM latency x one K-tile of
-            // prefetch" from "L2 -> LDS rate" as the bound of the K loop
-#ifdef SPV_LAB
-            static const bool lda0 = SPV_LAB_SET("SPV_STRIP_LDA0");
-            if (lda0) lda = 0;
-#endif
-            if (accumulate && acc_mb >= 2 && acc_mb <= 4) mb = acc_mb;
             SPV_COUNT_PATH(bc != nullptr ? SPV_PATH_GEMM_STRIP_POOL : accumulate ? SPV_PATH_GEMM_STRIP_ACC : SPV_PATH_GEMM_STRIP);
             if (bc != nullptr && bc_pw % 8 != 0) {   // two-window epilogue: its own instantiation (in the one-window kernel it cost 6 %)
                 if (mb == 4) SPV_STRIP(4, 3);
@@ -2013,22 +1663,12 @@ int launch_gemm(const void* A, const void* B, const float* bias, void* C, int M,
         // direct-to-LDS double-buffered kernel for long reductions (measured: 896 vs 795 TFLOP/s at 4096^3, 755 vs 700 on
         // the 512 x 8192 x 33280 weight gradient); the skinny K <= 1024 layer GEMMs are faster on the register-staged
         // kernel (42 vs 50 us at 33280 x 768 x 512: three workgroups per CU instead of two)
-        static const int force_kb = SPV_LAB_INT("SPV_GEMM_KB", 0);  // tuning aid: 64 / 128 / -1 (off)
         // K <= 1024 (the layer GEMMs) stays on the register-staged kernel: the three-stage 64-byte-row ring measures the
         // same step time (2.978 vs 2.972 ms over three alternating runs) and 4 us more per isolated launch
-        if (force_kb >= 0 && K % GBK == 0 && k_per_split % GBK == 0 && (force_kb || kend_len(K, k_per_split) > 1024)) {
-            const int kb = force_kb ? force_kb : 128;
-            (void)kb;
-#ifdef SPV_LAB
-            if (kb == 64)
-                hipLaunchKernelGGL((gemm_nt_glds_kernel<TO, 64, 3>), grid, dim3(256), 0, st, static_cast<const bf16_t*>(A),
-                                   static_cast<const bf16_t*>(B), bias, static_cast<TO*>(C), ws, M, N, K, lda, ldb, ldc, k_per_split,
-                                   accumulate, tiles_n, tiles_m * tiles_n, splits, rg, gs, roff, bias2d, bc, bc_pw, bc_bf, t_drop_p, t_drop_seed);
-            else
-#endif
-                hipLaunchKernelGGL((gemm_nt_glds_kernel<TO, 128, 2>), grid, dim3(256), 0, st, static_cast<const bf16_t*>(A),
-                                   static_cast<const bf16_t*>(B), bias, static_cast<TO*>(C), ws, M, N, K, lda, ldb, ldc, k_per_split,
-                                   accumulate, tiles_n, tiles_m * tiles_n, splits, rg, gs, roff, bias2d, bc, bc_pw, bc_bf, t_drop_p, t_drop_seed);
+        if (K % GBK == 0 && k_per_split % GBK == 0 && kend_len(K, k_per_split) > 1024) {
+            hipLaunchKernelGGL((gemm_nt_glds_kernel<TO, 128, 2>), grid, dim3(256), 0, st, static_cast<const bf16_t*>(A),
+                               static_cast<const bf16_t*>(B), bias, static_cast<TO*>(C), ws, M, N, K, lda, ldb, ldc, k_per_split,
+                               accumulate, tiles_n, tiles_m * tiles_n, splits, rg, gs, roff, bias2d, bc, bc_pw, bc_bf, t_drop_p, t_drop_seed);
             SPV_LAUNCH_CHECK("spv_gemm_nt(glds)");
             goto reduce;
         }
@@ -2160,30 +1800,8 @@ static int gemm_tn_impl(const void* A, const void* B, void* C, int M, int N, int
         splits = cdiv(K, k_per_split);
     }
     float* ws = splits > 1 ? static_cast<float*>(workspace) : nullptr;
-    // opt-in (SPV_TN_DMA=1): isolated it is 3-6 % faster than the register-staged kernel (52.5 vs 54.5 us incl. the reduce), inside
-    // the training step it measured SLOWER (68 vs 47 us per launch), so the register-staged kernel stays the default
-    static const int use_dma = SPV_LAB_INT("SPV_TN_DMA", 0);
-    (void)use_dma;
-    static const int use_wide = SPV_LAB_INT("SPV_TN_WIDE", 1);
-    static const int wide_min = SPV_LAB_INT("SPV_TN_WIDE_MIN", 4);   // tuning aid
-#ifdef SPV_LAB
-    if (use_dma && M % BM == 0 && N % BN == 0 && K % TDK == 0 && k_per_split % TDK == 0 && (ws != nullptr || ldc % 4 == 0)) {
-        const int nwg = tiles_m * tiles_n * splits;
-        if (out_dtype == SPV_BF16) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_dma_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, TD_SMEM);
-            hipLaunchKernelGGL((gemm_tn_dma_kernel<bf16_t>), dim3(nwg), dim3(512), TD_SMEM, st, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, ws,
-                               M, N, K, lda, ldb, ldc, k_per_split, accumulate, tiles_n, tiles_m * tiles_n, splits);
-        } else {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_dma_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, TD_SMEM);
-            hipLaunchKernelGGL((gemm_tn_dma_kernel<float>), dim3(nwg), dim3(512), TD_SMEM, st, (const bf16_t*)A, (const bf16_t*)B, (float*)C, ws,
-                               M, N, K, lda, ldb, ldc, k_per_split, accumulate, tiles_n, tiles_m * tiles_n, splits);
-        }
-        SPV_LAUNCH_CHECK("spv_gemm_tn(dma)");
-        SPV_COUNT_PATH(SPV_PATH_GEMM_TN_DMA);
-    } else
-#endif
-    static const int use_tall = SPV_LAB_INT("SPV_TN_TALL", 1);
-    if (use_tall && M == TTM && N % BN == 0 && N >= 8 * BN && tiles_n * splits >= 192 && k_per_split >= 16 * TTK) {
+    constexpr int wide_min = 4;   // fewest split-K slabs that pay for the 256 x 128 tile (see below)
+    if (M == TTM && N % BN == 0 && N >= 8 * BN && tiles_n * splits >= 192 && k_per_split >= 16 * TTK) {
         // all of M in one workgroup: the B panel (the gathered matrix of the MHPermutMix gradient) is read once
         const int nwg = tiles_n * splits;
         if (out_dtype == SPV_BF16) {
@@ -2196,44 +1814,38 @@ static int gemm_tn_impl(const void* A, const void* B, void* C, int M, int N, int
                                ldc, k_per_split, accumulate, tiles_n, tiles_n, splits);
         }
         SPV_LAUNCH_CHECK("spv_gemm_tn(tall)");
-    } else
-    if (use_wide && splits >= wide_min && M % TWM == 0 && N % BN == 0 && (M / TWM) * tiles_n * splits >= 128) {
-        // the 256 x 128 tile (8 waves, one workgroup per CU): the split-K layer weight gradients (SPV_TN_WIDE=0 for the 128 x 128
-        // kernel).  Measured in graph mode, alternating: 2.372 vs 2.385 ms/step -- 1.6 us per launch; without split-K (the MHPermutMix
-        // weight gradient, 512 x 8192 x 33 280) it is SLOWER (651 vs 510 us), hence splits >= 4
+    } else if (splits >= wide_min && M % TWM == 0 && N % BN == 0 && (M / TWM) * tiles_n * splits >= 128) {
+        // the 256 x 128 tile (8 waves, one workgroup per CU): the split-K layer weight gradients.  Measured in graph mode, alternating,
+        // against the 128 x 128 kernel: 2.372 vs 2.385 ms/step -- 1.6 us per launch; without split-K (the MHPermutMix weight gradient,
+        // 512 x 8192 x 33 280) it is SLOWER (651 vs 510 us), hence splits >= 4
         const int wt = (M / TWM) * tiles_n;
-        static const int wide_db = SPV_LAB_INT("SPV_TN_WIDE_DB", 1);   // two LDS buffers, one barrier per K-tile
-#define SPV_TNW(TOV, DBV, SM)                                                                                                             \
+#define SPV_TNW(TOV)                                                                                                                      \
     do {                                                                                                                                  \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_wide_kernel<TOV, DBV>), hipFuncAttributeMaxDynamicSharedMemorySize, SM); \
-        hipLaunchKernelGGL((gemm_tn_wide_kernel<TOV, DBV>), dim3(wt * splits), dim3(512), SM, st, (const bf16_t*)A, (const bf16_t*)B, (TOV*)C,   \
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_wide_kernel<TOV>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_SMEM_DB); \
+        hipLaunchKernelGGL((gemm_tn_wide_kernel<TOV>), dim3(wt * splits), dim3(512), TW_SMEM_DB, st, (const bf16_t*)A, (const bf16_t*)B, (TOV*)C, \
                            ws, M, N, K, lda, ldb, ldc, k_per_split, accumulate, tiles_n, wt, splits);                                     \
     } while (0)
-        if (out_dtype == SPV_BF16) {
-            if (wide_db) SPV_TNW(bf16_t, true, TW_SMEM_DB); else SPV_TNW(bf16_t, false, TW_SMEM);
-        } else {
-            if (wide_db) SPV_TNW(float, true, TW_SMEM_DB); else SPV_TNW(float, false, TW_SMEM);
-        }
+        if (out_dtype == SPV_BF16) SPV_TNW(bf16_t);
+        else SPV_TNW(float);
 #undef SPV_TNW
         SPV_LAUNCH_CHECK("spv_gemm_tn(wide)");
         SPV_COUNT_PATH(SPV_PATH_GEMM_TN_WIDE);
     } else {
-    dim3 grid(tiles_m * tiles_n * splits);
-    // One K-tile in flight (144 VGPRs, 40 KB of LDS) for the sliver-shaped gradient of the patch embedding (512 x 48 x 33 280): that
-    // launch runs on the main stream BESIDE the batched layer gradients, whose workgroups (8 waves x 184 VGPRs, 112 KB) leave exactly
-    // 144 VGPRs per SIMD and 45 KB per CU -- with three tiles in flight (216 VGPRs) its workgroups waited for those CUs to drain.
-    static const int depth_env = SPV_LAB_INT("SPV_TN_DEPTH", 0);  // tuning aid: 1 / 3 force a depth
-    const int depth = depth_env ? depth_env : (N <= 64 ? 1 : 3);
+        dim3 grid(tiles_m * tiles_n * splits);
+        // One K-tile in flight (144 VGPRs, 40 KB of LDS) for the sliver-shaped gradient of the patch embedding (512 x 48 x 33 280): that
+        // launch runs on the main stream BESIDE the batched layer gradients, whose workgroups (8 waves x 184 VGPRs, 112 KB) leave exactly
+        // 144 VGPRs per SIMD and 45 KB per CU -- with three tiles in flight (216 VGPRs) its workgroups waited for those CUs to drain.
+        const int depth = N <= 64 ? 1 : 3;
 #define SPV_TN(TOV, DV)                                                                                                     \
     hipLaunchKernelGGL((gemm_tn_kernel<TOV, DV>), grid, dim3(256), 0, st, (const bf16_t*)A, (const bf16_t*)B, (TOV*)C, ws, M, N, K, \
                        lda, ldb, ldc, k_per_split, accumulate, tiles_n, tiles_m * tiles_n, splits)
-    if (out_dtype == SPV_BF16) {
-        if (depth == 1) SPV_TN(bf16_t, 1); else SPV_TN(bf16_t, 3);
-    } else {
-        if (depth == 1) SPV_TN(float, 1); else SPV_TN(float, 3);
-    }
+        if (out_dtype == SPV_BF16) {
+            if (depth == 1) SPV_TN(bf16_t, 1); else SPV_TN(bf16_t, 3);
+        } else {
+            if (depth == 1) SPV_TN(float, 1); else SPV_TN(float, 3);
+        }
 #undef SPV_TN
-    SPV_LAUNCH_CHECK("spv_gemm_tn");
+        SPV_LAUNCH_CHECK("spv_gemm_tn");
     }
     FoldJobs fj{};
     int fold_blocks = 0;
@@ -2338,19 +1950,8 @@ static int gemm_tn_batch_impl(const spv_tn_problem* probs, int nprob, int K, int
     }
     tb.first_tile[nprob] = tiles;
     hipStream_t st = static_cast<hipStream_t>(stream);
-#ifdef SPV_LAB
-    {
-        static int last_abl = 0;
-        const int abl = SPV_LAB_INT("SPV_TN_ABLATE", 0);
-        if (abl != last_abl) {   // (a copy per launch cost every timed launch ~60 us of host synchronisation)
-            (void)hipMemcpyToSymbol(HIP_SYMBOL(g_tn_ablate), &abl, sizeof(abl));
-            last_abl = abl;
-        }
-    }
-#endif
     // the 256 x 128 tile when every problem divides into it and the K-slices are long enough to pay for its longer prologue
-    static const int wide_env = SPV_LAB_INT("SPV_TNB_WIDE", 1);
-    bool wide = wide_env != 0 && k_per_split >= 8 * TBK;
+    bool wide = k_per_split >= 8 * TBK;
     for (int i = 0; i < nprob && wide; ++i) wide = probs[i].m % TWM == 0 && probs[i].n % BN == 0 && (probs[i].k == 0 || probs[i].k >= TBK);
     if (parts & 1) {
         SPV_COUNT_PATH(SPV_PATH_GEMM_TN);
@@ -2365,28 +1966,12 @@ static int gemm_tn_batch_impl(const spv_tn_problem* probs, int nprob, int K, int
             }
             tw.first_tile[nprob] = wt;
             const int wgrid = wlong * splits + ((wt - wlong + 7) & ~7);
-            static const int wide_db = SPV_LAB_INT("SPV_TN_WIDE_DB", 1);   // two LDS buffers, one barrier per K-tile
-            if (wide_db) {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_batch_wide_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_SMEM_DB);
-                hipLaunchKernelGGL(gemm_tn_batch_wide_kernel<true>, dim3(wgrid), dim3(512), TW_SMEM_DB, st, tw, static_cast<float*>(workspace), K, k_per_split, splits);
-            } else {
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_batch_wide_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_SMEM);
-                hipLaunchKernelGGL(gemm_tn_batch_wide_kernel<false>, dim3(wgrid), dim3(512), TW_SMEM, st, tw, static_cast<float*>(workspace), K, k_per_split, splits);
-            }
+            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_batch_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TW_SMEM_DB);
+            hipLaunchKernelGGL(gemm_tn_batch_wide_kernel, dim3(wgrid), dim3(512), TW_SMEM_DB, st, tw, static_cast<float*>(workspace), K, k_per_split, splits);
             SPV_COUNT_PATH(SPV_PATH_GEMM_TN_WIDE);
         } else {
             const int grid128 = long_tiles * splits + ((tiles - long_tiles + 7) & ~7);
-#ifdef SPV_LAB
-            static const int bdepth = SPV_LAB_INT("SPV_TNB_DEPTH", 3);
-            if (SPV_LAB_INT("SPV_TNB_DB", 0) && k_per_split >= 8 * TBK) {
-                constexpr int DBSMEM = 2 * 2 * TBK * TROWB;
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_batch_db_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DBSMEM);
-                hipLaunchKernelGGL(gemm_tn_batch_db_kernel, dim3(grid128), dim3(256), DBSMEM, st, tb, static_cast<float*>(workspace), K, k_per_split, splits);
-            } else if (bdepth == 1)
-                hipLaunchKernelGGL(gemm_tn_batch_kernel<1>, dim3(grid128), dim3(256), 0, st, tb, static_cast<float*>(workspace), K, k_per_split, splits);
-            else
-#endif
-                hipLaunchKernelGGL(gemm_tn_batch_kernel<3>, dim3(grid128), dim3(256), 0, st, tb, static_cast<float*>(workspace), K, k_per_split, splits);
+            hipLaunchKernelGGL(gemm_tn_batch_kernel<3>, dim3(grid128), dim3(256), 0, st, tb, static_cast<float*>(workspace), K, k_per_split, splits);
         }
         SPV_LAUNCH_CHECK("spv_gemm_tn_batch");
     }

@@ -762,8 +762,7 @@ extern "C" int spv_permut_pack(const int64_t* perms, const float* signs, uint32_
 /* 1 when spv_permut_gather_fwd can emit the pooled skip for this window on the long-row (scatter) path */
 extern "C" int spv_permut_pool_supported(int heads, int d, int pool_window, int dtype) {
     (void)heads;
-    return (dtype == SPV_BF16 && long_row(d) && d % 8 == 0 && pool_window > 0 && d % pool_window == 0 && scat_len(d) % pool_window == 0 &&
-            !SPV_LAB_SET("SPV_GATHER_FWD_PARTS")) ? 1 : 0;
+    return (dtype == SPV_BF16 && long_row(d) && d % 8 == 0 && pool_window > 0 && d % pool_window == 0 && scat_len(d) % pool_window == 0) ? 1 : 0;
 }
 
 extern "C" int64_t spv_permut_table_words(int heads, int d) {
@@ -787,9 +786,8 @@ extern "C" int spv_permut_gather_fwd(const void* x, const uint32_t* idx, void* g
                       (total / 4) % PT == 0,
                   "spv_permut_gather_fwd: unsupported pool window %d", pool_window);
     }
-    static const bool wide_only = SPV_LAB_SET("SPV_PERMUT_WIDE");  // A/B switch: the round-1 kernels
     const int64_t total_e = (int64_t)heads * d;
-    if (!wide_only && dtype == SPV_BF16 && compact_ok(d) && (size_t)d * 4 <= (size_t)LDS_LIMIT &&
+    if (dtype == SPV_BF16 && compact_ok(d) && (size_t)d * 4 <= (size_t)LDS_LIMIT &&
         (pooled == nullptr || ((pool_window == 8 || pool_window == 16 || pool_window == 32) && (total_e / 8) % PT == 0))) {
         const Compact c = compact_of(idx, total_e);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_fwd_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
@@ -806,7 +804,7 @@ extern "C" int spv_permut_gather_fwd(const void* x, const uint32_t* idx, void* g
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_fwd_lds_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
             hipLaunchKernelGGL((gather_fwd_lds_kernel<float>), dim3(batch), dim3(PT), lds, st, (const float*)x, idx, (float*)g, heads, d, (float*)pooled, pool_window);
         }
-    } else if (!SPV_LAB_SET("SPV_GATHER_FWD_PARTS") && dtype == SPV_BF16 && long_row(d) && d % 8 == 0 && (pooled == nullptr || scat_pool) &&
+    } else if (dtype == SPV_BF16 && long_row(d) && d % 8 == 0 && (pooled == nullptr || scat_pool) &&
                (((uintptr_t)x | (uintptr_t)g) & 15) == 0 && heads <= 65535 && batch <= 65535) {
         // output quarters in LDS, filled from the inverse table's lists (spv_permut_pack)
         const ScatTail t = scat_of(const_cast<uint32_t*>(idx) + (spv_permut_table_words(heads, d) - scat_words(heads, d)) + scat_set_words(heads, d), heads, d);
@@ -839,15 +837,13 @@ extern "C" int spv_permut_gather_bwd(const void* dg, const uint32_t* idx, void* 
     const uint32_t* inv = idx + (size_t)heads * d;
     const size_t es = dtype == SPV_BF16 ? 2 : 4;
     const bool aligned = ((size_t)d * es) % 16 == 0 && d % 4 == 0;
-    static const bool wide_only = SPV_LAB_SET("SPV_PERMUT_WIDE");
-    static const bool no_dma = SPV_LAB_SET("SPV_GATHER_NO_DMA");   // A/B switch
-    if (!wide_only && !no_dma && dtype == SPV_BF16 && compact_ok(d) && ((size_t)d * 2) % 1024 == 0 && (size_t)d * 4 <= (size_t)LDS_LIMIT &&
+    if (dtype == SPV_BF16 && compact_ok(d) && ((size_t)d * 2) % 1024 == 0 && (size_t)d * 4 <= (size_t)LDS_LIMIT &&
         d <= 8 * PT * C_IT && (((uintptr_t)dg | (uintptr_t)dx) & 15) == 0) {
         const Compact c = compact_of(idx, (int64_t)heads * d);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         const int wgs = std::min(batch, 256);
         hipLaunchKernelGGL(gather_bwd_dma_kernel, dim3(wgs), dim3(PT), (size_t)d * 4, st, (const bf16_t*)dg, c.inv16, c.inv_sg, (bf16_t*)dx, heads, d, batch);
-    } else if (!wide_only && dtype == SPV_BF16 && compact_ok(d) && (size_t)d * 2 <= (size_t)LDS_LIMIT && d <= 8 * PT * C_IT) {
+    } else if (dtype == SPV_BF16 && compact_ok(d) && (size_t)d * 2 <= (size_t)LDS_LIMIT && d <= 8 * PT * C_IT) {
         const Compact c = compact_of(idx, (int64_t)heads * d);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_c16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         hipLaunchKernelGGL(gather_bwd_c16_kernel, dim3(batch), dim3(PT), (size_t)d * 2, st, (const bf16_t*)dg, c.inv16, c.inv_sg, (bf16_t*)dx, heads, d);
@@ -860,14 +856,14 @@ extern "C" int spv_permut_gather_bwd(const void* dg, const uint32_t* idx, void* 
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_lds_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
             hipLaunchKernelGGL((gather_bwd_lds_kernel<float>), dim3(batch), dim3(PT), lds, st, (const float*)dg, inv, (float*)dx, heads, d);
         }
-    } else if (!SPV_LAB_SET("SPV_GATHER_BWD_PARTS") && dtype == SPV_BF16 && long_row(d) && d % 8 == 0 && (size_t)scat_len(d) * 4 <= (size_t)LDS_LIMIT) {
+    } else if (dtype == SPV_BF16 && long_row(d) && d % 8 == 0 && (size_t)scat_len(d) * 4 <= (size_t)LDS_LIMIT) {
         // the scatter into output parts (lists built by spv_permut_pack behind the other tables)
         const ScatTail t = scat_of(const_cast<uint32_t*>(idx) + (spv_permut_table_words(heads, d) - scat_words(heads, d)), heads, d);
         const int np = scat_parts(d), L = scat_len(d);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         hipLaunchKernelGGL(gather_bwd_scatter_kernel, dim3(np, batch), dim3(1024), (size_t)L * 4, st, (const bf16_t*)dg, t.off, t.ej, t.et, (bf16_t*)dx, heads, d, L,
                            np);
-    } else if (!SPV_LAB_SET("SPV_GATHER_BWD_GLOBAL") && dtype == SPV_BF16 && d % 8 == 0 && (((uintptr_t)dg | (uintptr_t)dx | (uintptr_t)inv) & 15) == 0) {
+    } else if (dtype == SPV_BF16 && d % 8 == 0 && (((uintptr_t)dg | (uintptr_t)dx | (uintptr_t)inv) & 15) == 0) {
         // each of a sample's `heads` gradient rows serves only d lookups (the forward's ONE row serves heads x d), so a workgroup stages
         // heads x parts = 24 parts of 151 KB for its 32 768 results: 581 us per Base layer where the global path measures 438 in the
         // kernel statistics -- and still the better step (same job, alternating: 27.73 / 27.88 against 28.17 / 28.28 ms), because it

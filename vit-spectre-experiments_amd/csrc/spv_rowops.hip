@@ -1406,7 +1406,7 @@ extern "C" int spv_spectre_tail_fwd(const void* h, const void* x, const float* g
     SPV_CHECK((int64_t)n * k_in < (1ll << 31), "spv_spectre_tail_fwd: n*k_in too large");
     {
         const int fast = dtype == SPV_BF16, bfl = dtype == SPV_BF16, obf = out_dtype == SPV_BF16;
-        static const int fwd_wgs = SPV_LAB_INT("SPV_TAIL_FWD_WGS", 2048);   // tuning aid (lab build)
+        constexpr int fwd_wgs = 2048;
         dim3 lgrid(std::min(cdiv(rows, RW), fwd_wgs));
 #define LC_FWD(CO, CI)                                                                                                        \
         if (n == 64 * CO && k_in == 64 * CI && obf == bfl) {                                                                  \
@@ -1422,8 +1422,7 @@ extern "C" int spv_spectre_tail_fwd(const void* h, const void* x, const float* g
         LC_FWD(12, 48) // 3072 -> 768: linear3 at the Base width (exact windows of 4)
 #undef LC_FWD
     }
-    static const bool no_wide = SPV_LAB_SET("SPV_TAIL_NO_WIDE");   // A/B switch
-    if (!no_wide && n == RW * 64 * WCO && k_in * WR == n && (out_dtype == SPV_BF16) == (dtype == SPV_BF16) &&
+    if (n == RW * 64 * WCO && k_in * WR == n && (out_dtype == SPV_BF16) == (dtype == SPV_BF16) &&
         (((uintptr_t)h | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta) & 15) == 0) {
         const dim3 wgrid(std::min(rows, 2048));
         if (dtype == SPV_BF16) hipLaunchKernelGGL((tail_wide_fwd_kernel<1, true>), wgrid, dim3(RT), 0, st, h, x, gamma, beta, out, mean, rstd, rows, p_drop, seed);
@@ -1454,8 +1453,7 @@ static int tail_bwd_impl(const void* dout, const void* h, const float* mean, con
     SPV_CHECK((int64_t)n * k_in < (1ll << 31), "spv_spectre_tail_bwd: n*k_in too large");
     {
         const int fast = dtype == SPV_BF16, bfl = dtype == SPV_BF16, dbf = dout_dtype == SPV_BF16;
-        static const int bwd_wgs = SPV_LAB_INT("SPV_TAIL_BWD_WGS", BWD_MAX_WG);   // tuning aid (lab build), <= BWD_MAX_WG
-        const int lwgs = std::min(cdiv(rows, RW), std::min(bwd_wgs, BWD_MAX_WG));
+        const int lwgs = std::min(cdiv(rows, RW), BWD_MAX_WG);
         // no skip gradient asked for (the data-gradient GEMM adds it in its epilogue): the input width plays no part
         const int k_lc = (dx_pool == nullptr && up.src == nullptr) ? n : k_in;
 #define LC_BWD(CO, CI)                                                                                                        \
@@ -1476,8 +1474,7 @@ static int tail_bwd_impl(const void* dout, const void* h, const float* mean, con
         LC_BWD(12, 48)
 #undef LC_BWD
     }
-    static const bool no_wide = SPV_LAB_SET("SPV_TAIL_NO_WIDE");   // A/B switch
-    if (!no_wide && up.src == nullptr && n == RW * 64 * WCO && k_in * WR == n && (dout_dtype == SPV_BF16) == (dtype == SPV_BF16) &&
+    if (up.src == nullptr && n == RW * 64 * WCO && k_in * WR == n && (dout_dtype == SPV_BF16) == (dtype == SPV_BF16) &&
         (((uintptr_t)h | (uintptr_t)dout | (uintptr_t)dh | (uintptr_t)gamma | (uintptr_t)beta | (uintptr_t)partials) & 15) == 0) {
         // one workgroup per row at a time; the slab count is the same function of rows as everywhere (spv_tail_bwd_parts)
         const int wwgs = std::min(cdiv(rows, RW), BWD_MAX_WG);
@@ -1511,8 +1508,7 @@ extern "C" int spv_spectre_tail_bwd(const void* dout, const void* h, const float
 }
 
 extern "C" int spv_tail_up_supported(int n, int k_in, int dtype) {
-    static const bool off = SPV_LAB_SET("SPV_TAIL_NO_UP");
-    return (!off && n == 768 && k_in == 512 && check_dtype(dtype)) ? 1 : 0;
+    return (n == 768 && k_in == 512 && check_dtype(dtype)) ? 1 : 0;
 }
 
 extern "C" int spv_spectre_tail_bwd_up(const void* dout, const void* h, const float* mean, const float* rstd, const float* gamma,
@@ -1528,8 +1524,7 @@ extern "C" int spv_spectre_tail_bwd_up(const void* dout, const void* h, const fl
 
 // ---- linear3 tail + residual + LayerNorm-2 as one kernel each way (512 outputs from 768 inputs: the lane-contiguous <8, 12> kernels)
 extern "C" int spv_tail_ln_supported(int n, int k_in, int dtype) {
-    static const bool off = SPV_LAB_SET("SPV_TAIL_NO_FUSE");
-    return (!off && n == 512 && k_in == 768 && check_dtype(dtype)) ? 1 : 0;
+    return (n == 512 && k_in == 768 && check_dtype(dtype)) ? 1 : 0;
 }
 extern "C" int64_t spv_tail_ln_partial_floats(int n) { return (int64_t)BWD_MAX_WG * 5 * n; }
 
@@ -1575,8 +1570,7 @@ extern "C" int spv_spectre_tail_ln_bwd(const void* dout2, const void* f3, const 
 }
 
 extern "C" int spv_haar_ln_supported(int dim, int dtype) {
-    static const bool off = SPV_LAB_SET("SPV_HAAR_NO_FUSE");   // A/B switch
-    return (!off && dtype == SPV_BF16 && (dim == 512 || dim == 1024)) ? 1 : 0;
+    return (dtype == SPV_BF16 && (dim == 512 || dim == 1024)) ? 1 : 0;
 }
 
 extern "C" int spv_haar_ln_fwd(const void* x, const float* gamma, const float* beta, void* out, float* mean, float* rstd, int rows, int dim,
@@ -1633,9 +1627,8 @@ extern "C" int spv_add_layernorm_bwd(const void* dout, const void* a, const void
     SPV_CHECK(pick_cfg(n, cfg), "spv_add_layernorm_bwd: unsupported row length %d", n);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int wgs = std::min(cdiv(rows, RW), BWD_MAX_WG);
-    static const bool no_fast = SPV_LAB_SET("SPV_ADDLN_GENERIC");   // A/B switch
     const bool aligned16 = (((uintptr_t)dout | (uintptr_t)a | (uintptr_t)(b ? b : a) | (uintptr_t)din | (uintptr_t)gamma) & 15) == 0;
-    if (!no_fast && aligned16 && (n == 512 || n == 768 || n == 1024)) {
+    if (aligned16 && (n == 512 || n == 768 || n == 1024)) {
         const size_t lds = (size_t)2 * n * sizeof(float);
         const bool bf = dtype == SPV_BF16;
 #define SPV_ADDLN_FAST(MI)                                                                                                                 \

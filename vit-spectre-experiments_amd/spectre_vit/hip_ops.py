@@ -6,6 +6,7 @@ on a HIP device: a CPU tensor raises (there is deliberately no CPU / eager-PyTor
 """
 from __future__ import annotations
 
+import collections
 import ctypes
 import os
 import warnings
@@ -389,19 +390,8 @@ def _gemm_launch(a, b, bias, c, M, N, K, lda, ldb, ldc, accumulate=0, splits=1, 
                  _p(workspace), _stream())
 
 
-# Development switches: read from the environment ONLY in lab mode (SPV_LAB=1, together with the lab build of the library:
-# `make -C csrc lab`, SPV_LIB_PATH=.../libspv_hip_lab.so).  In the product configuration every one of them is its default; tests
-# that exercise an alternative path set the module attribute.
-_LAB = os.environ.get("SPV_LAB") == "1"
-
-
-def _lab(name, default):
-    return os.environ.get(name, default) if _LAB else default
-
-
-_SIDE_STREAM = _lab("SPV_SIDE_STREAM", "1") != "0"
-_SIDE_MIN_FLOPS = float(_lab("SPV_SIDE_MIN_FLOPS", "1e11"))  # weight gradients at least this big fork to the side stream
-_TN_DMA = _lab("SPV_TN_DMA", "0") == "1"  # must match the lab library's own switch (spv_gemm.hip)
+# (the flags of this module are plain attributes -- tests, spectre_vit.graph and bench.py set some; none is read from the environment)
+_SIDE_MIN_FLOPS = 1e11  # weight gradients at least this big fork to the side stream
 _side_streams = {}
 _side_keep = []  # tensors a side-stream kernel still reads/writes: kept alive until the join
 
@@ -428,8 +418,6 @@ def join_side_stream():
 # Held folds need gradient memory that outlives the node (a GradReducer sink): autograd would otherwise copy the unfinished tensor.
 # With data parallelism the bucket hooks need every gradient as soon as its node has run: nothing is held.
 # ------------------------------------------------------------------------------------------------
-import collections  # noqa: E402
-
 PATH_COUNTS = collections.Counter()   # host-side dispatch census (tests assert that the shapes they ran took the batched / side paths)
 _held_folds = []   # (partials, outputs, parts, n)
 _held_task = -2    # the autograd graph task (backward pass) the held folds belong to
@@ -440,22 +428,14 @@ FOLD_RIDERS = 6    # fold jobs a layer's own reduce launch carries
 _held_wgrads = []  # (dh, x, dw address, rows, n, k, fold or None)
 WGRAD_BATCH = 8    # problems per launch (csrc/spv_gemm.hip TNB_MAX)
 BATCH_FOLDS = 16   # fold jobs the batch's reduce launch carries (FJ_MAX)
-_WGRAD_HOLD = _lab("SPV_WGRAD_BATCH", "1") != "0"
-_WGRAD_SPLITS = int(_lab("SPV_WGRAD_BATCH_SPLITS", "0"))   # tuning aid: 0 = chosen per batch
-_WGRAD_SIDE = _lab("SPV_WGRAD_SIDE", "1") != "0"            # the batch starts on the side stream beside the embedding's backward
-NO_HOLD = bool(_lab("SPV_NO_HOLD", ""))         # nothing is held back (the launch sequence of the overlapped data-parallel path)
-FOLD_RIDE = not _lab("SPV_NO_FOLD_RIDE", "")    # tail folds ride in their layer's weight-gradient reduce
+_WGRAD_HOLD = True   # layer weight gradients are held for the batch launch
+FOLD_RIDE = True     # tail folds ride in their layer's weight-gradient reduce
 
 
 # Under data parallelism the overlapped (eager) exchange needs every gradient as soon as its node has run, so nothing is held.  A
 # step that exchanges its gradients in ONE call after the backward pass (spectre_vit.graph.GraphedDPStep) has no such need and
 # sets this flag while its backward passes run.
 HOLD_UNDER_DP = False
-WGRAD_PER_LAYER = _lab("SPV_WGRAD_PER_LAYER", "0") == "1"   # lab: each layer's two weight gradients as their own side-stream batch, started when
-# that layer's backward is done (operands still in the Infinity Cache) instead of one batch at the end of the pass
-FOLDS_BESIDE_BATCH = False   # True: start_held_wgrads issues the held folds as their own launch on the main stream, beside the batch,
-# instead of as extra workgroups of its reduce.  Measured (round 3): the reduce drops 29 -> 17 us, but the 68-us fold launch then
-# stands in front of the embedding's backward on the main stream, which becomes the longer chain: window 251 -> 266 us.  Off.
 TIME_HELD = False   # bench.py's roofline pass: bracket the launch sequence the headline times (held + batched weight gradients)
 
 
@@ -477,7 +457,7 @@ def _queue_end_of_backward(fn):
 def _hold_ok():
     if not _HOLD_API:
         return False
-    if NO_HOLD or (_timing() and not TIME_HELD):
+    if _timing() and not TIME_HELD:
         return False
     if HOLD_UNDER_DP:
         return True
@@ -498,8 +478,6 @@ def _fold_array(folds):
 def _batch_splits(tiles):
     """K-slices of a batch of `tiles` 128 x 128 tiles: the count whose workgroups fill whole rounds of the chip's ~512 slots (two
     4-wave workgroups per CU) best; measured on 192 tiles: 5 slices (960 workgroups) 307 us, 2: 321, 4: 355, 3: 396"""
-    if _WGRAD_SPLITS > 0:
-        return _WGRAD_SPLITS
     if 160 <= tiles <= 224:
         # the six 33 280-row layer gradients of the Small model (192 tiles): re-measured in round 3 on both tile shapes of the batched
         # kernel (tools/tnb_bench.py: 3: 296 / 278 us, 4: 305 / 341, 5: 259 / 281, 6: 247 / 249, 7: 231 / 229, 8: 256 / 267, 10: 242 / 240)
@@ -514,11 +492,10 @@ def _batch_splits(tiles):
     return best
 
 
-def _flush_held_wgrads(folds_out=None):
+def _flush_held_wgrads():
     """the weight gradients held back during this backward pass: one launch (+ one reduce that carries their folds and the folds held
     so far) per group of up to eight.  Returns every tensor the launches read or write (operands, fold partials, split-K
-    workspaces): a caller that runs this on a side stream keeps them alive until the streams are joined.  folds_out (a list): the
-    folds are NOT given to the reduce but appended to it -- the caller launches them itself (start_held_wgrads: on the main stream)."""
+    workspaces): a caller that runs this on a side stream keeps them alive until the streams are joined."""
     used = []
     while _held_wgrads:
         # up to eight per launch, the long reductions first; gradients over fewer rows (the CLS-only last layer's: 512) ride in the same
@@ -542,9 +519,6 @@ def _flush_held_wgrads(folds_out=None):
                 folds.append(fold)
         while _held_folds and len(folds) < BATCH_FOLDS:
             folds.append(_held_folds.pop(0))
-        if folds_out is not None:
-            folds_out += folds
-            folds = []
         splits = max(1, min(_batch_splits(tiles), rows // 256))   # (the CLS-only last layer: 512 rows)
         ws = torch.empty((splits * floats,), dtype=torch.float32, device=group[0][0].device)
         used.append(ws)
@@ -569,22 +543,12 @@ def start_held_wgrads():
     """Called by the LAST node of the backward pass that does real work (the patch embedding): every layer's weight gradient is held
     by now, so their batch starts here on the side stream and runs beside the embedding's backward -- a chain of small, latency-bound
     launches that leaves most of the chip idle.  The end-of-pass callback joins the streams.  True when something was started."""
-    if not (_WGRAD_SIDE and _held_wgrads and _held_task == _graph_task_id()) or _timing():
+    if not (_held_wgrads and _held_task == _graph_task_id()) or _timing():
         return False   # (a timed pass keeps the batch on the main stream: its event brackets must not overlap other kernels)
     side = _side_stream(_held_wgrads[0][0].device)
     side.wait_stream(torch.cuda.current_stream())
-    folds = []
     with torch.cuda.stream(side):
-        used = _flush_held_wgrads(folds if FOLDS_BESIDE_BATCH else None)
-    if folds:
-        # the folds (column sums of the tails' partial slabs: nothing reads them before the optimizer) as ONE launch of 256-thread
-        # workgroups on the MAIN stream: they fit on the CUs beside the batch's workgroups and are done long before it ends -- as
-        # extra workgroups of its reduce they were 16 of that launch's 29 us, behind the batch
-        while _held_folds:
-            folds.append(_held_folds.pop(0))
-        arr = _fold_array(folds)
-        _native.call("spv_fold_multi", ctypes.addressof(arr), len(folds), _stream())
-        used += [f[0] for f in folds]
+        used = _flush_held_wgrads()
     # everything the side-stream launches touch stays referenced until join_side_stream(): the operands AND the fold partials (they
     # were allocated on the main stream and had no other owner once the flush returned -- the caching allocator could hand their
     # blocks to the embedding's backward, which runs on the main stream beside the batch, before the reduce has read them)
@@ -654,7 +618,7 @@ def _hold_fold(partials, outs, sinks, parts, n):
 def _fold_rides(dtype, rows, n, k):
     """the tail backward's fold can ride in this weight gradient's split-K reduce (bf16 TN path on the main stream)"""
     return (dtype == torch.bfloat16 and n % 8 == 0 and k % 8 == 0 and FOLD_RIDE
-            and not (_SIDE_STREAM and not _timing() and 2.0 * rows * n * k >= _SIDE_MIN_FLOPS))
+            and not (not _timing() and 2.0 * rows * n * k >= _SIDE_MIN_FLOPS))
 
 
 def _fold_job(partials, outs, rows, n):
@@ -686,10 +650,6 @@ def _weight_grad(dh, x, rows, n, k, sink=None, fold=None, fold_sunk=False, out=N
     # (The 256 x 128 tile at 4 slices is 8 % faster on the MHPermutMix gradient [512, 8192, 33280] in isolation -- 320 against 348 us --
     # and SLOWER where it runs, on the side stream beside the data-gradient GEMM and the inverse gather: 701 against ~500 us, step 5.92
     # -> 6.25 ms.  Its 112 KB of LDS per workgroup leave those kernels less of every CU than the 128 x 128 tile's 40 KB.)
-    if _TN_DMA and n % 128 == 0 and k % 128 == 0 and rows % 64 == 0 and dh.dtype == torch.bfloat16:
-        # the LDS-DMA kernel (spv_gemm.hip gemm_tn_dma_kernel; opt-in, SPV_TN_DMA=1) runs ONE 8-wave workgroup per CU: one dispatch
-        # round of <= 256 workgroups (24 tiles x 10 K-slices of 52 K-tiles at the layer shapes)
-        splits = max(1, min(256 // tiles, rows // 64))
     ws = None
     if dh.dtype == torch.bfloat16 and n % 8 == 0 and k % 8 == 0:
         if tiles >= 8 and 2.0 * rows * n * k < _SIDE_MIN_FLOPS and _hold_wgrad(dh, x, dw, sink, rows, n, k, fold, fold_sunk):
@@ -708,7 +668,7 @@ def _weight_grad(dh, x, rows, n, k, sink=None, fold=None, fold_sunk=False, out=N
                              len(folds), _stream())
             else:
                 _native.call("spv_gemm_tn", _p(dh), _p(x), _p(dw), n, k, rows, n, k, k, F32, 0, splits, _p(ws), _stream())
-        if _SIDE_STREAM and not _timing() and 2.0 * rows * n * k >= _SIDE_MIN_FLOPS:
+        if not _timing() and 2.0 * rows * n * k >= _SIDE_MIN_FLOPS:
             # a big weight gradient (the MHPermutMix 8192 -> 512 linear: 279 GFLOP) has no consumer inside the backward
             # chain: run it on a second HIP stream so that it fills the ramp/tail gaps of the data-gradient GEMM and
             # overlaps the HBM-bound inverse gather on the main stream (10.57 -> 10.38 ms/step).  Not worth it for the
@@ -1781,8 +1741,6 @@ class FNetResidualFn(torch.autograd.Function):
     def backward(ctx, dout):
         sn = ctx.saved
         B, N, D = ctx.shape
-        if WGRAD_PER_LAYER:
-            start_held_wgrads()   # this layer's two weight gradients (held by the feed-forward half's backward, just done): side stream
         d2 = dout.reshape(-1, D)
         if not d2.is_contiguous():
             d2 = d2.contiguous()
