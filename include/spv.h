@@ -56,6 +56,7 @@ enum {
     SPV_PATH_TOKEN_UNPOOL = 19,  /* spv_token_pool_bwd */
     SPV_PATH_ATTN_ROW0_FWD = 20, /* spv_attention_row0_fwd (the attention mixer's CLS-only last layer) */
     SPV_PATH_ATTN_ROW0_BWD = 21, /* spv_attention_row0_bwd */
+    SPV_PATH_AUGMENT = 22,       /* spv_augment_u8 (the training transform chain, one workgroup per image) */
     SPV_PATH_COUNT = 24
 };
 long long spv_path_count(int which);
@@ -461,6 +462,65 @@ int spv_conv3x3_wgrad(const void* dy, const void* x, float* dw, void* dyt, void*
 int spv_token_pool_fwd(const void* y, void* out, int B, int L, int C, int T, int ldo, int dtype, void* stream);
 /* its transpose: dy [B][L][C] = sum over the windows holding l of dout[b][t][c] / |window t| (+ add [B][L][C] when not NULL) */
 int spv_token_pool_bwd(const void* dout, int ldo, const void* add, void* dy, int B, int L, int C, int T, int dtype, void* stream);
+
+/* ---- training augmentation: the transform chain of spectre_vit/repl/train.py:100-115 on the device --------------------------
+ * RandomHorizontalFlip -> ColorJitter -> RandomGrayscale -> RandomAffine(degrees) -> RandomApply([GaussianBlur(3)]) -> ToTensor ->
+ * Normalize -> RandomErasing, as torchvision defines the ops on FLOAT tensors in [0, 1] (no rounding to 8 bits between the ops; the
+ * reference's PIL pipeline rounds after every op -- the stated deviation, at most one 8-bit step per op).
+ *
+ * Parameter table: SPV_AUG_NPARAM fp32 per sample,
+ *   [SPV_AUG_FLIP] 0 / 1                   [SPV_AUG_BRIGHT] [SPV_AUG_CONTRAST] [SPV_AUG_SAT] blend factors (1 = identity)
+ *   [SPV_AUG_HUE] hue shift in turns (0 = skipped)       [SPV_AUG_ORDER] 0..23: the order of the four jitter ops, the index of the
+ *   permutation of (brightness, contrast, saturation, hue) in lexicographic order (0 = b c s h, 23 = h s c b)
+ *   [SPV_AUG_GRAY] 0 / 1                   [SPV_AUG_ANGLE] rotation in DEGREES (0 = skipped; the kernel takes cos and sin itself)
+ *   [SPV_AUG_BLUR] 0 / 1, [SPV_AUG_SIGMA]  [SPV_AUG_ERASE_I / _J / _H / _W] top, left, height, width of the erased rectangle
+ *   (height 0 or width 0 = none); entries 14 and 15 are written zero and not read.
+ *
+ * spv_augment_params fills the table on the device, one thread per sample, from the library's counter hash (the mix32 of the dropout
+ * masks) keyed by (seed, step, sample slot, draw index): no host synchronisation, no torch generator.  The stream of numbers is the
+ * library's own, not torchvision's.  Draw indices: 0 flip, 1-3 brightness / contrast / saturation, 4 hue, 5 order, 6 grayscale,
+ * 7 angle, 8 blur, 9 sigma, 10 erase, then for attempt a < 10 of RandomErasing's search 11 + 4 a: area, log-ratio, top, left
+ * (h = round(sqrt(area ratio)), w = round(sqrt(area / ratio)), accepted when h < H and w < W, top-left uniform on the positions that keep it inside; none accepted = no erase).
+ * Every Bernoulli is "uniform < p", every range [lo, hi] is lo + (hi - lo) u: p = 0 or lo == hi switches a draw off. */
+#define SPV_AUG_NPARAM 16
+#define SPV_AUG_FLIP 0
+#define SPV_AUG_BRIGHT 1
+#define SPV_AUG_CONTRAST 2
+#define SPV_AUG_SAT 3
+#define SPV_AUG_HUE 4
+#define SPV_AUG_ORDER 5
+#define SPV_AUG_GRAY 6
+#define SPV_AUG_ANGLE 7
+#define SPV_AUG_BLUR 8
+#define SPV_AUG_SIGMA 9
+#define SPV_AUG_ERASE_I 10
+#define SPV_AUG_ERASE_J 11
+#define SPV_AUG_ERASE_H 12
+#define SPV_AUG_ERASE_W 13
+typedef struct spv_augment_cfg {   /* a HOST struct, read during the call */
+    float flip_p;
+    float bright_lo, bright_hi, contrast_lo, contrast_hi, sat_lo, sat_hi, hue_lo, hue_hi;
+    float gray_p;
+    float degrees;                 /* angle U[-degrees, degrees] */
+    float blur_p, sigma_lo, sigma_hi;
+    float erase_p, scale_lo, scale_hi, ratio_lo, ratio_hi;
+} spv_augment_cfg;
+int spv_augment_params(float* params, int batch, int chans, int height, int width, const spv_augment_cfg* cfg, uint64_t seed,
+                       uint64_t step, void* stream);
+/* 1 when spv_augment_u8 can stage the image: chans 1 or 3, height and width >= 2, and two fp32 copies of the image within the 64 KiB
+ * of LDS a workgroup may take (3 x 32 x 32 and 1 x 28 x 28 fit; 224 x 224 does not). */
+int spv_augment_supported(int chans, int height, int width);
+/* Applies the chain: out_nchw[b] (fp32 [chans][height][width], normalised) from src_nhwc[index[b]] (uint8 [height][width][chans], the
+ * loader's layout as spv_patchify_u8 takes it; index == NULL: rows 0..batch-1) and params[b].  A pure function of its arguments.
+ * Per image, on floats: u8 / 255 mirrored in W if flip; the four jitter ops in the drawn order, each clamped to [0, 1] (brightness
+ * x b; contrast c x + (1 - c) mean(grey); saturation s x + (1 - s) grey; hue by torchvision's hexcone RGB <-> HSV round trip, h :=
+ * frac(h + shift)), grey = 0.2989 R + 0.587 G + 0.114 B (chans == 1: grey = the pixel, saturation and hue the identity); grayscale;
+ * nearest-neighbour rotation about (W/2, H/2) with zero fill; separable 3-tap Gaussian blur with reflect padding; (x - mean[c])
+ * inv_std[c]; erased rectangle := 0.  DESIGN.md section 4c has the formulas.
+ * An index outside [0, n_src) cannot be seen by the host (the index lives on the device, and calls never synchronise): the kernel
+ * reads nothing for such a row and writes NaN to its whole image. */
+int spv_augment_u8(const unsigned char* src_nhwc, const int64_t* index, const float* params, const float* mean, const float* inv_std,
+                   float* out_nchw, int batch, int n_src, int chans, int height, int width, void* stream);
 
 #ifdef __cplusplus
 }

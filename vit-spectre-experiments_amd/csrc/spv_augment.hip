@@ -1,0 +1,330 @@
+// Training augmentation on the device: the transform chain of the reference's loader (spectre_vit/repl/train.py:100-115,
+// RandomHorizontalFlip -> ColorJitter -> RandomGrayscale -> RandomAffine -> RandomApply([GaussianBlur(3)]) -> ToTensor -> Normalize ->
+// RandomErasing) as two kernels: spv_augment_params draws the per-sample parameter table, spv_augment_u8 applies it, one workgroup per
+// image with the image staged in LDS.  Definitions: include/spv.h and DESIGN.md section 4c.
+#include "spv_common.h"
+#include <math.h>
+
+constexpr int AUG_THREADS = 256;
+constexpr int AUG_WAVES = AUG_THREADS / 64;
+static_assert(AUG_WAVES == 4, "the contrast mean adds four per-wave partial sums");
+constexpr int AUG_LDS_BYTES = 64 * 1024;   // what a workgroup may take without an opt-in attribute
+constexpr int AUG_RED_FLOATS = 8;          // per-wave partial sums of the contrast mean
+
+static inline size_t aug_lds_bytes(int chans, int height, int width) {
+    return ((size_t)2 * chans * height * width + AUG_RED_FLOATS) * sizeof(float);
+}
+
+extern "C" int spv_augment_supported(int chans, int height, int width) {
+    if (!(chans == 1 || chans == 3) || height < 2 || width < 2 || height > 4096 || width > 4096) return 0;
+    return aug_lds_bytes(chans, height, width) <= (size_t)AUG_LDS_BYTES ? 1 : 0;
+}
+
+// ---------------------------------------------------------------- parameter draws
+// uniform in [0, 1) with 24 bits, draw `d` of the sample whose key is `key`
+__device__ __forceinline__ float aug_u01(unsigned key, unsigned d) {
+    return (float)(mix32(key + (d + 1u) * 0xc2b2ae35u) >> 8) * (1.0f / 16777216.0f);
+}
+__device__ __forceinline__ float aug_range(float lo, float hi, float u) { return lo + (hi - lo) * u; }
+
+__global__ __launch_bounds__(AUG_THREADS) void augment_params_kernel(float* __restrict__ params, int B, int H, int W, spv_augment_cfg c,
+                                                                     uint64_t seed, uint64_t step) {
+    const int s = blockIdx.x * AUG_THREADS + threadIdx.x;
+    if (s >= B) return;
+    unsigned key = mix32((unsigned)seed + 0x9e3779b1u) ^ mix32((unsigned)(seed >> 32) + 0x7f4a7c15u);
+    key = mix32(key + (unsigned)step * 0x85ebca6bu) ^ mix32((unsigned)(step >> 32) + 0x27d4eb2fu);
+    key = mix32(key + (unsigned)s * 0x9e3779b1u);
+    float p[SPV_AUG_NPARAM];
+#pragma unroll
+    for (int i = 0; i < SPV_AUG_NPARAM; ++i) p[i] = 0.0f;
+    p[SPV_AUG_FLIP] = aug_u01(key, 0) < c.flip_p ? 1.0f : 0.0f;
+    p[SPV_AUG_BRIGHT] = aug_range(c.bright_lo, c.bright_hi, aug_u01(key, 1));
+    p[SPV_AUG_CONTRAST] = aug_range(c.contrast_lo, c.contrast_hi, aug_u01(key, 2));
+    p[SPV_AUG_SAT] = aug_range(c.sat_lo, c.sat_hi, aug_u01(key, 3));
+    p[SPV_AUG_HUE] = aug_range(c.hue_lo, c.hue_hi, aug_u01(key, 4));
+    p[SPV_AUG_ORDER] = (float)min((int)(aug_u01(key, 5) * 24.0f), 23);
+    p[SPV_AUG_GRAY] = aug_u01(key, 6) < c.gray_p ? 1.0f : 0.0f;
+    p[SPV_AUG_ANGLE] = aug_range(-c.degrees, c.degrees, aug_u01(key, 7));
+    p[SPV_AUG_BLUR] = aug_u01(key, 8) < c.blur_p ? 1.0f : 0.0f;
+    p[SPV_AUG_SIGMA] = aug_range(c.sigma_lo, c.sigma_hi, aug_u01(key, 9));
+    if (aug_u01(key, 10) < c.erase_p) {
+        // RandomErasing.get_params: up to ten attempts, the first rectangle that fits wins
+        const float area = (float)(H * W), llo = logf(c.ratio_lo), lhi = logf(c.ratio_hi);
+        for (int a = 0; a < 10; ++a) {
+            const unsigned d = 11u + 4u * (unsigned)a;
+            const float ea = area * aug_range(c.scale_lo, c.scale_hi, aug_u01(key, d));
+            const float ratio = expf(aug_range(llo, lhi, aug_u01(key, d + 1)));
+            const int h = (int)rintf(sqrtf(ea * ratio)), w = (int)rintf(sqrtf(ea / ratio));
+            if (!(h < H && w < W)) continue;
+            p[SPV_AUG_ERASE_I] = (float)min((int)(aug_u01(key, d + 2) * (float)(H - h + 1)), H - h);
+            p[SPV_AUG_ERASE_J] = (float)min((int)(aug_u01(key, d + 3) * (float)(W - w + 1)), W - w);
+            p[SPV_AUG_ERASE_H] = (float)h;
+            p[SPV_AUG_ERASE_W] = (float)w;
+            break;
+        }
+    }
+    float4* o = reinterpret_cast<float4*>(params + (size_t)s * SPV_AUG_NPARAM);
+#pragma unroll
+    for (int i = 0; i < SPV_AUG_NPARAM / 4; ++i) o[i] = make_float4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]);
+}
+
+extern "C" int spv_augment_params(float* params, int batch, int chans, int height, int width, const spv_augment_cfg* cfg, uint64_t seed,
+                                  uint64_t step, void* stream) {
+    SPV_CHECK(params != nullptr && cfg != nullptr, "spv_augment_params: params / cfg missing");
+    SPV_CHECK(((uintptr_t)params & 15) == 0, "spv_augment_params: params must be 16-byte aligned");
+    SPV_CHECK(batch > 0 && (chans == 1 || chans == 3) && height >= 2 && width >= 2 && height <= 4096 && width <= 4096,
+              "spv_augment_params: bad shape batch=%d chans=%d %dx%d", batch, chans, height, width);
+    const spv_augment_cfg& c = *cfg;
+    const bool probs = c.flip_p >= 0.0f && c.flip_p <= 1.0f && c.gray_p >= 0.0f && c.gray_p <= 1.0f && c.blur_p >= 0.0f &&
+                       c.blur_p <= 1.0f && c.erase_p >= 0.0f && c.erase_p <= 1.0f;
+    SPV_CHECK(probs, "spv_augment_params: a probability outside [0, 1]");
+    const bool ranges = c.bright_lo >= 0.0f && c.bright_lo <= c.bright_hi && c.contrast_lo >= 0.0f && c.contrast_lo <= c.contrast_hi &&
+                        c.sat_lo >= 0.0f && c.sat_lo <= c.sat_hi && c.hue_lo >= -0.5f && c.hue_lo <= c.hue_hi && c.hue_hi <= 0.5f &&
+                        c.degrees >= 0.0f && c.degrees <= 180.0f && c.sigma_lo > 0.0f && c.sigma_lo <= c.sigma_hi && c.scale_lo >= 0.0f &&
+                        c.scale_lo <= c.scale_hi && c.scale_hi <= 1.0f && c.ratio_lo > 0.0f && c.ratio_lo <= c.ratio_hi;
+    SPV_CHECK(ranges, "spv_augment_params: a range is empty or outside its op's domain");
+    hipLaunchKernelGGL(augment_params_kernel, dim3(cdiv(batch, AUG_THREADS)), dim3(AUG_THREADS), 0, static_cast<hipStream_t>(stream), params,
+                       batch, height, width, c, seed, step);
+    SPV_LAUNCH_CHECK("spv_augment_params");
+    return 0;
+}
+
+// ---------------------------------------------------------------- the chain
+__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
+__device__ __forceinline__ float grey_of(float r, float g, float b) { return 0.2989f * r + 0.587f * g + 0.114f * b; }
+
+// torchvision's _rgb2hsv / _hsv2rgb (the hexcone formulas) with h := frac(h + shift) between them
+__device__ __forceinline__ void hue_shift(float& r, float& g, float& b, float shift) {
+    const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
+    const float d = mx - mn;
+    const bool flat = d == 0.0f;
+    const float v = mx;
+    const float s = flat ? 0.0f : d / mx;
+    const float dd = flat ? 1.0f : d;
+    const float rc = (mx - r) / dd, gc = (mx - g) / dd, bc = (mx - b) / dd;
+    const float h6 = mx == r ? bc - gc : (mx == g ? 2.0f + rc - bc : 4.0f + gc - rc);
+    float h = h6 / 6.0f + 1.0f;
+    h -= floorf(h);
+    h += shift;
+    h -= floorf(h);
+    const float h6b = h * 6.0f;
+    const float fi = floorf(h6b);
+    const float f = h6b - fi;
+    int i = (int)fi % 6;
+    const float p = clamp01(v * (1.0f - s));
+    const float q = clamp01(v * (1.0f - s * f));
+    const float t = clamp01(v * (1.0f - s * (1.0f - f)));
+    r = i == 0 ? v : (i == 1 ? q : (i == 2 ? p : (i == 3 ? p : (i == 4 ? t : v))));
+    g = i == 0 ? t : (i == 1 ? v : (i == 2 ? v : (i == 3 ? q : (i == 4 ? p : p))));
+    b = i == 0 ? p : (i == 1 ? p : (i == 2 ? t : (i == 3 ? v : (i == 4 ? v : q))));
+}
+
+// LDS: two planar [C][H][W] fp32 images (12 KiB each at 3 x 32 x 32) + the reduction slots.  Planar, so that the per-pixel passes touch
+// consecutive addresses per channel (no bank conflict) and the result leaves as it lies (NCHW).  The rotation's gather reads address
+// sy * W + sx: at W = 32 and |angle| <= 30 degrees two lanes of a 32-lane group (one output row) meet on a bank only with equal sx and
+// sy two rows apart, which needs >= 4 pixels along the row (sin 30 = 0.5) over which sx has moved by >= 3 (cos 30 = 0.87): conflict free.
+// Thread t owns pixels t, t + 256, ... through the jitter and grayscale ops (no barrier between them; the contrast mean is the one
+// workgroup reduction); rotation and blur read neighbours, with a barrier in front of each pass.
+template <int C>
+__global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const unsigned char* __restrict__ src, const int64_t* __restrict__ index,
+                                                                 const float* __restrict__ params, const float* __restrict__ mean,
+                                                                 const float* __restrict__ inv_std, float* __restrict__ out, int n_src,
+                                                                 int H, int W, int vec) {
+    extern __shared__ float lds[];
+    const int HW = H * W, CHW = C * HW;
+    float* cur = lds;
+    float* oth = lds + CHW;
+    float* red = lds + 2 * CHW;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const float* p = params + (size_t)b * SPV_AUG_NPARAM;
+    float* o = out + (size_t)b * CHW;
+    const int64_t row = index != nullptr ? index[b] : (int64_t)b;
+    if (row < 0 || row >= (int64_t)n_src) {   // workgroup uniform: nothing is read, the image is poisoned
+        for (int e = tid; e < CHW; e += AUG_THREADS) o[e] = __builtin_nanf("");
+        return;
+    }
+    const unsigned char* img = src + (size_t)row * CHW;
+
+    // 1. load u8 / 255, mirrored in W if flip: the owner of output pixel (y, x) reads source pixel (y, W - 1 - x)
+    const bool flip = p[SPV_AUG_FLIP] != 0.0f;
+    for (int px = tid; px < HW; px += AUG_THREADS) {
+        const int y = px / W, x = px - y * W;
+        const unsigned char* s = img + (size_t)(y * W + (flip ? W - 1 - x : x)) * C;
+#pragma unroll
+        for (int c = 0; c < C; ++c) cur[c * HW + px] = (float)s[c] / 255.0f;
+    }
+
+    // 2. ColorJitter: the four ops in the order the permutation index names (lexicographic over b, c, s, h = 0, 1, 2, 3)
+    {
+        int idx = (int)p[SPV_AUG_ORDER];
+        idx = idx < 0 ? 0 : (idx > 23 ? 23 : idx);
+        unsigned avail = 0x3210u;   // the ops not yet used, one per nibble, ascending
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int n = k == 0 ? idx / 6 : (k == 1 ? (idx % 6) / 2 : (k == 2 ? idx % 2 : 0));
+            const int op = (int)((avail >> (4 * n)) & 0xfu);
+            avail = (avail & ((1u << (4 * n)) - 1u)) | ((avail >> (4 * n + 4)) << (4 * n));
+            if (op == 0) {
+                const float f = p[SPV_AUG_BRIGHT];
+                for (int px = tid; px < HW; px += AUG_THREADS) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) cur[c * HW + px] = clamp01(cur[c * HW + px] * f);
+                }
+            } else if (op == 1) {
+                const float f = p[SPV_AUG_CONTRAST];
+                float part = 0.0f;
+                for (int px = tid; px < HW; px += AUG_THREADS) {
+                    if constexpr (C == 3) part += grey_of(cur[px], cur[HW + px], cur[2 * HW + px]);
+                    else part += cur[px];
+                }
+                part = wave_sum(part);
+                if ((tid & 63) == 0) red[tid >> 6] = part;
+                __syncthreads();
+                const float m = ((red[0] + red[1]) + (red[2] + red[3])) / (float)HW;
+                const float add = (1.0f - f) * m;
+                for (int px = tid; px < HW; px += AUG_THREADS) {
+#pragma unroll
+                    for (int c = 0; c < C; ++c) cur[c * HW + px] = clamp01(f * cur[c * HW + px] + add);
+                }
+            } else if (op == 2) {
+                if constexpr (C == 3) {
+                    const float f = p[SPV_AUG_SAT];
+                    for (int px = tid; px < HW; px += AUG_THREADS) {
+                        const float r = cur[px], g = cur[HW + px], bl = cur[2 * HW + px];
+                        const float gr = (1.0f - f) * grey_of(r, g, bl);
+                        cur[px] = clamp01(f * r + gr);
+                        cur[HW + px] = clamp01(f * g + gr);
+                        cur[2 * HW + px] = clamp01(f * bl + gr);
+                    }
+                }
+            } else {
+                if constexpr (C == 3) {
+                    const float shift = p[SPV_AUG_HUE];
+                    if (shift != 0.0f) {
+                        for (int px = tid; px < HW; px += AUG_THREADS) {
+                            float r = cur[px], g = cur[HW + px], bl = cur[2 * HW + px];
+                            hue_shift(r, g, bl, shift);
+                            cur[px] = r;
+                            cur[HW + px] = g;
+                            cur[2 * HW + px] = bl;
+                        }
+                    }
+                }
+            }
+        }
+    }
+
+    // 3. grayscale
+    if constexpr (C == 3) {
+        if (p[SPV_AUG_GRAY] != 0.0f) {
+            for (int px = tid; px < HW; px += AUG_THREADS) {
+                const float gr = grey_of(cur[px], cur[HW + px], cur[2 * HW + px]);
+                cur[px] = gr;
+                cur[HW + px] = gr;
+                cur[2 * HW + px] = gr;
+            }
+        }
+    }
+
+    // 4. rotation: nearest neighbour through the inverse map torchvision hands to PIL, zero fill
+    const float angle = p[SPV_AUG_ANGLE];
+    if (angle != 0.0f) {
+        __syncthreads();
+        const float rad = -angle * 0.017453292519943295f;
+        const float cs = cosf(rad), sn = sinf(rad);
+        const float cx = 0.5f * (float)W, cy = 0.5f * (float)H;
+        const float tx = cx - cx * cs - cy * sn, ty = cy + cx * sn - cy * cs;
+        for (int px = tid; px < HW; px += AUG_THREADS) {
+            const int y = px / W, x = px - y * W;
+            const float X = (float)x + 0.5f, Y = (float)y + 0.5f;
+            const float sx = cs * X + sn * Y + tx, sy = -sn * X + cs * Y + ty;
+            const int ix = (int)floorf(sx), iy = (int)floorf(sy);
+            const bool in = ix >= 0 && ix < W && iy >= 0 && iy < H;
+            const int sp = in ? iy * W + ix : 0;
+#pragma unroll
+            for (int c = 0; c < C; ++c) oth[c * HW + px] = in ? cur[c * HW + sp] : 0.0f;
+        }
+        float* t = cur; cur = oth; oth = t;
+    }
+
+    // 5. blur: separable 3 taps, reflect padding (index -1 -> 1, W -> W - 2)
+    if (p[SPV_AUG_BLUR] != 0.0f) {
+        const float sigma = p[SPV_AUG_SIGMA];
+        const float e = expf(-1.0f / (2.0f * sigma * sigma));
+        const float norm = 1.0f + 2.0f * e;
+        const float w0 = 1.0f / norm, w1 = e / norm;
+        __syncthreads();
+        for (int px = tid; px < HW; px += AUG_THREADS) {
+            const int y = px / W, x = px - y * W;
+            const int xl = x == 0 ? 1 : x - 1, xr = x == W - 1 ? W - 2 : x + 1;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float* r = cur + c * HW + y * W;
+                oth[c * HW + px] = w1 * r[xl] + w0 * r[x] + w1 * r[xr];
+            }
+        }
+        __syncthreads();
+        for (int px = tid; px < HW; px += AUG_THREADS) {
+            const int y = px / W, x = px - y * W;
+            const int yu = y == 0 ? 1 : y - 1, yd = y == H - 1 ? H - 2 : y + 1;
+#pragma unroll
+            for (int c = 0; c < C; ++c) {
+                const float* pl = oth + c * HW;
+                cur[c * HW + px] = w1 * pl[yu * W + x] + w0 * pl[px] + w1 * pl[yd * W + x];
+            }
+        }
+    }
+    __syncthreads();
+
+    // 6. + 7. normalise, erase, store NCHW (the LDS image is the output's layout)
+    const int ei = (int)p[SPV_AUG_ERASE_I], ej = (int)p[SPV_AUG_ERASE_J];
+    const int eh = (int)p[SPV_AUG_ERASE_H], ew = (int)p[SPV_AUG_ERASE_W];
+    if (vec) {   // HW % 4 == 0 and out 16-byte aligned: a float4 lies inside one channel plane
+        for (int q = tid; q < CHW / 4; q += AUG_THREADS) {
+            const int e0 = 4 * q;
+            const int c = e0 / HW, px = e0 - c * HW;
+            const float mu = mean[c], is = inv_std[c];
+            const float4 v = *reinterpret_cast<const float4*>(cur + e0);
+            float r[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+            for (int u = 0; u < 4; ++u) {
+                const int y = (px + u) / W, x = (px + u) - y * W;
+                const bool erased = y >= ei && y < ei + eh && x >= ej && x < ej + ew;
+                r[u] = erased ? 0.0f : (r[u] - mu) * is;
+            }
+            *reinterpret_cast<float4*>(o + e0) = make_float4(r[0], r[1], r[2], r[3]);
+        }
+    } else {
+        for (int e = tid; e < CHW; e += AUG_THREADS) {
+            const int c = e / HW, px = e - c * HW;
+            const int y = px / W, x = px - y * W;
+            const bool erased = y >= ei && y < ei + eh && x >= ej && x < ej + ew;
+            o[e] = erased ? 0.0f : (cur[e] - mean[c]) * inv_std[c];
+        }
+    }
+}
+
+extern "C" int spv_augment_u8(const unsigned char* src_nhwc, const int64_t* index, const float* params, const float* mean,
+                              const float* inv_std, float* out_nchw, int batch, int n_src, int chans, int height, int width, void* stream) {
+    SPV_CHECK(batch > 0 && n_src > 0 && chans > 0 && height > 0 && width > 0, "spv_augment_u8: bad shape");
+    SPV_CHECK(spv_augment_supported(chans, height, width),
+              "spv_augment_u8: a %d x %d x %d image is not supported (1 or 3 channels, two fp32 copies of the image within %d bytes of LDS)",
+              chans, height, width, AUG_LDS_BYTES);
+    SPV_CHECK(src_nhwc != nullptr && out_nchw != nullptr, "spv_augment_u8: src / out missing");
+    SPV_CHECK(params != nullptr, "spv_augment_u8: params missing");
+    SPV_CHECK(mean != nullptr && inv_std != nullptr, "spv_augment_u8: mean / inv_std missing");
+    SPV_CHECK(index != nullptr || batch <= n_src, "spv_augment_u8: index == NULL reads rows 0..batch-1, but batch=%d > n_src=%d", batch, n_src);
+    SPV_CHECK(((uintptr_t)out_nchw & 3) == 0 && ((uintptr_t)params & 3) == 0, "spv_augment_u8: out / params must be 4-byte aligned");
+    const int vec = (height * width) % 4 == 0 && ((uintptr_t)out_nchw & 15) == 0;
+    const size_t lds = aug_lds_bytes(chans, height, width);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (chans == 3)
+        hipLaunchKernelGGL(augment_u8_kernel<3>, dim3(batch), dim3(AUG_THREADS), lds, st, src_nhwc, index, params, mean, inv_std, out_nchw,
+                           n_src, height, width, vec);
+    else
+        hipLaunchKernelGGL(augment_u8_kernel<1>, dim3(batch), dim3(AUG_THREADS), lds, st, src_nhwc, index, params, mean, inv_std, out_nchw,
+                           n_src, height, width, vec);
+    SPV_LAUNCH_CHECK("spv_augment_u8");
+    SPV_COUNT_PATH(SPV_PATH_AUGMENT);
+    return 0;
+}

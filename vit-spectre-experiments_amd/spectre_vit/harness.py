@@ -3,7 +3,8 @@
 Same loop structure (train.py:207-295 classification, :298-361 distillation): seeds, model from a parsed config,
 AdamW(betas, lr, weight_decay), autocast, per-epoch eval, accuracy bookkeeping on device, best-validation
 ``state_dict`` checkpoint.  What differs: synthetic CIFAR-shaped data resident on the GPU (no torchvision / network),
-bf16 autocast (no GradScaler needed), scalars to a JSON-lines file instead of TensorBoard, optional data parallelism
+bf16 autocast (no GradScaler needed), the training transform chain of train.py:100-115 as an on-GPU kernel pair (``--augment``,
+spectre_vit.augment) instead of PIL on loader workers, scalars to a JSON-lines file instead of TensorBoard, optional data parallelism
 (one process per GPU, RCCL all-reduce through spectre_vit.dp.GradReducer), and a synthetic frozen teacher for the
 distillation path (the DINOv3 weights are unavailable offline).
 
@@ -22,6 +23,7 @@ import torch
 import torch.distributed as dist
 from torch import nn, optim
 
+from spectre_vit.augment import TrainAugment
 from spectre_vit.configs.parser import parse_config
 from spectre_vit.distillation import SyntheticTeacher, distillation_loss
 from spectre_vit.dp import GradReducer, broadcast_module
@@ -40,6 +42,11 @@ def seed_everything(seed: int):
     torch.manual_seed(seed)
     if torch.cuda.is_available():
         torch.cuda.manual_seed_all(seed)
+
+
+def augment_seed(seed: int, rank: int = 0) -> int:
+    """the augmentation stream's 64-bit seed: the config seed in the low word, the rank in the high one (ranks draw different tables)"""
+    return (int(seed) & 0xFFFFFFFF) | ((int(rank) & 0xFFFFFFFF) << 32)
 
 
 def build_model(c, mixer="permut", device="cuda", model="spectre"):
@@ -69,16 +76,20 @@ class SyntheticCifar:
         self.mean = torch.tensor(CIFAR_MEAN[:c.in_channels], device=device).view(1, -1, 1, 1)
         self.std = torch.tensor(CIFAR_STD[:c.in_channels], device=device).view(1, -1, 1, 1)
 
-    def batches(self, batch_size, shuffle, generator=None, rank=0, world=1, raw_uint8=False, drop_last=True):
-        """raw_uint8: yield the uint8 NHWC batch itself; the model's patch gather normalises it (SURVEY 8f-3).
-        drop_last=False (validation): the short tail batch is yielded too, so every sample of the rank's shard is seen
-        (the reference's DataLoader default, train.py:151-155)."""
+    def index_batches(self, batch_size, shuffle, generator=None, rank=0, world=1, drop_last=True):
+        """the row indices (int64, on the set's device) of every batch of one pass, in the order `batches` draws them"""
         n = self.images.shape[0]
         idx = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
         idx = idx[rank::world].to(self.images.device)
         stop = idx.numel() - batch_size + 1 if drop_last else idx.numel()
         for i in range(0, stop, batch_size):
-            sel = idx[i:i + batch_size]
+            yield idx[i:i + batch_size]
+
+    def batches(self, batch_size, shuffle, generator=None, rank=0, world=1, raw_uint8=False, drop_last=True):
+        """raw_uint8: yield the uint8 NHWC batch itself; the model's patch gather normalises it (SURVEY 8f-3).
+        drop_last=False (validation): the short tail batch is yielded too, so every sample of the rank's shard is seen
+        (the reference's DataLoader default, train.py:151-155)."""
+        for sel in self.index_batches(batch_size, shuffle, generator, rank, world, drop_last):
             if raw_uint8:
                 yield self.images[sel].permute(0, 2, 3, 1).contiguous(), self.labels[sel]
                 continue
@@ -87,11 +98,19 @@ class SyntheticCifar:
 
 
 def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
-          use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre"):
+          use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
+          augment=False, batch_hook=None):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
-    The default is the reference's own loop shape (train.py:216-238) with the overlapped bucket exchange under data parallelism."""
+    The default is the reference's own loop shape (train.py:216-238) with the overlapped bucket exchange under data parallelism.
+    augment=True: every training batch goes through the reference's transform chain (train.py:100-115) on the GPU -- the training set
+    kept once as uint8 NHWC, the shuffled batch index, the global step and augment_seed(config seed, rank) handed to
+    spectre_vit.augment.TrainAugment; validation batches stay ToTensor + Normalize (eval_transform_spectre).  With graph=True its two
+    launches run on the step's stream in front of the replay.  Not with uint8_input (the chain's output is float) or distill.
+    batch_hook(kind, step, img, label), kind "train" / "val": called with every batch as the model is about to see it (test seam)."""
+    if augment and (uint8_input or distill):
+        raise ValueError("augment=True yields normalised float batches for the plain training step: not with uint8_input or distill")
     c = parse_config(config_path)
     seed = getattr(c, "random_seed", 42)
     lr = getattr(c, "learning_rate", 1e-3)
@@ -129,13 +148,29 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     log_f = open(os.path.join(out_dir, "scalars.jsonl"), "a") if rank == 0 else None
     gen = torch.Generator().manual_seed(seed)
     best_acc, history = 0.0, []
+    global_step = 0
+    aug = train_nhwc = None
+    if augment:
+        aug = TrainAugment(CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels], seed=augment_seed(seed, rank))
+        train_nhwc = train_set.images.permute(0, 2, 3, 1).contiguous()
+
+    def train_batches():
+        if aug is None:
+            yield from train_set.batches(batch_size, True, gen, rank, world, raw_uint8=uint8_input and not distill)
+            return
+        for sel in train_set.index_batches(batch_size, True, gen, rank, world):
+            yield aug(train_nhwc, sel, step=global_step), train_set.labels[sel]
+
     start = time.perf_counter()
     for epoch in range(epochs):
         model.train()
         running = torch.zeros((), device=device)
         correct = torch.zeros((), device=device, dtype=torch.int64)
         total, steps = 0, 0
-        for img, label in train_set.batches(batch_size, True, gen, rank, world, raw_uint8=uint8_input and not distill):
+        for img, label in train_batches():
+            if batch_hook is not None:
+                batch_hook("train", global_step, img, label)
+            global_step += 1
             if graph:
                 if gstep is None:   # built on the first batch (its shape is the captured one); warm-up steps are real training steps
                     from spectre_vit.graph import GraphedDPStep, GraphedTrainStep
@@ -183,6 +218,8 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         with torch.no_grad():
             for img, label in val_set.batches(min(getattr(c, "val_batch_size", batch_size), n_val), False, None, rank, world,
                                               raw_uint8=uint8_input and not distill, drop_last=False):
+                if batch_hook is not None:
+                    batch_hook("val", v_steps, img, label)
                 with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp and not distill):
                     y_pred = model(img)
                 v_correct += (label == torch.argmax(y_pred, dim=1)).sum()
@@ -223,10 +260,12 @@ def main():
     ap.add_argument("--batch-size", type=int, default=None)
     ap.add_argument("--distill", action="store_true")
     ap.add_argument("--graph", action="store_true", help="replay the training step from HIP graphs (spectre_vit.graph)")
+    ap.add_argument("--augment", action="store_true",
+                    help="the reference's training transform chain (train.py:100-115) on the GPU (spectre_vit.augment)")
     ap.add_argument("--out", default="runs/spectre_vit")
     a = ap.parse_args()
     train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph,
-          model=a.model)
+          model=a.model, augment=a.augment)
 
 
 if __name__ == "__main__":
