@@ -57,6 +57,7 @@ enum {
     SPV_PATH_ATTN_ROW0_FWD = 20, /* spv_attention_row0_fwd (the attention mixer's CLS-only last layer) */
     SPV_PATH_ATTN_ROW0_BWD = 21, /* spv_attention_row0_bwd */
     SPV_PATH_AUGMENT = 22,       /* spv_augment_u8 (the training transform chain, one workgroup per image) */
+    SPV_PATH_TEACHER_VIEW = 23,  /* spv_teacher_view_u8 (the distillation teacher's 224 view, one workgroup per image and row band) */
     SPV_PATH_COUNT = 24
 };
 long long spv_path_count(int which);
@@ -521,6 +522,40 @@ int spv_augment_supported(int chans, int height, int width);
  * reads nothing for such a row and writes NaN to its whole image. */
 int spv_augment_u8(const unsigned char* src_nhwc, const int64_t* index, const float* params, const float* mean, const float* inv_std,
                    float* out_nchw, int batch, int n_src, int chans, int height, int width, void* stream);
+
+/* ---- paired-view distillation: spectre_vit/repl/train.py:92-100, 139-141 (the teacher's view), 300-302, 334-348 (the loss) ------
+ * spv_teacher_view_u8: out[b] = Normalize(ToTensor(CenterCrop(crop)(Resize(resize, BICUBIC)(src[index[b]])))) from the resident uint8
+ * NHWC set of square n x n images (the layout spv_augment_u8 reads; index == NULL: rows 0..batch-1) to a dense NCHW batch
+ * [batch][chans][crop][crop] in `dtype`.  The resize is Pillow's 8-bit resampling (what torchvision's Resize does to a PIL image), bit
+ * for bit: per axis, output coordinate xx in [lo, lo + crop), lo = (resize - crop) / 2, has the four taps xmin .. xmin + 3 with integer
+ * coefficients k (22 fractional bits, each row summing to 2^22); a pass is clip8((2^21 + sum_d pixel[xmin + d] k[d]) >> 22); the
+ * horizontal pass runs first and is stored as uint8, the vertical pass over that.  Only the cropped rows and columns are computed.
+ *   table  int32 [5][crop_p], crop_p = crop rounded up to 8: row 0 = xmin, rows 1-4 = the taps, entry j for output coordinate lo + j,
+ *          zero past crop (the same table serves both axes); built on the host in float64 (spectre_vit.distillation.teacher_view_table);
+ *   lut    fp32 [chans][256]: lut[c][v] = (v / 255 - mean[c]) / std[c] in correctly rounded fp32 operations, i.e. ToTensor + Normalize of
+ *          the 8-bit value v (built by the host); bf16 output is that value rounded to nearest even.
+ * spv_teacher_view_supported: chans 1 or 3, 2 <= n <= resize (no down-scaling: Pillow widens the support there), 0 < crop <= resize,
+ * all four taps of every cropped output inside the image, and the staging of a band of 32 output rows -- table, lut, the source rows
+ * the band needs, their horizontal pass -- within the 64 KiB of LDS a workgroup may take (3 x 32 x 32 and 1 x 28 x 28 to 256 / 224 fit,
+ * as does 3 x 256 x 256).  Everything else is refused on the host.  An index outside [0, n_src) cannot be seen by the host: the kernel
+ * reads nothing for such a row and writes NaN to its whole image.  Table values that become addresses are clamped in the kernel. */
+int spv_teacher_view_supported(int chans, int n, int resize, int crop);
+int spv_teacher_view_u8(const unsigned char* src_nhwc, const int64_t* index, const int* table, const float* lut, void* out_nchw, int batch,
+                        int n_src, int chans, int n, int resize, int crop, int dtype, void* stream);
+/* The distillation loss, one launch each way:
+ *   out3[0] = w_soft * out3[1] + w_ce * out3[2],   out3[1] = T^2 / rows * sum_r sum_c p_t (log p_t - log p_s),   out3[2] = mean_r CE(z_r, y_r)
+ * with p_t = softmax(teacher / T), log p_s = log_softmax(student / T); fp32 logits [rows][classes], int64 labels.  lse3 [3][rows]
+ * receives the log-sum-exps of z, z / T and t / T (the backward's input).  log p_t is t / T - lse, so a teacher probability that
+ * underflows contributes its limit 0 (log(softmax) gives 0 * -inf = NaN there: the one deviation from the reference's formula).
+ * Rows are joined in a fixed order (spv_cross_entropy_fwd's scheme): `workspace` holds spv_distill_loss_workspace_floats() floats,
+ * zeroed once by the caller; two calls give the same bits.  A label outside [0, classes) makes out3[0] and out3[2] NaN and reads
+ * nothing out of bounds.
+ *   dlogits = grad_out[0] / rows * (w_soft T (softmax(z / T) - p_t) + w_ce (softmax(z) - onehot(y))) */
+int64_t spv_distill_loss_workspace_floats(void);
+int spv_distill_loss_fwd(const float* student, const float* teacher, const int64_t* labels, float* lse3, float* out3, float* workspace,
+                         int rows, int classes, float T, float w_soft, float w_ce, void* stream);
+int spv_distill_loss_bwd(const float* student, const float* teacher, const int64_t* labels, const float* lse3, const float* grad_out,
+                         float* dlogits, int rows, int classes, float T, float w_soft, float w_ce, void* stream);
 
 #ifdef __cplusplus
 }

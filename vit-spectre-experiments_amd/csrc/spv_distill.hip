@@ -1,0 +1,365 @@
+// Paired-view distillation on the device (reference spectre_vit/repl/train.py:92-100, 139-141, 298-361): the teacher's view of a
+// sample -- Resize(resize, BICUBIC) -> CenterCrop(crop) -> ToTensor -> Normalize of the raw 8-bit image, Pillow's integer resampling
+// bit for bit -- and the soft-target + cross-entropy loss as one kernel each way.  Definitions: include/spv.h and DESIGN.md section 4d.
+#include "spv_common.h"
+#include <algorithm>
+#include <math.h>
+
+namespace {
+
+// ================================================================ teacher view
+constexpr int TV_THREADS = 256;
+constexpr int TV_BAND = 32;                // output rows per workgroup: 7 bands at crop 224
+constexpr int TV_TAPS = 4;                 // bicubic support 2 without widening (n <= resize)
+constexpr int TV_PREC = 22;                // Pillow's PRECISION_BITS for 8-bit images: 32 - 8 - 2
+constexpr int TV_LDS_BYTES = 64 * 1024;    // what a workgroup may take without an opt-in attribute
+constexpr int TV_MAX_SIDE = 4096;
+
+struct TvPlan {
+    int ok, crop_p, max_rows;
+    size_t src_bytes, lds;
+};
+
+// Pillow's window of output coordinate xx (precompute_coeffs): [xmin, xmax) in source pixels
+static inline void tv_window(int xx, int n, int resize, int* xmin, int* xmax) {
+    const double scale = (double)n / (double)resize;
+    const double center = ((double)xx + 0.5) * scale;
+    int lo = (int)(center - 2.0 + 0.5), hi = (int)(center + 2.0 + 0.5);
+    *xmin = lo < 0 ? 0 : lo;
+    *xmax = hi > n ? n : hi;
+}
+
+// The staging plan of one (chans, n, resize, crop): every cropped output must have its four taps inside the image; a band of TV_BAND
+// output rows needs the source rows [ymin(first), ymin(last) + 4), at most max_rows of them.  LDS: the coefficient table
+// [5][crop_p] int32, the normalisation table [chans][256] fp32, max_rows source rows as they lie (NHWC bytes), and the horizontal
+// pass's result [chans][max_rows][crop_p] uint8.
+static TvPlan tv_plan(int chans, int n, int resize, int crop) {
+    TvPlan p = {0, 0, 0, 0, 0};
+    if (!(chans == 1 || chans == 3) || n < 2 || n > resize || crop <= 0 || crop > resize || resize > TV_MAX_SIDE) return p;
+    const int lo = (resize - crop) / 2;
+    int max_rows = TV_TAPS;
+    for (int y0 = 0; y0 < crop; y0 += TV_BAND) {
+        const int y1 = std::min(y0 + TV_BAND, crop);
+        int first = 0;
+        for (int y = y0; y < y1; ++y) {
+            int xmin, xmax;
+            tv_window(lo + y, n, resize, &xmin, &xmax);
+            if (xmax - xmin != TV_TAPS) return p;
+            if (y == y0) first = xmin;
+            max_rows = std::max(max_rows, xmin + TV_TAPS - first);
+        }
+    }
+    p.crop_p = (crop + 7) / 8 * 8;
+    p.max_rows = max_rows;
+    p.src_bytes = ((size_t)max_rows * n * chans + 15) / 16 * 16;
+    p.lds = (size_t)5 * p.crop_p * sizeof(int) + (size_t)chans * 256 * sizeof(float) + p.src_bytes + (size_t)chans * max_rows * p.crop_p;
+    p.ok = p.lds <= (size_t)TV_LDS_BYTES ? 1 : 0;
+    return p;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+__device__ __forceinline__ int tv_clip8(int acc) { return clampi(acc >> TV_PREC, 0, 255); }
+
+template <typename T, int COLS> struct tv_store;
+template <typename T> struct tv_store<T, 1> {
+    static __device__ __forceinline__ void st(T* p, const float (&v)[1]) { io<T>::st(p, v[0]); }
+};
+template <> struct tv_store<float, 4> {
+    static __device__ __forceinline__ void st(float* p, const float (&v)[4]) { io<float>::st4(p, v); }
+};
+template <> struct tv_store<bf16_t, 8> {
+    static __device__ __forceinline__ void st(bf16_t* p, const float (&v)[8]) {
+        uint4 t;
+        t.x = pack_bf16x2(v[0], v[1]);
+        t.y = pack_bf16x2(v[2], v[3]);
+        t.z = pack_bf16x2(v[4], v[5]);
+        t.w = pack_bf16x2(v[6], v[7]);
+        *reinterpret_cast<uint4*>(p) = t;
+    }
+};
+
+// Workgroup (b, band): output rows [band * TV_BAND, ...) of image b, every channel.  The source rows the band needs are staged as
+// they lie; the horizontal pass writes them resampled to `crop` columns as uint8 (Pillow stores that pass as 8 bits), planar, four
+// columns per thread as one dword; the vertical pass gives each lane COLS consecutive columns of one output row, lanes running along
+// the row and on into the next one, so a wave's stores are 16 bytes per lane to consecutive addresses.  Every table value that becomes
+// an address is clamped: a wrong table gives wrong pixels, never a read outside the staged rows.
+template <typename T, int COLS>
+__global__ __launch_bounds__(TV_THREADS) void teacher_view_kernel(const unsigned char* __restrict__ src, const int64_t* __restrict__ index,
+                                                                  const int* __restrict__ table, const float* __restrict__ lut,
+                                                                  T* __restrict__ out, int n_src, int C, int n, int crop, int crop_p,
+                                                                  int max_rows, int src_bytes) {
+    extern __shared__ __align__(16) unsigned char tv_lds[];
+    int* tab = reinterpret_cast<int*>(tv_lds);
+    float* nl = reinterpret_cast<float*>(tab + 5 * crop_p);
+    unsigned char* simg = reinterpret_cast<unsigned char*>(nl + C * 256);
+    unsigned char* hb = simg + src_bytes;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int y0 = blockIdx.y * TV_BAND, y1 = min(y0 + TV_BAND, crop), ny = y1 - y0;
+    T* o = out + (size_t)b * C * crop * crop;
+    const int64_t row = index != nullptr ? index[b] : (int64_t)b;
+    if (row < 0 || row >= (int64_t)n_src) {   // workgroup uniform: nothing is read, the band is poisoned
+        for (int c = 0; c < C; ++c)
+            for (int e = tid; e < ny * crop; e += TV_THREADS) io<T>::st(o + ((size_t)c * crop + y0) * crop + e, __builtin_nanf(""));
+        return;
+    }
+    for (int i = tid; i < 5 * crop_p; i += TV_THREADS) tab[i] = table[i];
+    for (int i = tid; i < C * 256; i += TV_THREADS) nl[i] = lut[i];
+    const int r0 = clampi(table[y0], 0, n - TV_TAPS);
+    const int r1 = clampi(table[y1 - 1], 0, n - TV_TAPS) + TV_TAPS;
+    const int nr = min(max(r1 - r0, TV_TAPS), max_rows);
+    {
+        const unsigned char* g = src + (size_t)row * n * n * C + (size_t)r0 * n * C;
+        const int bytes = nr * n * C;
+        if (((uintptr_t)g & 3) == 0) {
+            const int words = bytes >> 2;
+            for (int i = tid; i < words; i += TV_THREADS) reinterpret_cast<unsigned*>(simg)[i] = reinterpret_cast<const unsigned*>(g)[i];
+            for (int i = (words << 2) + tid; i < bytes; i += TV_THREADS) simg[i] = g[i];
+        } else {
+            for (int i = tid; i < bytes; i += TV_THREADS) simg[i] = g[i];
+        }
+    }
+    __syncthreads();
+
+    // horizontal pass over the staged rows
+    const int q4 = crop_p >> 2;
+    for (int it = tid; it < nr * C * q4; it += TV_THREADS) {
+        const int q = it % q4, rc = it / q4;
+        const int c = rc % C, r = rc / C;
+        const int4 xm = *reinterpret_cast<const int4*>(tab + 4 * q);
+        const int4 k0 = *reinterpret_cast<const int4*>(tab + crop_p + 4 * q);
+        const int4 k1 = *reinterpret_cast<const int4*>(tab + 2 * crop_p + 4 * q);
+        const int4 k2 = *reinterpret_cast<const int4*>(tab + 3 * crop_p + 4 * q);
+        const int4 k3 = *reinterpret_cast<const int4*>(tab + 4 * crop_p + 4 * q);
+        const int xs[4] = {xm.x, xm.y, xm.z, xm.w};
+        const int w0[4] = {k0.x, k0.y, k0.z, k0.w}, w1[4] = {k1.x, k1.y, k1.z, k1.w};
+        const int w2[4] = {k2.x, k2.y, k2.z, k2.w}, w3[4] = {k3.x, k3.y, k3.z, k3.w};
+        const unsigned char* sr = simg + (size_t)r * n * C + c;
+        unsigned packed = 0;
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            const unsigned char* s = sr + clampi(xs[u], 0, n - TV_TAPS) * C;
+            const int acc = (1 << (TV_PREC - 1)) + (int)s[0] * w0[u] + (int)s[C] * w1[u] + (int)s[2 * C] * w2[u] + (int)s[3 * C] * w3[u];
+            int v = tv_clip8(acc);
+            // Kept opaque on purpose.  Left to itself the compiler fuses shift + clamp of two neighbours into one v_ashr_pk_u8_i32 and
+            // ORs bytes 2 and 3 into that result's upper half; on the MI355X those two bytes then came out wrong (columns 2 and 3 of
+            // every group of four, measured), as if the instruction left bits 31:16 of its destination as they were.
+            asm volatile("" : "+v"(v));
+            packed |= (unsigned)v << (8 * u);
+        }
+        *reinterpret_cast<unsigned*>(hb + ((size_t)c * max_rows + r) * crop_p + 4 * q) = packed;
+    }
+    __syncthreads();
+
+    // vertical pass, normalisation table, store
+    const int qn = crop / COLS;   // COLS > 1 only when it divides crop
+    for (int it = tid; it < C * ny * qn; it += TV_THREADS) {
+        const int q = it % qn, yc = it / qn;
+        const int y = y0 + yc % ny, c = yc / ny;
+        const int rr = clampi(clampi(tab[y], 0, n - TV_TAPS) - r0, 0, nr - TV_TAPS);
+        const int k0 = tab[crop_p + y], k1 = tab[2 * crop_p + y], k2 = tab[3 * crop_p + y], k3 = tab[4 * crop_p + y];
+        const unsigned char* h = hb + ((size_t)c * max_rows + rr) * crop_p + COLS * q;
+        unsigned char t0[COLS], t1[COLS], t2[COLS], t3[COLS];
+        __builtin_memcpy(t0, h, COLS);   // COLS-byte aligned: crop_p is a multiple of 8
+        __builtin_memcpy(t1, h + crop_p, COLS);
+        __builtin_memcpy(t2, h + 2 * crop_p, COLS);
+        __builtin_memcpy(t3, h + 3 * crop_p, COLS);
+        const float* nlc = nl + c * 256;
+        float v[COLS];
+#pragma unroll
+        for (int u = 0; u < COLS; ++u) {
+            const int acc = (1 << (TV_PREC - 1)) + (int)t0[u] * k0 + (int)t1[u] * k1 + (int)t2[u] * k2 + (int)t3[u] * k3;
+            v[u] = nlc[tv_clip8(acc)];
+        }
+        tv_store<T, COLS>::st(o + ((size_t)c * crop + y) * crop + COLS * q, v);
+    }
+}
+
+// ================================================================ distillation loss
+constexpr int DL_THREADS = 256;
+constexpr int DL_WAVES = DL_THREADS / 64;
+constexpr int DL_MAX_WG = 64;
+
+// Wave per row, two passes over the row (the second one is served by the cache: a row is 4 * classes bytes).  With q = softmax(z / T),
+// p = softmax(t / T) the row's soft term is  sum p (log p - log q).  In general it is taken with every logit shifted by its row's
+// maximum:  sum p u - (log s_t - log s_z),  u = ((t - max t) - (z - max z)) / T,  s = the shifted exponential sums -- no term is larger
+// than the quantities a log-softmax handles, however far apart the two rows' levels are.  When the two distributions are close (the
+// state distillation drives towards) that is a cancellation of two log-sum-exps; with d = (t - z) / T the same term is
+// sum p d - log1p(sum q expm1(d)),  exact to fp32 RELATIVE precision for small d: taken when max |d| < 1/2.
+// A teacher probability that underflows contributes 0 (the limit), where log(softmax) gives 0 * -inf.
+// Rows are joined as in ce_fwd_kernel: per-workgroup partial sums, the last workgroup to arrive adds them in a fixed order and re-arms
+// the counter.
+__global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
+                                                                 const int64_t* __restrict__ labels, float* __restrict__ lse3,
+                                                                 float* __restrict__ out3, float* __restrict__ partial,
+                                                                 unsigned* __restrict__ counter, int rows, int C, float T, float w_soft,
+                                                                 float w_ce) {
+    __shared__ float ws[2][DL_WAVES];
+    __shared__ bool last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const float invT = 1.0f / T;
+    float acc_soft = 0.0f, acc_ce = 0.0f;
+    for (int r = blockIdx.x * DL_WAVES + wave; r < rows; r += gridDim.x * DL_WAVES) {
+        const float* zr = z + (size_t)r * C;
+        const float* tr = t + (size_t)r * C;
+        float mz = -INFINITY, mt = -INFINITY, dmax = 0.0f;
+        for (int c = lane; c < C; c += 64) {
+            const float a = zr[c], b = tr[c];
+            mz = fmaxf(mz, a);
+            mt = fmaxf(mt, b);
+            dmax = fmaxf(dmax, fabsf((b - a) * invT));
+        }
+        mz = wave_max(mz);
+        mt = wave_max(mt);
+        dmax = wave_max(dmax);
+        const bool nearby = dmax < 0.5f;   // wave uniform
+        float s1 = 0.0f, s2 = 0.0f, s3 = 0.0f, pu = 0.0f, qe = 0.0f;
+        for (int c = lane; c < C; c += 64) {
+            const float a = zr[c], b = tr[c];
+            const float az = (a - mz) * invT, bt = (b - mt) * invT;
+            const float ez = expf(az), et = expf(bt);
+            const float d = (b - a) * invT;
+            s1 += expf(a - mz);
+            s2 += ez;
+            s3 += et;
+            pu += et * (nearby ? d : bt - az);
+            qe += ez * expm1f(nearby ? d : 0.0f);
+        }
+        s1 = wave_sum(s1);
+        s2 = wave_sum(s2);
+        s3 = wave_sum(s3);
+        pu = wave_sum(pu);
+        qe = wave_sum(qe);
+        const float lz = mz + logf(s1), lzt = mz * invT + logf(s2), ltt = mt * invT + logf(s3);
+        const float gap = nearby ? log1pf(qe / s2) : logf(s3) - logf(s2);
+        const int64_t y = labels[r];
+        if (lane == 0) {
+            lse3[r] = lz;
+            lse3[rows + r] = lzt;
+            lse3[2 * rows + r] = ltt;
+            acc_soft += pu / s3 - gap;
+            acc_ce += (y >= 0 && y < C) ? lz - zr[y] : __builtin_nanf("");   // a label outside [0, C) poisons the loss instead of reading wild
+        }
+    }
+    if (lane == 0) {
+        ws[0][wave] = acc_soft;
+        ws[1][wave] = acc_ce;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        float a = 0.0f, b = 0.0f;
+        for (int w = 0; w < DL_WAVES; ++w) {
+            a += ws[0][w];
+            b += ws[1][w];
+        }
+        partial[blockIdx.x] = a;
+        partial[DL_MAX_WG + blockIdx.x] = b;
+        __threadfence();
+        last = atomicAdd(counter, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (last) {
+        __threadfence();
+        if (wave == 0) {   // one partial pair per lane (gridDim.x <= 64), joined by the same tree every time
+            const bool in = lane < (int)gridDim.x;
+            const float a = wave_sum(in ? __builtin_nontemporal_load(partial + lane) : 0.0f);
+            const float b = wave_sum(in ? __builtin_nontemporal_load(partial + DL_MAX_WG + lane) : 0.0f);
+            if (lane == 0) {
+                const float soft = a * (T * T) / (float)rows, ce = b / (float)rows;
+                out3[0] = w_soft * soft + w_ce * ce;
+                out3[1] = soft;
+                out3[2] = ce;
+                *counter = 0u;
+            }
+        }
+    }
+}
+
+// dz = go / rows * (w_soft T (softmax(z / T) - softmax(t / T)) + w_ce (softmax(z) - onehot))
+__global__ __launch_bounds__(DL_THREADS) void distill_bwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
+                                                                 const int64_t* __restrict__ labels, const float* __restrict__ lse3,
+                                                                 const float* __restrict__ go, float* __restrict__ dz, int rows, int C,
+                                                                 float T, float w_soft, float w_ce) {
+    const float scale = go[0] / (float)rows, invT = 1.0f / T;
+    const float ks = w_soft * T;
+    const int64_t total = (int64_t)rows * C;
+    for (int64_t e = (int64_t)blockIdx.x * DL_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * DL_THREADS) {
+        const int r = (int)(e / C), c = (int)(e - (int64_t)r * C);
+        const float a = z[e];
+        const float q = expf(a * invT - lse3[rows + r]), p = expf(t[e] * invT - lse3[2 * rows + r]);
+        const float s = expf(a - lse3[r]);
+        dz[e] = (ks * (q - p) + w_ce * (s - (labels[r] == c ? 1.0f : 0.0f))) * scale;
+    }
+}
+
+}  // namespace
+
+extern "C" int spv_teacher_view_supported(int chans, int n, int resize, int crop) { return tv_plan(chans, n, resize, crop).ok; }
+
+extern "C" int spv_teacher_view_u8(const unsigned char* src_nhwc, const int64_t* index, const int* table, const float* lut, void* out_nchw,
+                                   int batch, int n_src, int chans, int n, int resize, int crop, int dtype, void* stream) {
+    SPV_CHECK(batch > 0 && n_src > 0, "spv_teacher_view_u8: bad shape batch=%d n_src=%d", batch, n_src);
+    const TvPlan p = tv_plan(chans, n, resize, crop);
+    SPV_CHECK(p.ok,
+              "spv_teacher_view_u8: %d x %d x %d -> resize %d, crop %d is not supported (1 or 3 channels, 2 <= n <= resize, 0 < crop <= "
+              "resize, four taps inside the image for every cropped output, staging within %d bytes of LDS)",
+              chans, n, n, resize, crop, TV_LDS_BYTES);
+    SPV_CHECK(dtype == SPV_F32 || dtype == SPV_BF16, "spv_teacher_view_u8: bad dtype %d", dtype);
+    SPV_CHECK(src_nhwc != nullptr && out_nchw != nullptr, "spv_teacher_view_u8: src / out missing");
+    SPV_CHECK(table != nullptr && lut != nullptr, "spv_teacher_view_u8: table / lut missing");
+    SPV_CHECK(index != nullptr || batch <= n_src, "spv_teacher_view_u8: index == NULL reads rows 0..batch-1, but batch=%d > n_src=%d", batch,
+              n_src);
+    SPV_CHECK(((uintptr_t)table & 3) == 0 && ((uintptr_t)lut & 3) == 0 && ((uintptr_t)out_nchw & 3) == 0,
+              "spv_teacher_view_u8: table / lut / out must be 4-byte aligned");
+    const int bands = cdiv(crop, TV_BAND);
+    SPV_CHECK(bands <= 65535, "spv_teacher_view_u8: crop=%d gives too many row bands", crop);
+    const bool aligned = ((uintptr_t)out_nchw & 15) == 0;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const dim3 grid(batch, bands), block(TV_THREADS);
+#define SPV_TV_LAUNCH(TY, COLS)                                                                                                       \
+    hipLaunchKernelGGL((teacher_view_kernel<TY, COLS>), grid, block, p.lds, st, src_nhwc, index, table, lut, static_cast<TY*>(out_nchw), \
+                       n_src, chans, n, crop, p.crop_p, p.max_rows, (int)p.src_bytes)
+    if (dtype == SPV_BF16) {
+        if (aligned && crop % 8 == 0) SPV_TV_LAUNCH(bf16_t, 8);
+        else SPV_TV_LAUNCH(bf16_t, 1);
+    } else {
+        if (aligned && crop % 4 == 0) SPV_TV_LAUNCH(float, 4);
+        else SPV_TV_LAUNCH(float, 1);
+    }
+#undef SPV_TV_LAUNCH
+    SPV_LAUNCH_CHECK("spv_teacher_view_u8");
+    SPV_COUNT_PATH(SPV_PATH_TEACHER_VIEW);
+    return 0;
+}
+
+extern "C" int64_t spv_distill_loss_workspace_floats() { return 2 * DL_MAX_WG + 1; }   // two partial sums per workgroup + the arrival counter
+
+static int distill_check(const char* name, const void* a, const void* b, const void* c, const void* d, const void* e, const void* f, int rows,
+                         int classes, float T, float w_soft, float w_ce) {
+    SPV_CHECK(rows > 0 && classes > 0, "%s: empty (rows=%d classes=%d)", name, rows, classes);
+    SPV_CHECK(T > 0.0f && std::isfinite(T), "%s: temperature T=%g must be positive and finite", name, (double)T);
+    SPV_CHECK(std::isfinite(w_soft) && std::isfinite(w_ce), "%s: a loss weight is not finite", name);
+    SPV_CHECK(a != nullptr && b != nullptr && c != nullptr, "%s: student / teacher / labels missing", name);
+    SPV_CHECK(d != nullptr && e != nullptr && f != nullptr, "%s: an output or workspace pointer is missing", name);
+    return 0;
+}
+
+extern "C" int spv_distill_loss_fwd(const float* student, const float* teacher, const int64_t* labels, float* lse3, float* out3,
+                                    float* workspace, int rows, int classes, float T, float w_soft, float w_ce, void* stream) {
+    if (int rc = distill_check("spv_distill_loss_fwd", student, teacher, labels, lse3, out3, workspace, rows, classes, T, w_soft, w_ce)) return rc;
+    const int wgs = std::min(cdiv(rows, DL_WAVES), DL_MAX_WG);
+    hipLaunchKernelGGL(distill_fwd_kernel, dim3(wgs), dim3(DL_THREADS), 0, static_cast<hipStream_t>(stream), student, teacher, labels, lse3,
+                       out3, workspace, reinterpret_cast<unsigned*>(workspace + 2 * DL_MAX_WG), rows, classes, T, w_soft, w_ce);
+    SPV_LAUNCH_CHECK("spv_distill_loss_fwd");
+    return 0;
+}
+
+extern "C" int spv_distill_loss_bwd(const float* student, const float* teacher, const int64_t* labels, const float* lse3,
+                                    const float* grad_out, float* dlogits, int rows, int classes, float T, float w_soft, float w_ce,
+                                    void* stream) {
+    if (int rc = distill_check("spv_distill_loss_bwd", student, teacher, labels, lse3, grad_out, dlogits, rows, classes, T, w_soft, w_ce)) return rc;
+    const int64_t total = (int64_t)rows * classes;
+    hipLaunchKernelGGL(distill_bwd_kernel, dim3((unsigned)std::min<int64_t>((total + DL_THREADS - 1) / DL_THREADS, 1024)), dim3(DL_THREADS), 0,
+                       static_cast<hipStream_t>(stream), student, teacher, labels, lse3, grad_out, dlogits, rows, classes, T, w_soft, w_ce);
+    SPV_LAUNCH_CHECK("spv_distill_loss_bwd");
+    return 0;
+}

@@ -21,7 +21,7 @@ c_vp, c_i, c_i64, c_u64, c_f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ct
 # indices of include/spv.h's SPV_PATH_* enum (dispatch census, test aid)
 PATH = dict(gemm_strip=0, gemm_strip_acc=1, gemm_tn=2, tail_lc=3, tail_up=4, tail_ln=5, fnet_mfma=6, gather_lds=7, gemm_tn_wide=9,
             gemm_tn_batch=10, gemm_strip_pool=11, permut_row0=12, gemm_rows=13,
-            spectrum=14, conv_fwd=15, conv_dgrad=16, conv_wgrad=17, token_pool=18, token_unpool=19, attn_row0_fwd=20, attn_row0_bwd=21, augment=22)
+            spectrum=14, conv_fwd=15, conv_dgrad=16, conv_wgrad=17, token_pool=18, token_unpool=19, attn_row0_fwd=20, attn_row0_bwd=21, augment=22, teacher_view=23)
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/spv.h one to one
 SIGNATURES = {
@@ -116,11 +116,16 @@ SIGNATURES = {
     "spv_augment_params": [c_vp, c_i, c_i, c_i, c_i, c_vp, c_u64, c_u64, c_vp],
     "spv_augment_supported": [c_i, c_i, c_i],
     "spv_augment_u8": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp],
+    "spv_teacher_view_supported": [c_i, c_i, c_i, c_i],
+    "spv_teacher_view_u8": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_i, c_vp],
+    "spv_distill_loss_workspace_floats": [],
+    "spv_distill_loss_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_f, c_f, c_f, c_vp],
+    "spv_distill_loss_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_f, c_f, c_f, c_vp],
 }
 _RESTYPES = {"spv_last_error": ctypes.c_char_p, "spv_path_count": ctypes.c_longlong, "spv_rowop_partial_floats": c_i64, "spv_fnet_workspace_floats": c_i64,
              "spv_fnet_twiddle_floats": c_i64, "spv_tail_ln_partial_floats": c_i64, "spv_permut_table_words": c_i64, "spv_small_sl_partial_floats": c_i64,
-             "spv_cross_entropy_workspace_floats": c_i64}
-_NO_STATUS = set(_RESTYPES) | {"spv_version", "spv_fnet_ln_supported", "spv_fnet_cls_supported", "spv_tail_ln_supported", "spv_tail_up_supported", "spv_small_sl_supported", "spv_tail_bwd_parts", "spv_embed_bwd_groups", "spv_haar_ln_supported", "spv_permut_pool_supported", "spv_spectrum_floats", "spv_augment_supported"}
+             "spv_cross_entropy_workspace_floats": c_i64, "spv_distill_loss_workspace_floats": c_i64}
+_NO_STATUS = set(_RESTYPES) | {"spv_version", "spv_fnet_ln_supported", "spv_fnet_cls_supported", "spv_tail_ln_supported", "spv_tail_up_supported", "spv_small_sl_supported", "spv_tail_bwd_parts", "spv_embed_bwd_groups", "spv_haar_ln_supported", "spv_permut_pool_supported", "spv_spectrum_floats", "spv_augment_supported", "spv_teacher_view_supported"}
 
 class FoldJob(ctypes.Structure):
     """spv_fold_job (include/spv.h): the fold of a tail backward's partial column sums, handed to spv_gemm_tn_fold"""

@@ -5,7 +5,15 @@ spectre_vit/repl/train.py:334-348.
 the real teacher weights are not available offline, so ``SyntheticTeacher`` provides the same output
 contract with fixed random projections for benchmarks and tests.  The teacher runs under ``no_grad`` in stock PyTorch --
 it is outside the accelerated path.
+
+The paired-view step (reference train.py:139-141, 298-361) on the HIP path (csrc/spv_distill.hip):
+``TeacherView`` is the teacher's transform -- Resize(256, BICUBIC) -> CenterCrop(224) -> ToTensor -> Normalize of the raw 8-bit
+sample (train.py:92-100), Pillow's integer resampling bit for bit -- read from the resident uint8 NHWC set through the batch's index;
+``DistillationLoss`` is the soft-target + cross-entropy loss as one launch each way (``hip_ops.distill_loss``).
 """
+import math
+
+import numpy as np
 import torch
 import torch.nn as nn
 
@@ -73,3 +81,143 @@ def distillation_loss(student_logits, teacher_logits, labels, T=2.0, soft_target
     else:
         ce = nn.functional.cross_entropy(student_logits, labels)
     return soft_target_loss_weight * soft + ce_loss_weight * ce, soft, ce
+
+
+# ---------------------------------------------------------------- the teacher's view (csrc/spv_distill.hip)
+PRECISION_BITS = 22   # Pillow's fixed point for 8-bit images: 32 - 8 - 2
+
+
+def _bicubic(x, a=-0.5):
+    x = abs(x)
+    if x < 1.0:
+        return ((a + 2.0) * x - (a + 3.0)) * x * x + 1
+    if x < 2.0:
+        return (((x - 5) * x + 8) * x - 4) * a
+    return 0.0
+
+
+def teacher_view_table(n, resize=256, crop=224):
+    """The coefficient table of Resize(resize, BICUBIC) -> CenterCrop(crop) along one axis of an n-pixel source, as Pillow builds it
+    for 8-bit images (float64 weights normalised to sum 1, then rounded half away from zero to 22 fractional bits).  Returns
+    (xmin int32 [crop], taps int32 [crop, 4]): cropped output j reads source pixels xmin[j] .. xmin[j] + 3.  Only up-scaling is
+    supported (n <= resize: Pillow widens the support otherwise), and every cropped output must keep its four taps inside the image."""
+    n, resize, crop = int(n), int(resize), int(crop)
+    if not (2 <= n <= resize and 0 < crop <= resize):
+        raise ValueError(f"teacher view: n={n}, resize={resize}, crop={crop} outside 2 <= n <= resize, 0 < crop <= resize")
+    lo = (resize - crop) // 2
+    scale = n / resize
+    xmin = np.zeros(crop, np.int32)
+    taps = np.zeros((crop, 4), np.int32)
+    for j in range(crop):
+        center = (lo + j + 0.5) * scale
+        x0 = max(int(center - 2.0 + 0.5), 0)
+        x1 = min(int(center + 2.0 + 0.5), n)
+        if x1 - x0 != 4:
+            raise ValueError(f"teacher view: output {lo + j} of an n={n} source at resize={resize} has {x1 - x0} taps inside the image; "
+                             "the kernel takes exactly 4")
+        w = [_bicubic(x + x0 - center + 0.5) for x in range(4)]
+        ww = 0.0
+        for v in w:
+            ww += v
+        w = [v / ww for v in w]
+        xmin[j] = x0
+        taps[j] = [int(v * (1 << PRECISION_BITS) - 0.5) if v < 0 else int(v * (1 << PRECISION_BITS) + 0.5) for v in w]
+    return xmin, taps
+
+
+_tables = {}   # (n, resize, crop, device) -> int32 [5][crop_p] on the device
+
+
+def _device_table(n, resize, crop, device):
+    key = (n, resize, crop, str(device))
+    if key not in _tables:
+        xmin, taps = teacher_view_table(n, resize, crop)
+        crop_p = (crop + 7) // 8 * 8
+        packed = np.zeros((5, crop_p), np.int32)
+        packed[0, :crop] = xmin
+        packed[1:, :crop] = taps.T
+        _tables[key] = torch.from_numpy(packed).to(device)
+    return _tables[key]
+
+
+def normalize_lut(mean, std):
+    """fp32 [C][256]: ToTensor + Normalize of every 8-bit value, by torch's own fp32 operations on the host, on a (C, 256, 1) "image"
+    with the statistics shaped (C, 1, 1) as torchvision shapes them: the table is built by the very expression it stands for, so
+    whatever torch's kernels do with a scalar-like operand (a one-channel std is one), the table does too"""
+    C = len(mean)
+    v = torch.arange(256, dtype=torch.uint8).view(1, 256, 1).expand(C, 256, 1).contiguous().float().div(255)
+    m = torch.tensor(mean, dtype=torch.float32).view(-1, 1, 1)
+    s = torch.tensor(std, dtype=torch.float32).view(-1, 1, 1)
+    return ((v - m) / s).reshape(C, 256).contiguous()
+
+
+class TeacherView:
+    """The teacher's transform of reference train.py:92-100 on the GPU, for square uint8 sources:
+
+        view = TeacherView(CIFAR_MEAN, CIFAR_STD)                     # resize=256, crop=224
+        img_teacher = view(train_u8_nhwc, index)                      # (B, C, 224, 224), float32 or bfloat16
+
+    No autograd: the teacher runs under no_grad."""
+
+    def __init__(self, mean, std, resize=256, crop=224, dtype=torch.float32):
+        self.mean = tuple(float(m) for m in mean)
+        self.std = tuple(float(s) for s in std)
+        if len(self.mean) != len(self.std) or len(self.mean) not in (1, 3):
+            raise ValueError(f"mean / std name {len(self.mean)} / {len(self.std)} channels; the teacher view kernel takes 1 or 3")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise TypeError(f"the teacher view is written as float32 or bfloat16, got {dtype}")
+        self.resize, self.crop, self.dtype = int(resize), int(crop), dtype
+        if not 0 < self.crop <= self.resize:
+            raise ValueError(f"teacher view: crop={crop} outside 0 < crop <= resize={resize}")
+        self._lut = {}   # device -> fp32 [C][256]
+
+    def lut(self, device):
+        key = str(device)
+        if key not in self._lut:
+            self._lut[key] = normalize_lut(self.mean, self.std).to(device)
+        return self._lut[key]
+
+    def __call__(self, images_u8_nhwc, index=None):
+        """images_u8_nhwc: the resident uint8 set (N, n, n, C); index: int64 (B,) rows of it (None: all of them)."""
+        from spectre_vit import _native
+        from spectre_vit.hip_ops import _DT, _p, _require_gpu, _stream
+        x = images_u8_nhwc
+        if x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous():
+            raise TypeError(f"the teacher view kernel takes a contiguous uint8 (N, H, W, C) set, got {x.dtype} {tuple(x.shape)}")
+        N, H, W, C = x.shape
+        if C != len(self.mean):
+            raise ValueError(f"{C}-channel images, but mean / std name {len(self.mean)} channels")
+        if index is not None:
+            if index.dtype != torch.int64 or index.dim() != 1 or not index.is_contiguous():
+                raise TypeError(f"index is a contiguous int64 vector, got {index.dtype} {tuple(index.shape)}")
+            batch = index.numel()
+        else:
+            batch = N
+        _require_gpu(x, index)
+        if H != W or not _native.call("spv_teacher_view_supported", C, H, self.resize, self.crop):
+            raise ValueError(f"a {C} x {H} x {W} source to resize {self.resize}, crop {self.crop} is outside the teacher view kernel "
+                             "(square, 1 or 3 channels, n <= resize, four taps inside the image, staging within 64 KiB of LDS)")
+        table = _device_table(H, self.resize, self.crop, x.device)
+        out = torch.empty((batch, C, self.crop, self.crop), dtype=self.dtype, device=x.device)
+        _native.call("spv_teacher_view_u8", _p(x), _p(index), _p(table), _p(self.lut(x.device)), _p(out), batch, N, C, H, self.resize,
+                     self.crop, _DT[self.dtype], _stream())
+        return out
+
+
+class DistillationLoss(nn.Module):
+    """The loss of reference train.py:300-302, 334-348 on the HIP path (GPU only, like spectre_vit.loss.CrossEntropyLoss): returns the
+    weighted loss; ``.soft`` and ``.ce`` hold the unweighted soft-target and cross-entropy terms of the last call (device scalars,
+    detached), the reference's "Batch Loss/Dist" and "Batch Loss/CE"."""
+
+    def __init__(self, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75):
+        super().__init__()
+        if not (T > 0 and math.isfinite(T)):
+            raise ValueError(f"temperature T={T} must be positive and finite")
+        self.T, self.soft_target_loss_weight, self.ce_loss_weight = float(T), float(soft_target_loss_weight), float(ce_loss_weight)
+        self.soft = self.ce = None
+
+    def forward(self, student_logits, teacher_logits, labels):
+        from . import hip_ops
+        loss, self.soft, self.ce = hip_ops.distill_loss(student_logits, teacher_logits, labels, self.T, self.soft_target_loss_weight,
+                                                        self.ce_loss_weight)
+        return loss

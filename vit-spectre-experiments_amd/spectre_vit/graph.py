@@ -200,3 +200,47 @@ class GraphedDPStep(GraphedTrainStep):
         self.graph.replay()
         self.reducer.allreduce_flat(force=self.force_collective)   # host-issued, on the current stream's order: RCCL over xGMI
         self.graph_opt.replay()
+
+
+class GraphedDistillStep(GraphedTrainStep):
+    """The distillation step of reference train.py:298-361 replayed from one graph: zero_grad, student forward, the fused loss
+    (``spectre_vit.distillation.DistillationLoss``) against a fixed-address ``teacher_logits`` buffer, backward, optimizer.  The teacher
+    is NOT captured -- a real backbone is arbitrary user code -- it runs eagerly under no_grad in front of the replay, on the step's
+    stream:
+
+        step = GraphedDistillStep(model, optimizer, DistillationLoss(), img, labels, teacher_logits, autocast_dtype=None)
+        loss = step(img, labels, teacher_logits)      # step.soft / step.ce / step.out: the other captured outputs
+
+    Single process only: a graph-replayed data-parallel distillation rank is not built."""
+
+    def __init__(self, model, optimizer, criterion, example_img, example_labels, example_teacher_logits, autocast_dtype=None, warmup=3,
+                 process_group=None):
+        import torch.distributed as dist
+        if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
+            raise RuntimeError("GraphedDistillStep is the single-process step: GraphedDPStep is not built for distillation "
+                               "(run the ranks of a torch.distributed job with the eager step)")
+        self.teacher_logits = example_teacher_logits.detach().clone()
+        super().__init__(model, optimizer, criterion, example_img, example_labels, autocast_dtype=autocast_dtype, warmup=warmup,
+                         process_group=process_group)
+
+    def _forward_backward(self):
+        _native.call("spv_seed_advance", self.seed_word.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        self.reducer.zero_grad()
+        with torch.autocast("cuda", dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None):
+            out = self.model(self.img)
+        loss = self.criterion(out, self.teacher_logits, self.labels)   # on the fp32 logits, outside autocast
+        loss.backward(self._one)
+        return loss, out
+
+    def _warm(self, warmup):
+        super()._warm(warmup)
+        self.warm_soft, self.warm_ce = self.criterion.soft, self.criterion.ce
+
+    def _build(self, warmup):
+        super()._build(warmup)
+        self.soft, self.ce = self.criterion.soft, self.criterion.ce
+
+    def __call__(self, img=None, labels=None, teacher_logits=None):
+        if teacher_logits is not None and not self._closed:
+            self.teacher_logits.copy_(teacher_logits, non_blocking=True)
+        return super().__call__(img, labels)

@@ -6,7 +6,9 @@ AdamW(betas, lr, weight_decay), autocast, per-epoch eval, accuracy bookkeeping o
 bf16 autocast (no GradScaler needed), the training transform chain of train.py:100-115 as an on-GPU kernel pair (``--augment``,
 spectre_vit.augment) instead of PIL on loader workers, scalars to a JSON-lines file instead of TensorBoard, optional data parallelism
 (one process per GPU, RCCL all-reduce through spectre_vit.dp.GradReducer), and a synthetic frozen teacher for the
-distillation path (the DINOv3 weights are unavailable offline).
+distillation path (the DINOv3 weights are unavailable offline).  ``train(distill=True)`` is the early form of that path (the teacher
+sees a 64 x 64 interpolation of the student's batch); ``train_distill`` / ``--distill-paired`` is the loop with the reference's two views
+per sample, the teacher's 224 view and the KD loss on HIP kernels, and the step replayed from a graph on request.
 
     python -m spectre_vit.harness --config spectre_vit/configs/spectre_vit_cifar100.py --epochs 2 --steps-per-epoch 20
 """
@@ -25,7 +27,7 @@ from torch import nn, optim
 
 from spectre_vit.augment import TrainAugment
 from spectre_vit.configs.parser import parse_config
-from spectre_vit.distillation import SyntheticTeacher, distillation_loss
+from spectre_vit.distillation import DistillationLoss, SyntheticTeacher, TeacherView, distillation_loss
 from spectre_vit.dp import GradReducer, broadcast_module
 from spectre_vit.loss import CrossEntropyLoss
 from spectre_vit.models.spectre.spectre import SpectreViT
@@ -249,6 +251,159 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     return model, history
 
 
+def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
+                  use_amp=False, graph=False, augment=True, teacher=None, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75,
+                  resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None):
+    """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
+    batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
+    (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
+    spectre_vit.distillation.TeacherView (Resize(resize, BICUBIC) -> CenterCrop(crop) -> ToTensor -> Normalize of the raw 8-bit image).
+    The teacher (None: SyntheticTeacher; any module with forward(x, return_features=True)) runs under no_grad; the student's step goes
+    through the fused DistillationLoss, eagerly with GradReducer (also as a rank of a torch.distributed job) or, graph=True, replayed
+    by spectre_vit.graph.GraphedDistillStep with FusedAdamW (single process).  use_amp=False as the reference's distillation cell
+    (train.py:299); True runs the student under bf16 autocast, the loss on its fp32 logits.  Validation: student only, CE only, every
+    sample (train.py:365-383).  The three per-batch losses the reference logs (train.py:355-359) are kept on the device and written
+    once per epoch as {"step", "Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE"} lines: no host synchronisation per step.
+    batch_hook(kind, step, img, label), kind "train" / "teacher" / "val" (test seam)."""
+    from spectre_vit import _native
+    c = parse_config(config_path)
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    if graph and world > 1:
+        raise ValueError("graph=True replays the single-process distillation step (GraphedDistillStep); a data-parallel rank runs it eagerly")
+    if not _native.call("spv_teacher_view_supported", int(c.in_channels), int(c.img_size), int(resize), int(crop)):
+        raise ValueError(f"the teacher view kernel does not take {c.in_channels} x {c.img_size} x {c.img_size} images at resize={resize}, "
+                         f"crop={crop} (1 or 3 channels, img_size <= resize, 0 < crop <= resize, four taps inside the image)")
+    if not (T > 0):
+        raise ValueError(f"temperature T={T} must be positive")
+    seed = getattr(c, "random_seed", 42)
+    lr = getattr(c, "learning_rate", 1e-3)
+    rank = int(os.environ.get("RANK", "0"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local_rank)
+    if world > 1 and not dist.is_initialized():
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("nccl")
+    device = torch.device("cuda", local_rank)
+    seed_everything(seed)
+    model = build_model(c, mixer, device)
+    broadcast_module(model)
+    batch_size = batch_size or c.batch_size
+    train_set = SyntheticCifar(n_train, c, device, seed=seed)
+    val_set = SyntheticCifar(n_val, c, device, seed=seed + 1)
+    train_nhwc = train_set.images.permute(0, 2, 3, 1).contiguous()
+    mean, std = CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels]
+    aug = TrainAugment(mean, std, seed=augment_seed(seed, rank)) if augment else None
+    view = TeacherView(mean, std, resize=resize, crop=crop)
+    if teacher is None:
+        teacher = SyntheticTeacher(c.num_classes, 384, c.in_channels).to(device)
+    teacher.eval()
+    criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight)
+    val_criterion = CrossEntropyLoss()
+    gstep = None
+    if graph:
+        from spectre_vit.optim import FusedAdamW
+        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
+                               static_grads=True)
+        reducer = None   # the graphed step owns its own (fixed-address) gradient buffer
+    else:
+        optimizer = optim.AdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay)  # train.py:307-309
+        reducer = GradReducer(model)
+    os.makedirs(out_dir, exist_ok=True)
+    log_f = open(os.path.join(out_dir, "scalars.jsonl"), "a") if rank == 0 else None
+    gen = torch.Generator().manual_seed(seed)
+    best_acc, history = 0.0, []
+    global_step = 0
+    per_pass = (n_train // world) // batch_size
+    epoch_steps = min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass
+    autocast_dtype = torch.bfloat16 if use_amp else None
+    start = time.perf_counter()
+    for epoch in range(epochs):
+        model.train()
+        correct = torch.zeros((), device=device, dtype=torch.int64)
+        batch_losses = torch.zeros((max(epoch_steps, 1), 3), device=device)   # (Train, Dist, CE) per step, read once per epoch
+        first_step = global_step
+        total, steps = 0, 0
+        for sel in train_set.index_batches(batch_size, True, gen, rank, world):
+            label = train_set.labels[sel]
+            if aug is not None:
+                img = aug(train_nhwc, sel, step=global_step)
+            else:
+                img = (train_set.images[sel].float() / 255.0 - train_set.mean) / train_set.std
+            img_teacher = view(train_nhwc, sel)
+            if batch_hook is not None:
+                batch_hook("train", global_step, img, label)
+                batch_hook("teacher", global_step, img_teacher, label)
+            global_step += 1
+            with torch.no_grad():   # train.py:326-327
+                teacher_logits, _ = teacher(img_teacher, return_features=True)
+            teacher_logits = teacher_logits.float()
+            if graph:
+                if gstep is None:   # built on the first batch; its warm-up step WAS this batch's training step
+                    from spectre_vit.graph import GraphedDistillStep
+                    gstep = GraphedDistillStep(model, optimizer, criterion, img, label.long(), teacher_logits, autocast_dtype=autocast_dtype,
+                                               warmup=1)
+                    loss, soft, ce, y_pred = gstep.warm_loss, gstep.warm_soft, gstep.warm_ce, gstep.warm_out
+                else:
+                    loss = gstep(img, label.long(), teacher_logits)
+                    soft, ce, y_pred = gstep.soft, gstep.ce, gstep.out
+            else:
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
+                    y_pred = model(img)
+                loss = criterion(y_pred.float(), teacher_logits, label.long())
+                soft, ce = criterion.soft, criterion.ce
+                reducer.zero_grad()
+                loss.backward()
+                reducer.finish()
+                optimizer.step()
+            torch.stack((loss.detach(), soft, ce), out=batch_losses[steps])
+            correct += (label == torch.argmax(y_pred, dim=1)).sum()
+            total += label.size(0)
+            steps += 1
+            if steps >= epoch_steps:
+                break
+        per_batch = batch_losses[:steps].tolist()   # the epoch's one read of the per-batch scalars
+        train_loss = sum(r[0] for r in per_batch) / max(steps, 1)
+        train_acc = correct.item() / max(total, 1)
+
+        model.eval()
+        v_correct = torch.zeros((), device=device, dtype=torch.int64)
+        v_loss = torch.zeros((), device=device)
+        v_total, v_steps = 0, 0
+        with torch.no_grad():
+            for img, label in val_set.batches(min(getattr(c, "val_batch_size", batch_size), n_val), False, None, rank, world, drop_last=False):
+                if batch_hook is not None:
+                    batch_hook("val", v_steps, img, label)
+                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
+                    y_pred = model(img)
+                v_correct += (label == torch.argmax(y_pred, dim=1)).sum()
+                v_loss += val_criterion(y_pred.float(), label.long()) * label.size(0)
+                v_total += label.size(0)
+                v_steps += 1
+        stats = torch.stack([v_correct.float(), torch.tensor(float(v_total), device=device), v_loss])
+        if world > 1:
+            dist.all_reduce(stats)
+        val_acc = (stats[0] / stats[1].clamp(min=1)).item()
+        val_loss = (stats[2] / stats[1].clamp(min=1)).item()
+        rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
+               "Accuracy/Validation": val_acc, "steps": steps, "val_samples": int(stats[1].item())}
+        history.append(rec)
+        if rank == 0:
+            for k, (lt, ld, lc) in enumerate(per_batch):
+                log_f.write(json.dumps({"step": first_step + k, "Batch Loss/Train": lt, "Batch Loss/Dist": ld, "Batch Loss/CE": lc}) + "\n")
+            log_f.write(json.dumps(rec) + "\n")
+            log_f.flush()
+            log(rec)
+            if val_acc > best_acc or epoch == 0:  # as train (train.py:288-290); the reference's distillation cell keeps no checkpoint
+                best_acc = max(best_acc, val_acc)
+                torch.save(model.state_dict(), os.path.join(out_dir, "model_best.pt"))
+    if gstep is not None:
+        gstep.close()
+    if rank == 0:
+        log_f.write(json.dumps({"Training time": time.perf_counter() - start}) + "\n")
+        log_f.close()
+    return model, history
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="spectre_vit/configs/spectre_vit_cifar100.py")
@@ -262,8 +417,15 @@ def main():
     ap.add_argument("--graph", action="store_true", help="replay the training step from HIP graphs (spectre_vit.graph)")
     ap.add_argument("--augment", action="store_true",
                     help="the reference's training transform chain (train.py:100-115) on the GPU (spectre_vit.augment)")
+    ap.add_argument("--distill-paired", action="store_true",
+                    help="the reference's distillation loop with its two views per sample (train_distill): the student's augmented view "
+                         "and the teacher's Resize(256) -> CenterCrop(224) view, fused KD loss; with --graph, --no-augment")
+    ap.add_argument("--no-augment", action="store_true", help="--distill-paired: the student's view is ToTensor + Normalize only")
     ap.add_argument("--out", default="runs/spectre_vit")
     a = ap.parse_args()
+    if a.distill_paired:
+        train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out)
+        return
     train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph,
           model=a.model, augment=a.augment)
 

@@ -231,6 +231,12 @@ _WORK_MODELS = {
     "spv_small_sl_bwd": lambda i: ("head_bwd", i[0:3], i[3], "mfma", 4.0 * i[0] * i[1] * i[2]),
     "spv_cross_entropy_fwd": lambda i: ("cross_entropy_fwd", i[0:2], F32, "hbm", i[0] * i[1] * 4.0),
     "spv_cross_entropy_bwd": lambda i: ("cross_entropy_bwd", i[0:2], F32, "hbm", i[0] * i[1] * 8.0),
+    # student + teacher logits read (forward), read + the gradient written (backward)
+    "spv_distill_loss_fwd": lambda i: ("distill_loss_fwd", i[0:2], F32, "hbm", i[0] * i[1] * 8.0),
+    "spv_distill_loss_bwd": lambda i: ("distill_loss_bwd", i[0:2], F32, "hbm", i[0] * i[1] * 12.0),
+    # (batch, n_src, chans, n, resize, crop, dtype): the uint8 images read, the cropped view written once
+    "spv_teacher_view_u8": lambda i: ("teacher_view", (i[0], i[2], i[3], i[5]), i[6], "hbm",
+                                      1.0 * i[0] * i[2] * (i[3] * i[3] + i[5] * i[5] * _es(i[6]))),
     "spv_gemm_nt": lambda i: ("gemm_acc" if i[8] else "gemm", i[0:3], i[6], "mfma", 2.0 * i[0] * i[1] * i[2]),
     "spv_gemm_nt_grouped_rows": lambda i: ("gemm_grouped_rows", i[0:3], i[6], "mfma", 2.0 * i[0] * i[1] * i[2]),
     "spv_gemm_nt_grouped_rows_drop": lambda i: ("gemm_grouped_rows", i[0:3], i[6], "mfma", 2.0 * i[0] * i[1] * i[2]),
@@ -1411,6 +1417,57 @@ class CrossEntropyFn(torch.autograd.Function):
 
 def cross_entropy(logits, labels):
     return CrossEntropyFn.apply(logits, labels)
+
+
+_distill_workspaces = {}
+
+
+def _distill_workspace(dev):
+    key = dev.index   # as _ce_workspace: one per device, so that a graph capture reuses the warm-up's (zeroed) counter
+    ws = _distill_workspaces.get(key)
+    if ws is None:
+        ws = torch.zeros((_native.call("spv_distill_loss_workspace_floats"),), dtype=torch.float32, device=dev)
+        _distill_workspaces[key] = ws
+    return ws
+
+
+class DistillLossFn(torch.autograd.Function):
+    """w_soft T^2 / B sum p_t (log p_t - log p_s) + w_ce CE (reference repl/train.py:300-302, 334-348): one launch forward, one
+    backward -- the stock chain is two divisions, softmax, log_softmax, log, subtract, multiply, sum, two scalings, the cross-entropy
+    and autograd's backward of each.  Gradient to the student logits only."""
+
+    @staticmethod
+    def forward(ctx, student_logits, teacher_logits, labels, T, w_soft, w_ce):
+        _require_gpu(student_logits, teacher_logits, labels)
+        z, t = student_logits, teacher_logits
+        if (z.dim() != 2 or z.dtype != torch.float32 or t.dtype != torch.float32 or t.shape != z.shape or labels.dtype != torch.int64
+                or labels.shape != z.shape[:1]):
+            raise ValueError("distill_loss: fp32 student and teacher logits [rows, classes] and int64 labels [rows] expected")
+        z, t, y = z.contiguous(), t.detach().contiguous(), labels.contiguous()
+        rows, C = z.shape
+        lse = torch.empty((3, rows), dtype=torch.float32, device=z.device)
+        out = torch.empty((3,), dtype=torch.float32, device=z.device)
+        _native.call("spv_distill_loss_fwd", _p(z), _p(t), _p(y), _p(lse), _p(out), _p(_distill_workspace(z.device)), rows, C, float(T),
+                     float(w_soft), float(w_ce), _stream())
+        ctx.save_for_backward(z, t, y, lse)
+        ctx.consts = (float(T), float(w_soft), float(w_ce))
+        loss, soft, ce = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(soft, ce)
+        return loss, soft, ce
+
+    @staticmethod
+    def backward(ctx, go, _gsoft, _gce):
+        z, t, y, lse = ctx.saved_tensors
+        T, w_soft, w_ce = ctx.consts
+        go = go.reshape(1).float().contiguous()
+        dz = torch.empty_like(z)
+        _native.call("spv_distill_loss_bwd", _p(z), _p(t), _p(y), _p(lse), _p(go), _p(dz), z.shape[0], z.shape[1], T, w_soft, w_ce, _stream())
+        return dz, None, None, None, None, None
+
+
+def distill_loss(student_logits, teacher_logits, labels, T=2.0, w_soft=0.25, w_ce=0.75):
+    """(loss, soft, ce): the weighted loss (differentiable in the student logits) and the two unweighted terms, detached"""
+    return DistillLossFn.apply(student_logits, teacher_logits, labels, T, w_soft, w_ce)
 
 
 # ------------------------------------------------------------------------------------------------
