@@ -557,6 +557,18 @@ int spv_distill_loss_fwd(const float* student, const float* teacher, const int64
 int spv_distill_loss_bwd(const float* student, const float* teacher, const int64_t* labels, const float* lse3, const float* grad_out,
                          float* dlogits, int rows, int classes, float T, float w_soft, float w_ce, void* stream);
 
+/* The end of an inference / validation batch, one launch (csrc/spv_infer.hip): logits [rows][classes] (dtype: SPV_F32 or SPV_BF16),
+ * labels int64 [rows], *n_valid an int32 DEVICE word (read by the kernel, so a captured launch follows it), 1 <= k <= 8.
+ *   pred[r]  int64, every row: the index of the FIRST maximum (torch.argmax's documented tie rule).
+ *   stats    spv_eval_head_stats_words() 64-bit words, zeroed by the caller before the first call.  Words 0..2: seen, top1, topk as
+ *            int64; word 3: loss_sum as float64; the rest is the kernel's own (partials, arrival counter).  The call ADDS the batch:
+ *            only rows with r < *n_valid and 0 <= label < classes count (label -1: predicted, not counted); a row is a top-k hit when
+ *            #{j : z_j > z_y} + #{j < y : z_j == z_y} < k (k = 1: pred == y); its loss is logsumexp(z) - z_y in fp32, max-subtracted.
+ * The batch is joined in a fixed order and added to loss_sum with one float64 add: the same calls give the same bits. */
+int64_t spv_eval_head_stats_words(void);
+int spv_eval_head(const void* logits, const int64_t* labels, const int* n_valid, int64_t* pred, void* stats, int rows, int classes, int k,
+                  int dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

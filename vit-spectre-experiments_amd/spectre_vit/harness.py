@@ -99,9 +99,34 @@ class SyntheticCifar:
             yield img, self.labels[sel]
 
 
+def _graph_validate(session, batches, batch_hook, world):
+    """one validation pass through a spectre_vit.inference.InferenceSession: the model's current weights are taken (refresh), every batch
+    is one graph replay that ends in the on-device metrics kernel, and the epoch costs ONE host read.  -> (accuracy, loss, samples)"""
+    session.refresh()
+    session.reset_stats()
+    v_steps = 0
+    for img, label in batches:
+        if batch_hook is not None:
+            batch_hook("val", v_steps, img, label)
+        session.accumulate(img, label)
+        v_steps += 1
+    acc = session.stats_tensor()   # float64 (seen, top1, topk, loss_sum)
+    if world > 1:
+        dist.all_reduce(acc)
+    seen, top1, _, loss_sum = acc.tolist()
+    return top1 / max(seen, 1.0), loss_sum / max(seen, 1.0), int(seen)
+
+
+def _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, uint8):
+    from spectre_vit.inference import InferenceSession, eval_buckets
+    shard = len(range(rank, n_val, world))
+    return InferenceSession(model, batch_sizes=eval_buckets(shard, val_batch), autocast_dtype=autocast_dtype,
+                            input="uint8" if uint8 else "float")
+
+
 def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
           use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
-          augment=False, batch_hook=None):
+          augment=False, batch_hook=None, graph_eval=False):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
@@ -110,7 +135,11 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     kept once as uint8 NHWC, the shuffled batch index, the global step and augment_seed(config seed, rank) handed to
     spectre_vit.augment.TrainAugment; validation batches stay ToTensor + Normalize (eval_transform_spectre).  With graph=True its two
     launches run on the step's stream in front of the replay.  Not with uint8_input (the chain's output is float) or distill.
-    batch_hook(kind, step, img, label), kind "train" / "val": called with every batch as the model is about to see it (test seam)."""
+    batch_hook(kind, step, img, label), kind "train" / "val": called with every batch as the model is about to see it (test seam).
+    graph_eval=True: the epoch's validation runs through one spectre_vit.inference.InferenceSession -- a graph replay per batch (buckets:
+    the validation batch size and the tail rounded up to a multiple of 8), accuracy and loss accumulated on the device by its metrics
+    kernel, one host read per epoch; the session takes the trained weights with refresh() after the epoch's training, with graph=True
+    (weights updated through raw pointers) as with graph=False."""
     if augment and (uint8_input or distill):
         raise ValueError("augment=True yields normalised float batches for the plain training step: not with uint8_input or distill")
     c = parse_config(config_path)
@@ -136,7 +165,7 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     criterion = CrossEntropyLoss()  # nn.CrossEntropyLoss() of train.py:196 on the HIP path (spectre_vit/loss.py)
     if graph and distill:
         raise ValueError("graph=True replays the plain training step; the distillation step (teacher forward + KD loss) runs eagerly")
-    gstep = None
+    gstep = session = None
     if graph:
         from spectre_vit.optim import FusedAdamW
         optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
@@ -214,27 +243,35 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         train_acc = correct.item() / max(total, 1)
 
         model.eval()
-        v_correct = torch.zeros((), device=device, dtype=torch.int64)
-        v_loss = torch.zeros((), device=device)
-        v_total, v_steps = 0, 0
-        with torch.no_grad():
-            for img, label in val_set.batches(min(getattr(c, "val_batch_size", batch_size), n_val), False, None, rank, world,
-                                              raw_uint8=uint8_input and not distill, drop_last=False):
-                if batch_hook is not None:
-                    batch_hook("val", v_steps, img, label)
-                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp and not distill):
-                    y_pred = model(img)
-                v_correct += (label == torch.argmax(y_pred, dim=1)).sum()
-                v_loss += criterion(y_pred, label.long()) * label.size(0)  # sample-weighted: the tail batch is short
-                v_total += label.size(0)
-                v_steps += 1
-        stats = torch.stack([v_correct.float(), torch.tensor(float(v_total), device=device), v_loss])
-        if world > 1:
-            dist.all_reduce(stats)
-        val_acc = (stats[0] / stats[1].clamp(min=1)).item()
-        val_loss = (stats[2] / stats[1].clamp(min=1)).item()
+        val_batch = min(getattr(c, "val_batch_size", batch_size), n_val)
+        val_uint8 = uint8_input and not distill
+        if graph_eval:
+            if session is None:
+                session = _eval_session(model, n_val, val_batch, rank, world, torch.bfloat16 if use_amp and not distill else None, val_uint8)
+            val_acc, val_loss, val_samples = _graph_validate(
+                session, val_set.batches(val_batch, False, None, rank, world, raw_uint8=val_uint8, drop_last=False), batch_hook, world)
+        else:
+            v_correct = torch.zeros((), device=device, dtype=torch.int64)
+            v_loss = torch.zeros((), device=device)
+            v_total, v_steps = 0, 0
+            with torch.no_grad():
+                for img, label in val_set.batches(val_batch, False, None, rank, world, raw_uint8=val_uint8, drop_last=False):
+                    if batch_hook is not None:
+                        batch_hook("val", v_steps, img, label)
+                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp and not distill):
+                        y_pred = model(img)
+                    v_correct += (label == torch.argmax(y_pred, dim=1)).sum()
+                    v_loss += criterion(y_pred, label.long()) * label.size(0)  # sample-weighted: the tail batch is short
+                    v_total += label.size(0)
+                    v_steps += 1
+            stats = torch.stack([v_correct.float(), torch.tensor(float(v_total), device=device), v_loss])
+            if world > 1:
+                dist.all_reduce(stats)
+            val_acc = (stats[0] / stats[1].clamp(min=1)).item()
+            val_loss = (stats[2] / stats[1].clamp(min=1)).item()
+            val_samples = int(stats[1].item())
         rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
-               "Accuracy/Validation": val_acc, "steps": steps, "val_samples": int(stats[1].item())}
+               "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
         history.append(rec)
         if rank == 0:
             log_f.write(json.dumps(rec) + "\n")
@@ -245,6 +282,8 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
                 torch.save(model.state_dict(), os.path.join(out_dir, "model_best.pt"))
     if gstep is not None:
         gstep.close()
+    if session is not None:
+        session.close()
     if rank == 0:
         log_f.write(json.dumps({"Training time": time.perf_counter() - start}) + "\n")
         log_f.close()
@@ -253,7 +292,7 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
 
 def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
                   use_amp=False, graph=False, augment=True, teacher=None, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75,
-                  resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None):
+                  resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -264,7 +303,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     (train.py:299); True runs the student under bf16 autocast, the loss on its fp32 logits.  Validation: student only, CE only, every
     sample (train.py:365-383).  The three per-batch losses the reference logs (train.py:355-359) are kept on the device and written
     once per epoch as {"step", "Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE"} lines: no host synchronisation per step.
-    batch_hook(kind, step, img, label), kind "train" / "teacher" / "val" (test seam)."""
+    batch_hook(kind, step, img, label), kind "train" / "teacher" / "val" (test seam).  graph_eval: as in train()."""
     from spectre_vit import _native
     c = parse_config(config_path)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -299,7 +338,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     teacher.eval()
     criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight)
     val_criterion = CrossEntropyLoss()
-    gstep = None
+    gstep = session = None
     if graph:
         from spectre_vit.optim import FusedAdamW
         optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
@@ -366,26 +405,34 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
         train_acc = correct.item() / max(total, 1)
 
         model.eval()
-        v_correct = torch.zeros((), device=device, dtype=torch.int64)
-        v_loss = torch.zeros((), device=device)
-        v_total, v_steps = 0, 0
-        with torch.no_grad():
-            for img, label in val_set.batches(min(getattr(c, "val_batch_size", batch_size), n_val), False, None, rank, world, drop_last=False):
-                if batch_hook is not None:
-                    batch_hook("val", v_steps, img, label)
-                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
-                    y_pred = model(img)
-                v_correct += (label == torch.argmax(y_pred, dim=1)).sum()
-                v_loss += val_criterion(y_pred.float(), label.long()) * label.size(0)
-                v_total += label.size(0)
-                v_steps += 1
-        stats = torch.stack([v_correct.float(), torch.tensor(float(v_total), device=device), v_loss])
-        if world > 1:
-            dist.all_reduce(stats)
-        val_acc = (stats[0] / stats[1].clamp(min=1)).item()
-        val_loss = (stats[2] / stats[1].clamp(min=1)).item()
+        val_batch = min(getattr(c, "val_batch_size", batch_size), n_val)
+        if graph_eval:
+            if session is None:
+                session = _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, False)
+            val_acc, val_loss, val_samples = _graph_validate(session, val_set.batches(val_batch, False, None, rank, world, drop_last=False),
+                                                             batch_hook, world)
+        else:
+            v_correct = torch.zeros((), device=device, dtype=torch.int64)
+            v_loss = torch.zeros((), device=device)
+            v_total, v_steps = 0, 0
+            with torch.no_grad():
+                for img, label in val_set.batches(val_batch, False, None, rank, world, drop_last=False):
+                    if batch_hook is not None:
+                        batch_hook("val", v_steps, img, label)
+                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
+                        y_pred = model(img)
+                    v_correct += (label == torch.argmax(y_pred, dim=1)).sum()
+                    v_loss += val_criterion(y_pred.float(), label.long()) * label.size(0)
+                    v_total += label.size(0)
+                    v_steps += 1
+            stats = torch.stack([v_correct.float(), torch.tensor(float(v_total), device=device), v_loss])
+            if world > 1:
+                dist.all_reduce(stats)
+            val_acc = (stats[0] / stats[1].clamp(min=1)).item()
+            val_loss = (stats[2] / stats[1].clamp(min=1)).item()
+            val_samples = int(stats[1].item())
         rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
-               "Accuracy/Validation": val_acc, "steps": steps, "val_samples": int(stats[1].item())}
+               "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
         history.append(rec)
         if rank == 0:
             for k, (lt, ld, lc) in enumerate(per_batch):
@@ -398,13 +445,15 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                 torch.save(model.state_dict(), os.path.join(out_dir, "model_best.pt"))
     if gstep is not None:
         gstep.close()
+    if session is not None:
+        session.close()
     if rank == 0:
         log_f.write(json.dumps({"Training time": time.perf_counter() - start}) + "\n")
         log_f.close()
     return model, history
 
 
-def main():
+def build_parser():
     ap = argparse.ArgumentParser()
     ap.add_argument("--config", default="spectre_vit/configs/spectre_vit_cifar100.py")
     ap.add_argument("--mixer", default="permut")
@@ -421,13 +470,20 @@ def main():
                     help="the reference's distillation loop with its two views per sample (train_distill): the student's augmented view "
                          "and the teacher's Resize(256) -> CenterCrop(224) view, fused KD loss; with --graph, --no-augment")
     ap.add_argument("--no-augment", action="store_true", help="--distill-paired: the student's view is ToTensor + Normalize only")
+    ap.add_argument("--graph-eval", action="store_true",
+                    help="validate through a graph-replayed InferenceSession with on-device metrics (spectre_vit.inference)")
     ap.add_argument("--out", default="runs/spectre_vit")
-    a = ap.parse_args()
+    return ap
+
+
+def main(argv=None):
+    a = build_parser().parse_args(argv)
     if a.distill_paired:
-        train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out)
+        train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out,
+                      graph_eval=a.graph_eval)
         return
     train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph,
-          model=a.model, augment=a.augment)
+          model=a.model, augment=a.augment, graph_eval=a.graph_eval)
 
 
 if __name__ == "__main__":

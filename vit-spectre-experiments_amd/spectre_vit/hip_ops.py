@@ -7,6 +7,7 @@ on a HIP device: a CPU tensor raises (there is deliberately no CPU / eager-PyTor
 from __future__ import annotations
 
 import collections
+import contextlib
 import ctypes
 import os
 import warnings
@@ -122,6 +123,8 @@ class _ShadowCache:
         self.epoch = 0
 
     def get(self, w: torch.Tensor, dtype: torch.dtype):
+        if _pinned is not None:   # an InferenceSession's forward: its own fixed buffers, never this cache's
+            return _pinned.get(w, dtype)
         key = (id(w), dtype)
         ent = self._d.get(key)
         ver = (w.data_ptr(), w._version, tuple(w.shape), self.epoch)
@@ -184,6 +187,75 @@ class ShadowSet:
             w = wr()
             if w is not None:
                 _shadows._fresh[(id(w), self.dtype)] = (wr, wc, wt, (w._version, _shadows.epoch))
+
+
+class PinnedShadows:
+    """(W, W^T) copies at FIXED addresses, owned by one spectre_vit.inference.InferenceSession.  While the session's forward runs
+    (``with pinned_shadows(p):`` -- warm-up and capture) every ``_ShadowCache.get`` is served from here: the eager warm-up allocates
+    and fills a weight's copies on first sight, the capture then finds them and launches nothing, so a replay neither casts a weight
+    nor reads memory that ``invalidate_weight_shadows`` or a replaced cache object could free.  ``refresh()`` recasts every copy in
+    place with one spv_weight_shadows_multi launch per dtype."""
+
+    def __init__(self):
+        self.ent = {}      # (id(w), dtype) -> (w, W in dtype, W^T in dtype); w is held: the session owns the weights it reads
+        self._tables = {}  # dtype -> (entries, table, tile tensors, tiles)
+
+    def get(self, w, dtype):
+        key = (id(w), dtype)
+        e = self.ent.get(key)
+        if e is not None and e[0] is w:
+            return e[1], e[2]
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("a weight asked for its compute-dtype copies for the first time inside a graph capture: the warm-up "
+                               "forward must run the very launch sequence that is captured")
+        n, k = w.shape
+        wd = w.detach()
+        wc = wd if dtype == torch.float32 else torch.empty((n, k), dtype=dtype, device=w.device)
+        ldt = (n + 7) // 8 * 8
+        wt = torch.empty((k, ldt), dtype=dtype, device=w.device)
+        _native.call("spv_weight_shadows", _p(wd), 0 if wc is wd else _p(wc), _p(wt), n, k, ldt, _DT[dtype], _stream())
+        self.ent[key] = (w, wc, wt)
+        return wc, wt
+
+    def _table(self, dtype):
+        ents = [e for (_, dt), e in self.ent.items() if dt == dtype]
+        t = self._tables.get(dtype)
+        if t is not None and t[0] == len(ents):
+            return t
+        dev = ents[0][0].device
+        rows, tt, tx, ty = [], [], [], []
+        for i, (w, wc, wt) in enumerate(ents):
+            n, k = w.shape
+            ld = wt.shape[1]
+            rows += [w.data_ptr(), 0 if wc.data_ptr() == w.data_ptr() else wc.data_ptr(), wt.data_ptr(), n | (k << 32), ld]
+            for by in range((ld + 31) // 32):
+                for bx in range((k + 63) // 64):
+                    tt.append(i)
+                    tx.append(bx)
+                    ty.append(by)
+        t = (len(ents), torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(tt, dtype=torch.int32).to(dev),
+             torch.tensor(tx, dtype=torch.int32).to(dev), torch.tensor(ty, dtype=torch.int32).to(dev), len(tt))
+        self._tables[dtype] = t
+        return t
+
+    def refresh(self):
+        for dtype in {dt for _, dt in self.ent}:
+            _, table, tt, tx, ty, ntiles = self._table(dtype)
+            _native.call("spv_weight_shadows_multi", table.data_ptr(), tt.data_ptr(), tx.data_ptr(), ty.data_ptr(), ntiles, _DT[dtype],
+                         _stream())
+
+
+_pinned = None
+
+
+@contextlib.contextmanager
+def pinned_shadows(p):
+    global _pinned
+    prev, _pinned = _pinned, p
+    try:
+        yield p
+    finally:
+        _pinned = prev
 
 
 def refresh_weight_shadows(module, weights_fn):
@@ -1417,6 +1489,28 @@ class CrossEntropyFn(torch.autograd.Function):
 
 def cross_entropy(logits, labels):
     return CrossEntropyFn.apply(logits, labels)
+
+
+def eval_head_stats(device):
+    """a zeroed stats block of spv_eval_head: int64 words, [0:3] = seen, top1, topk, [3] = loss_sum (float64 bits)"""
+    return torch.zeros((_native.call("spv_eval_head_stats_words"),), dtype=torch.int64, device=device)
+
+
+def eval_head(logits, labels, n_valid, pred, stats, k=5):
+    """One launch at the end of an inference batch (csrc/spv_infer.hip): pred[r] = first maximum of logits[r], and the rows with
+    r < n_valid[0] and 0 <= label < classes are ADDED to ``stats`` (eval_head_stats): seen, top-1 and top-k hits as int64, the sum of
+    logsumexp(z) - z_y as float64, joined in a fixed order.  n_valid is an int32 device tensor: a captured launch follows it."""
+    _require_gpu(logits, labels, n_valid, pred, stats)
+    if logits.dim() != 2 or not logits.is_contiguous():
+        raise ValueError("eval_head: contiguous logits [rows, classes] expected")
+    rows, C = logits.shape
+    if (labels.dtype != torch.int64 or pred.dtype != torch.int64 or n_valid.dtype != torch.int32 or stats.dtype != torch.int64
+            or labels.numel() < rows or pred.numel() < rows or n_valid.numel() < 1
+            or stats.numel() < _native.call("spv_eval_head_stats_words")
+            or not (labels.is_contiguous() and pred.is_contiguous() and stats.is_contiguous())):
+        raise ValueError("eval_head: int64 labels[rows] and pred[rows], an int32 n_valid word and an eval_head_stats block expected")
+    _native.call("spv_eval_head", _p(logits), _p(labels), _p(n_valid), _p(pred), _p(stats), rows, C, int(k), _dt(logits), _stream())
+    return pred
 
 
 _distill_workspaces = {}
