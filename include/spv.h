@@ -325,6 +325,56 @@ int spv_adamw_multi(const void* table, const int* chunk_tensor, const int* chunk
                     float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
                     float bias_correction1, float bias_correction2, const float* step_dev, void* stream);
 
+/* ---- on-device step control: LR schedule, gradient clipping, non-finite skip --------------------------------
+ * What the reference's loop does on the host around optimizer.step() -- CosineAnnealingLR (spectre_vit/repl/train.py:202-203),
+ * GradScaler's dropped step on an inf / NaN gradient (train.py:205,236-238) and the usual torch.nn.utils.clip_grad_norm_ -- decided
+ * on the device, so that a HIP-graph replay (kernel arguments frozen at capture) follows the schedule and the gradient.  Three
+ * launches per step: spv_grad_sumsq per parameter group, ONE spv_step_control, spv_adamw_multi_ctl per group.
+ *
+ * The control block: 64 bytes of device memory, 8-byte aligned, written by spv_step_control with plain vector stores and read by
+ * spv_adamw_multi_ctl.  sched_step and skipped are the only fields carried from one step to the next (the caller initialises them,
+ * 0 for a fresh run). */
+typedef struct spv_step_ctl {
+    double a, b;        /* this step's rate of a group: lr = (float)(a * base_lr + b), product and sum each rounded to double */
+    float clip_coef;    /* the gradient is multiplied by this in registers: min(1, max_norm / (norm + 1e-6)); 1 without clipping */
+    int apply;          /* 0: this step is dropped (non-finite gradient): no parameter, moment or Adam step count changes */
+    float grad_norm;    /* L2 norm over every gradient of every group, as the last spv_step_control saw it */
+    int sched_step;     /* calls of spv_step_control so far = the schedule's t of the NEXT step (advances on dropped steps too) */
+    int skipped;        /* dropped steps so far */
+    int reserved[7];
+} spv_step_ctl;
+#define SPV_CTL_SCHEDULE 1   /* flags of spv_step_control */
+#define SPV_CTL_CLIP 2
+#define SPV_CTL_SKIP_NONFINITE 4
+
+/* partials[c] = sum of g^2 over chunk c of the spv_adamw_multi chunk table (table / chunk_tensor / chunk_off / sizes / nchunks as
+ * there; only the g pointers are read), formed in fp64: the square of an fp32 value never overflows a double, so the sum is
+ * non-finite exactly when an element is, and a large finite gradient stays finite.  One workgroup per chunk, a fixed summation
+ * order, no atomics. */
+int spv_grad_sumsq(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, double* partials,
+                   void* stream);
+
+/* One workgroup: folds partials[0 .. npartials) (every group's, in the caller's order) in a fixed order, then one thread fills *ctl
+ * for this step and advances ctl->sched_step.  t = ctl->sched_step on entry, W = warmup_steps, T = total_steps:
+ *   SPV_CTL_SCHEDULE        t < W:  lr = base * (t + 1) / (W + 1)                 (torch LinearLR(start_factor=1/(W+1), total_iters=W))
+ *                           t >= W: lr = eta_min + (base - eta_min) * (1 + cos(pi * min(t - W, T - W) / (T - W))) / 2
+ *                           (torch CosineAnnealingLR(T_max=T-W, eta_min) behind SequentialLR(milestones=[W]); past T the rate STAYS
+ *                           at eta_min where torch's closed form would rise again); evaluated in fp64.  Without the flag a = 1, b = 0.
+ *   SPV_CTL_CLIP            clip_coef = min(1, max_norm / (norm + 1e-6)) as torch.nn.utils.clip_grad_norm_ (a NaN norm gives a NaN
+ *                           coefficient, as there); the gradient tensors themselves are NOT rewritten.
+ *   SPV_CTL_SKIP_NONFINITE  apply = 0 and skipped += 1 when the sum of squares is not finite.
+ * When the step is applied, *step_ptrs[k] += 1 for k < nsteps: the Adam step counts (one float per parameter group) that
+ * spv_adamw_multi_ctl reads through step_dev.  step_ptrs is a DEVICE array of device pointers. */
+int spv_step_control(const double* partials, int npartials, float* const* step_ptrs, int nsteps, spv_step_ctl* ctl, int flags,
+                     int warmup_steps, int total_steps, double eta_min, float max_norm, void* stream);
+
+/* spv_adamw_multi with lr = (float)(ctl->a * base_lr + ctl->b), the gradient scaled by ctl->clip_coef in registers and nothing
+ * written at all when ctl->apply == 0.  The same update body as spv_adamw_multi: with a = 1, b = 0, clip_coef = 1, apply = 1 the
+ * results are bit for bit its results.  step_dev (required): the group's Adam step count, already advanced by spv_step_control. */
+int spv_adamw_multi_ctl(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, double base_lr,
+                        float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                        const float* step_dev, const spv_step_ctl* ctl, void* stream);
+
 /* ---- Walsh-Hadamard butterflies along the last axis -----------------------------------
  * spectre_vit/models/spectre/hadamar.py: fwht :12-32 / hadamard_transform :83-112 (mode 0, natural order; scale = n^-1/2
  * when normalised), fwht_fast :58-80 (mode 1: every stage interleaves sum / difference, un-normalised) and its transpose

@@ -1,5 +1,6 @@
 // spv_misc.hip -- error plumbing + small bandwidth kernels (casts, transposes, GELU, column sums).
 #include "spv_common.h"
+#include "spv_adamw_core.h"
 
 #include <string.h>
 
@@ -346,9 +347,8 @@ extern "C" int spv_colsum(const void* x, float* out, float* partials, int rows, 
 // 63 tensors / 13 MB of parameters (latency bound: most tensors are 512-element LayerNorm vectors); one launch whose
 // workgroups are dealt 2048-element chunks from a host-built chunk table streams the same bytes in a few microseconds.
 // Arithmetic = torch.optim.AdamW (decoupled weight decay, bias correction, amsgrad off, maximize off).
+// The update itself is adamw_chunk (spv_adamw_core.h), shared with the step-control form of the launch (spv_optim.hip).
 namespace {
-struct AdamTensor { float* p; const float* g; float* m; float* v; };
-
 __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamTensor* __restrict__ tab, const int* __restrict__ chunk_tensor,
                                                           const int* __restrict__ chunk_off, const int* __restrict__ sizes, float lr,
                                                           float beta1, float beta2, float omb1, float omb2, float eps, float wd,
@@ -357,44 +357,7 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamTensor* __re
     const int off = chunk_off[blockIdx.x];
     const AdamTensor a = tab[t];
     const int n = sizes[t];
-    if (step_dev != nullptr) {  // capturable mode: the step count lives on the device (already advanced for this step)
-        const float s = *step_dev;
-        bc1 = 1.0f - powf(beta1, s);
-        bc2 = 1.0f - powf(beta2, s);
-    }
-    const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2), decay = 1.0f - lr * wd;
-    const int base = off + threadIdx.x * 4;
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-        const int i = base + h * 1024;
-        if (i + 3 < n && ((reinterpret_cast<uintptr_t>(a.p) | reinterpret_cast<uintptr_t>(a.g) | reinterpret_cast<uintptr_t>(a.m) |
-                           reinterpret_cast<uintptr_t>(a.v)) & 15) == 0) {
-            float4 p = *reinterpret_cast<const float4*>(a.p + i), m = *reinterpret_cast<const float4*>(a.m + i);
-            float4 v = *reinterpret_cast<const float4*>(a.v + i);
-            const float4 g = *reinterpret_cast<const float4*>(a.g + i);
-            float* pp = &p.x; float* mm = &m.x; float* vv = &v.x; const float* gg = &g.x;
-#pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                mm[u] = beta1 * mm[u] + omb1 * gg[u];
-                vv[u] = beta2 * vv[u] + omb2 * gg[u] * gg[u];
-                pp[u] = pp[u] * decay - step_size * mm[u] / (sqrtf(vv[u]) * inv_sqrt_bc2 + eps);
-            }
-            *reinterpret_cast<float4*>(a.p + i) = p;
-            *reinterpret_cast<float4*>(a.m + i) = m;
-            *reinterpret_cast<float4*>(a.v + i) = v;
-        } else {
-            for (int u = 0; u < 4; ++u) {
-                const int j = i + u;
-                if (j >= n) break;
-                const float g = a.g[j];
-                const float m = beta1 * a.m[j] + omb1 * g;
-                const float v = beta2 * a.v[j] + omb2 * g * g;
-                a.m[j] = m;
-                a.v[j] = v;
-                a.p[j] = a.p[j] * decay - step_size * m / (sqrtf(v) * inv_sqrt_bc2 + eps);
-            }
-        }
-    }
+    adamw_chunk<false>(a, n, off, lr, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2, step_dev, 1.0f);
 }
 }  // namespace
 

@@ -1,0 +1,159 @@
+// spv_optim.hip -- on-device step control of the optimizer (include/spv.h: spv_step_ctl): the gradient's sum of squares, the
+// one-workgroup kernel that turns it and the step count into this step's learning rate / clip coefficient / apply flag, and the
+// AdamW launch that reads them.  Nothing here is decided on the host, so a captured training step follows the schedule and skips a
+// non-finite gradient on every replay.
+#include "spv_common.h"
+#include "spv_adamw_core.h"
+
+#include <math.h>
+
+static_assert(sizeof(spv_step_ctl) == 64, "spv_step_ctl is a fixed 64-byte layout (spectre_vit/optim.py packs it by hand)");
+
+namespace {
+// ---------------------------------------------------------------------------------------------------------
+// Sum of squares of one 2048-element gradient chunk, in fp64: the chunk walk of adamw_chunk (two float4 per thread where the
+// gradient's base is 16-byte aligned, scalar otherwise and in the short last chunk of a tensor).  Fixed order: eight squares per
+// thread, a butterfly over the wave, the four wave sums added by one thread.
+__global__ __launch_bounds__(256) void grad_sumsq_kernel(const AdamTensor* __restrict__ tab, const int* __restrict__ chunk_tensor,
+                                                         const int* __restrict__ chunk_off, const int* __restrict__ sizes,
+                                                         double* __restrict__ partials) {
+    __shared__ double wave_part[4];
+    const int t = chunk_tensor[blockIdx.x];
+    const int off = chunk_off[blockIdx.x];
+    const float* __restrict__ g = tab[t].g;
+    const int n = sizes[t];
+    const int base = off + threadIdx.x * 4;
+    double s = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = base + h * 1024;
+        if (i + 3 < n && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+            const float4 q = *reinterpret_cast<const float4*>(g + i);
+            s += (double)q.x * (double)q.x;
+            s += (double)q.y * (double)q.y;
+            s += (double)q.z * (double)q.z;
+            s += (double)q.w * (double)q.w;
+        } else {
+            for (int u = 0; u < 4; ++u) {
+                const int j = i + u;
+                if (j >= n) break;
+                const double x = (double)g[j];
+                s += x * x;
+            }
+        }
+    }
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w, 64);
+    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// One workgroup: partials -> ctl.  Thread i adds partials i, i + 256, ... in that order, a fixed tree joins the 256 sums; the same
+// launch gives the same bits on every replay and on every rank of a data-parallel job (each holds the same averaged gradient).
+__global__ __launch_bounds__(256) void step_control_kernel(const double* __restrict__ partials, int npartials, float* const* __restrict__ step_ptrs,
+                                                           int nsteps, spv_step_ctl* __restrict__ ctl, int flags, int warmup_steps,
+                                                           int total_steps, double eta_min, float max_norm) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int i = threadIdx.x; i < npartials; i += 256) s += partials[i];
+    red[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) red[threadIdx.x] += red[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x != 0) return;
+    const double sumsq = red[0];
+    const float norm = (float)sqrt(sumsq);
+    const int t = ctl->sched_step;
+    double a = 1.0, b = 0.0;
+    if (flags & SPV_CTL_SCHEDULE) {
+        if (t < warmup_steps) {
+            a = (double)(t + 1) / (double)(warmup_steps + 1);
+        } else {
+            const int span = total_steps - warmup_steps;
+            const int k = min(t - warmup_steps, span);
+            a = k >= span ? 0.0 : 0.5 * (1.0 + cos(M_PI * (double)k / (double)span));   // past T: exactly eta_min
+            b = eta_min * (1.0 - a);
+        }
+    }
+    float coef = 1.0f;
+    if (flags & SPV_CTL_CLIP) {
+        const float c = max_norm / (norm + 1e-6f);
+        coef = c < 1.0f ? c : (c != c ? c : 1.0f);   // clamp(max=1) that keeps a NaN, as torch's
+    }
+    const int apply = ((flags & SPV_CTL_SKIP_NONFINITE) && !isfinite(sumsq)) ? 0 : 1;
+    ctl->a = a;
+    ctl->b = b;
+    ctl->clip_coef = coef;
+    ctl->apply = apply;
+    ctl->grad_norm = norm;
+    ctl->sched_step = t + 1;
+    if (apply) {
+        for (int k = 0; k < nsteps; ++k) *step_ptrs[k] += 1.0f;
+    } else {
+        ctl->skipped += 1;
+    }
+}
+
+__global__ __launch_bounds__(256) void adamw_multi_ctl_kernel(const AdamTensor* __restrict__ tab, const int* __restrict__ chunk_tensor,
+                                                              const int* __restrict__ chunk_off, const int* __restrict__ sizes, double base_lr,
+                                                              float beta1, float beta2, float omb1, float omb2, float eps, float wd,
+                                                              const float* __restrict__ step_dev, const spv_step_ctl* __restrict__ ctl) {
+    if (ctl->apply == 0) return;   // a dropped step writes nothing
+    // product and sum rounded separately (no fused multiply-add): the host reproduces the rate from a, b bit for bit
+    const float lr = (float)__dadd_rn(__dmul_rn(ctl->a, base_lr), ctl->b);
+    const int t = chunk_tensor[blockIdx.x];
+    const int off = chunk_off[blockIdx.x];
+    const AdamTensor a = tab[t];
+    const int n = sizes[t];
+    adamw_chunk<true>(a, n, off, lr, beta1, beta2, omb1, omb2, eps, wd, 0.0f, 0.0f, step_dev, ctl->clip_coef);
+}
+}  // namespace
+
+extern "C" int spv_grad_sumsq(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
+                              double* partials, void* stream) {
+    SPV_CHECK(nchunks >= 0, "spv_grad_sumsq: nchunks = %d", nchunks);
+    SPV_CHECK(table && chunk_tensor && chunk_off && sizes, "spv_grad_sumsq: null table");
+    SPV_CHECK(partials, "spv_grad_sumsq: null partials");
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(grad_sumsq_kernel, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, partials);
+    SPV_LAUNCH_CHECK("spv_grad_sumsq");
+    return 0;
+}
+
+extern "C" int spv_step_control(const double* partials, int npartials, float* const* step_ptrs, int nsteps, spv_step_ctl* ctl, int flags,
+                                int warmup_steps, int total_steps, double eta_min, float max_norm, void* stream) {
+    SPV_CHECK(npartials >= 0 && nsteps >= 0, "spv_step_control: npartials = %d, nsteps = %d", npartials, nsteps);
+    SPV_CHECK(ctl, "spv_step_control: null control block");
+    SPV_CHECK((partials || npartials == 0) && (step_ptrs || nsteps == 0), "spv_step_control: null partials / step_ptrs");
+    SPV_CHECK((flags & ~(SPV_CTL_SCHEDULE | SPV_CTL_CLIP | SPV_CTL_SKIP_NONFINITE)) == 0, "spv_step_control: unknown flags 0x%x", flags);
+    if (flags & SPV_CTL_SCHEDULE) {
+        SPV_CHECK(warmup_steps >= 0 && total_steps > warmup_steps, "spv_step_control: schedule needs 0 <= warmup_steps < total_steps (%d, %d)",
+                  warmup_steps, total_steps);
+        SPV_CHECK(eta_min >= 0.0, "spv_step_control: eta_min = %g must be >= 0", eta_min);   // (false for a NaN too)
+    }
+    if (flags & SPV_CTL_CLIP) SPV_CHECK(max_norm > 0.0f, "spv_step_control: max_norm = %g must be > 0", (double)max_norm);
+    hipLaunchKernelGGL(step_control_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), partials, npartials, step_ptrs, nsteps,
+                       ctl, flags, warmup_steps, total_steps, eta_min, max_norm);
+    SPV_LAUNCH_CHECK("spv_step_control");
+    return 0;
+}
+
+extern "C" int spv_adamw_multi_ctl(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
+                                   double base_lr, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                                   float weight_decay, const float* step_dev, const spv_step_ctl* ctl, void* stream) {
+    SPV_CHECK(nchunks >= 0, "spv_adamw_multi_ctl: nchunks = %d", nchunks);
+    SPV_CHECK(table && chunk_tensor && chunk_off && sizes, "spv_adamw_multi_ctl: null table");
+    SPV_CHECK(step_dev && ctl, "spv_adamw_multi_ctl: null step count / control block");
+    SPV_CHECK(base_lr >= 0.0, "spv_adamw_multi_ctl: base_lr = %g must be >= 0", base_lr);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(adamw_multi_ctl_kernel, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, base_lr, beta1, beta2, one_minus_beta1,
+                       one_minus_beta2, eps, weight_decay, step_dev, ctl);
+    SPV_LAUNCH_CHECK("spv_adamw_multi_ctl");
+    return 0;
+}

@@ -16,7 +16,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # SPV_LIB_PATH: a second build of the same ABI, for A/B runs inside one GPU job (tools/); never a fallback
 LIB_PATH = os.environ.get("SPV_LIB_PATH") or os.path.join(os.path.dirname(_HERE), "lib", "libspv_hip.so")
 
-c_vp, c_i, c_i64, c_u64, c_f = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float
+c_vp, c_i, c_i64, c_u64, c_f, c_d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_double
 
 # indices of include/spv.h's SPV_PATH_* enum (dispatch census, test aid)
 PATH = dict(gemm_strip=0, gemm_strip_acc=1, gemm_tn=2, tail_lc=3, tail_up=4, tail_ln=5, fnet_mfma=6, gather_lds=7, gemm_tn_wide=9,
@@ -104,6 +104,9 @@ SIGNATURES = {
     "spv_set_seed_device_ptr": [c_vp],
     "spv_seed_advance": [c_vp, c_vp],
     "spv_adamw_multi": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp],
+    "spv_grad_sumsq": [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_vp],
+    "spv_step_control": [c_vp, c_i, c_vp, c_i, c_vp, c_i, c_i, c_i, c_d, c_f, c_vp],
+    "spv_adamw_multi_ctl": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_vp],
     "spv_fwht": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp],
     "spv_axpby": [c_vp, c_vp, c_vp, c_f, c_f, c_i64, c_i, c_vp],
     "spv_spectrum_floats": [c_i, c_i],

@@ -8,6 +8,10 @@ What is captured: zero_grad -> forward (autocast) -> loss -> backward -> optimiz
 spectre_vit/repl/train.py:216-238 minus the host-side bookkeeping.  Requirements:
   * the optimizer must keep its step count on the device: ``spectre_vit.optim.FusedAdamW(capturable=True)`` or
     ``torch.optim.AdamW(fused=True, capturable=True)``;
+  * learning-rate schedule, gradient clipping, non-finite skip: by-value kernel arguments are frozen at capture, so a rate set through
+    ``param_groups`` between replays has no effect -- ``FusedAdamW(schedule=..., max_grad_norm=..., skip_nonfinite=...)`` decides all
+    three on the device inside ``optimizer.step()``, which is what every step class here captures (``GraphedDPStep``: in graph B,
+    behind the all-reduce, so every rank decides alike);
   * dropout: seeds are by-value kernel arguments frozen at capture, so every dropout kernel adds a 64-bit device word that this
     class advances once per replay (``spv_seed_advance`` is the first node of the graph) -- fresh masks every step;
   * fixed shapes (one graph per batch shape).

@@ -99,6 +99,25 @@ class SyntheticCifar:
             yield img, self.labels[sel]
 
 
+def _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite, total_steps):
+    """the harness's five step-control arguments -> FusedAdamW keywords; {} when none is on (the optimizer choice is then untouched)"""
+    if lr_schedule not in (None, "cosine"):
+        raise ValueError(f"lr_schedule={lr_schedule!r}: None or 'cosine'")
+    if lr_schedule is None and (warmup_steps or eta_min):
+        raise ValueError("warmup_steps / eta_min belong to lr_schedule='cosine'")
+    if lr_schedule is None and clip_grad_norm is None and not skip_nonfinite:
+        return {}
+    from spectre_vit.optim import CosineSchedule
+    schedule = CosineSchedule(total_steps, warmup_steps, eta_min) if lr_schedule == "cosine" else None
+    return dict(schedule=schedule, max_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
+
+
+def _step_control_record(optimizer):
+    """the epoch record's step-control entries: ONE read of the optimizer's control block"""
+    c = optimizer._read_ctl()
+    return {"LR": optimizer.last_lr(c)[0], "GradNorm": c["grad_norm"], "SkippedSteps": c["skipped"]}
+
+
 def _graph_validate(session, batches, batch_hook, world):
     """one validation pass through a spectre_vit.inference.InferenceSession: the model's current weights are taken (refresh), every batch
     is one graph replay that ends in the on-device metrics kernel, and the epoch costs ONE host read.  -> (accuracy, loss, samples)"""
@@ -126,7 +145,8 @@ def _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, uint8):
 
 def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
           use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
-          augment=False, batch_hook=None, graph_eval=False):
+          augment=False, batch_hook=None, graph_eval=False, lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None,
+          skip_nonfinite=False):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
@@ -139,7 +159,11 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     graph_eval=True: the epoch's validation runs through one spectre_vit.inference.InferenceSession -- a graph replay per batch (buckets:
     the validation batch size and the tail rounded up to a multiple of 8), accuracy and loss accumulated on the device by its metrics
     kernel, one host read per epoch; the session takes the trained weights with refresh() after the epoch's training, with graph=True
-    (weights updated through raw pointers) as with graph=False."""
+    (weights updated through raw pointers) as with graph=False.
+    lr_schedule="cosine" (with warmup_steps, eta_min), clip_grad_norm, skip_nonfinite: the optimizer's on-device step control
+    (spectre_vit.optim: CosineSchedule over total_steps = steps per epoch * epochs as train.py:202-203, gradient clipping, a step with
+    an inf / NaN gradient dropped as GradScaler does, train.py:236-238).  With any of them the optimizer is FusedAdamW(capturable=True)
+    on the eager path too, and the epoch record gains "LR" (the last step's rate), "GradNorm" (the last step's) and "SkippedSteps"."""
     if augment and (uint8_input or distill):
         raise ValueError("augment=True yields normalised float batches for the plain training step: not with uint8_input or distill")
     c = parse_config(config_path)
@@ -166,11 +190,18 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     if graph and distill:
         raise ValueError("graph=True replays the plain training step; the distillation step (teacher forward + KD loss) runs eagerly")
     gstep = session = None
+    per_pass = (n_train // world) // batch_size
+    control = _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite,
+                                 (min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass) * epochs)
     if graph:
         from spectre_vit.optim import FusedAdamW
         optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
-                               static_grads=True)
+                               static_grads=True, **control)
         reducer = None   # the graphed step owns its own (fixed-address) gradient buffer
+    elif control:
+        from spectre_vit.optim import FusedAdamW
+        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True, **control)
+        reducer = GradReducer(model)
     else:
         optimizer = optim.AdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay)  # train.py:199-201
         reducer = GradReducer(model)
@@ -272,6 +303,8 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
             val_samples = int(stats[1].item())
         rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
                "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
+        if control:
+            rec.update(_step_control_record(optimizer))
         history.append(rec)
         if rank == 0:
             log_f.write(json.dumps(rec) + "\n")
@@ -292,7 +325,8 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
 
 def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
                   use_amp=False, graph=False, augment=True, teacher=None, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75,
-                  resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False):
+                  resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False,
+                  lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -303,7 +337,8 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     (train.py:299); True runs the student under bf16 autocast, the loss on its fp32 logits.  Validation: student only, CE only, every
     sample (train.py:365-383).  The three per-batch losses the reference logs (train.py:355-359) are kept on the device and written
     once per epoch as {"step", "Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE"} lines: no host synchronisation per step.
-    batch_hook(kind, step, img, label), kind "train" / "teacher" / "val" (test seam).  graph_eval: as in train()."""
+    batch_hook(kind, step, img, label), kind "train" / "teacher" / "val" (test seam).  graph_eval, lr_schedule, warmup_steps, eta_min,
+    clip_grad_norm, skip_nonfinite: as in train()."""
     from spectre_vit import _native
     c = parse_config(config_path)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -339,11 +374,18 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight)
     val_criterion = CrossEntropyLoss()
     gstep = session = None
+    per_pass = (n_train // world) // batch_size
+    epoch_steps = min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass
+    control = _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite, epoch_steps * epochs)
     if graph:
         from spectre_vit.optim import FusedAdamW
         optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
-                               static_grads=True)
+                               static_grads=True, **control)
         reducer = None   # the graphed step owns its own (fixed-address) gradient buffer
+    elif control:
+        from spectre_vit.optim import FusedAdamW
+        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True, **control)
+        reducer = GradReducer(model)
     else:
         optimizer = optim.AdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay)  # train.py:307-309
         reducer = GradReducer(model)
@@ -352,8 +394,6 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     gen = torch.Generator().manual_seed(seed)
     best_acc, history = 0.0, []
     global_step = 0
-    per_pass = (n_train // world) // batch_size
-    epoch_steps = min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass
     autocast_dtype = torch.bfloat16 if use_amp else None
     start = time.perf_counter()
     for epoch in range(epochs):
@@ -433,6 +473,8 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
             val_samples = int(stats[1].item())
         rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
                "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
+        if control:
+            rec.update(_step_control_record(optimizer))
         history.append(rec)
         if rank == 0:
             for k, (lt, ld, lc) in enumerate(per_batch):
@@ -472,18 +514,26 @@ def build_parser():
     ap.add_argument("--no-augment", action="store_true", help="--distill-paired: the student's view is ToTensor + Normalize only")
     ap.add_argument("--graph-eval", action="store_true",
                     help="validate through a graph-replayed InferenceSession with on-device metrics (spectre_vit.inference)")
+    ap.add_argument("--lr-schedule", default=None, choices=("cosine",),
+                    help="cosine annealing over steps-per-epoch * epochs steps (train.py:202-203), evaluated on the device every step")
+    ap.add_argument("--warmup-steps", type=int, default=0, help="--lr-schedule cosine: linear warm-up steps in front of the cosine")
+    ap.add_argument("--eta-min", type=float, default=0.0, help="--lr-schedule cosine: the rate the schedule ends at")
+    ap.add_argument("--clip-grad-norm", type=float, default=None, help="clip the global gradient norm (on the device, inside the optimizer step)")
+    ap.add_argument("--skip-nonfinite", action="store_true", help="drop a step whose gradients hold an inf or a NaN (GradScaler's rule)")
     ap.add_argument("--out", default="runs/spectre_vit")
     return ap
 
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
+    control = dict(lr_schedule=a.lr_schedule, warmup_steps=a.warmup_steps, eta_min=a.eta_min, clip_grad_norm=a.clip_grad_norm,
+                   skip_nonfinite=a.skip_nonfinite)
     if a.distill_paired:
         train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out,
-                      graph_eval=a.graph_eval)
+                      graph_eval=a.graph_eval, **control)
         return
     train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph,
-          model=a.model, augment=a.augment, graph_eval=a.graph_eval)
+          model=a.model, augment=a.augment, graph_eval=a.graph_eval, **control)
 
 
 if __name__ == "__main__":

@@ -5,28 +5,101 @@ Same update rule, same ``state`` layout (``step`` / ``exp_avg`` / ``exp_avg_sq``
 interchangeable with torch's), one parameter group or many.  torch's own fused kernel spends 100+ us per step on the FFT
 model's 63 small tensors; ``spv_adamw_multi`` walks a chunk table in a single launch.  ``capturable=True`` keeps the step
 count on the device, so the whole training step can be captured in a HIP graph (spectre_vit/graph.py).
+
+Step control (``schedule=``, ``max_grad_norm=``, ``skip_nonfinite=``): what the reference's loop does on the host around
+``optimizer.step()`` -- ``CosineAnnealingLR`` (train.py:202-203), ``GradScaler``'s dropped step on an inf / NaN gradient
+(train.py:205,236-238), and the usual ``clip_grad_norm_`` -- decided on the device from the step count and the gradient, so a
+replayed graph follows the schedule instead of keeping the captured rate.  Per step: ``spv_grad_sumsq`` per group, one
+``spv_step_control`` that fills a 64-byte control block (include/spv.h: spv_step_ctl), ``spv_adamw_multi_ctl`` per group.
 """
 from __future__ import annotations
 
+import math
+import struct
+
+import numpy as np
 import torch
 
 from spectre_vit import _native
 from spectre_vit.hip_ops import _stream
 
 _CHUNK = 2048
+_CTL_FMT = "<ddfifii28x"   # include/spv.h: spv_step_ctl (a, b, clip_coef, apply, grad_norm, sched_step, skipped, reserved)
+_CTL_SCHEDULE, _CTL_CLIP, _CTL_SKIP = 1, 2, 4
+
+
+class CosineSchedule:
+    """Linear warm-up, then cosine annealing, as a function of the number t of ``step()`` calls made so far (skipped steps count, the
+    way ``scheduler.step()`` sits in a user's loop).  W = warmup_steps, T = total_steps:
+
+        t <  W:  lr = base * (t + 1) / (W + 1)                                        LinearLR(start_factor=1/(W+1), total_iters=W)
+        t >= W:  lr = eta_min + (base - eta_min) * (1 + cos(pi * min(t - W, T - W) / (T - W))) / 2       CosineAnnealingLR(T - W, eta_min)
+
+    i.e. torch's ``SequentialLR([LinearLR, CosineAnnealingLR], milestones=[W])`` for t <= T.  Past T the rate STAYS at eta_min (torch's
+    closed form would rise again).  ``lr_at`` is the float64 definition; the device evaluates the same expressions in fp64 and
+    rounds the rate to fp32 once."""
+
+    def __init__(self, total_steps, warmup_steps=0, eta_min=0.0):
+        total_steps, warmup_steps, eta_min = int(total_steps), int(warmup_steps), float(eta_min)
+        if warmup_steps < 0:
+            raise ValueError(f"CosineSchedule: warmup_steps={warmup_steps} must be >= 0")
+        if total_steps <= warmup_steps:
+            raise ValueError(f"CosineSchedule: total_steps={total_steps} must be larger than warmup_steps={warmup_steps}")
+        if not eta_min >= 0.0:
+            raise ValueError(f"CosineSchedule: eta_min={eta_min} must be >= 0")
+        self.total_steps, self.warmup_steps, self.eta_min = total_steps, warmup_steps, eta_min
+
+    def lr_at(self, t, base_lr):
+        t, base_lr = int(t), float(base_lr)
+        W, T = self.warmup_steps, self.total_steps
+        if t < W:
+            return base_lr * (t + 1) / (W + 1)
+        if t >= T:
+            return self.eta_min
+        return self.eta_min + (base_lr - self.eta_min) * (1.0 + math.cos(math.pi * (t - W) / (T - W))) / 2.0
+
+    def __repr__(self):
+        return f"CosineSchedule(total_steps={self.total_steps}, warmup_steps={self.warmup_steps}, eta_min={self.eta_min})"
 
 
 class FusedAdamW(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False, static_grads=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False, static_grads=False,
+                 schedule=None, max_grad_norm=None, skip_nonfinite=False):
         """static_grads=True: the caller expects fixed gradient addresses (spectre_vit.dp.GradReducer(model, always=True), or a
         captured graph): after two identical look-ups a step only COMPARES the gradient addresses with the table's (one tuple of
         ``p.grad.data_ptr()`` per group, every step: a caller that swapped a ``.grad`` gets a rebuilt table, never a write through a
-        stale pointer) and skips the state walk and the table build -- 0.3 ms of host time per step otherwise."""
+        stale pointer) and skips the state walk and the table build -- 0.3 ms of host time per step otherwise.
+
+        Any of schedule / max_grad_norm / skip_nonfinite switches step() to the on-device control path (needs capturable=True):
+          schedule        a CosineSchedule: a group's rate is the schedule of its ``lr`` (the base rate) at t = step() calls so far.
+                          None: the group's ``lr``, read from param_groups on every eager call (a captured graph keeps the value).
+          max_grad_norm   the update uses g * min(1, max_grad_norm / (norm + 1e-6)), norm = the L2 norm over every gradient of every
+                          group, as torch.nn.utils.clip_grad_norm_ -- but ``p.grad`` is NOT rewritten (the scale is applied in the
+                          optimizer kernel's registers); read the norm with last_grad_norm().
+          skip_nonfinite  a step whose gradients hold an inf or a NaN changes no parameter, no moment and not the Adam step count
+                          (GradScaler.step()'s rule); skipped_steps() counts them and the schedule count still advances.
+        Without skip_nonfinite a non-finite norm under clipping acts as torch's does (NaN weights)."""
         if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError(f"FusedAdamW: invalid hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
+        if schedule is not None and not isinstance(schedule, CosineSchedule):
+            raise ValueError(f"FusedAdamW: schedule must be a spectre_vit.optim.CosineSchedule or None, not {schedule!r}")
+        if max_grad_norm is not None and not float(max_grad_norm) > 0.0:
+            raise ValueError(f"FusedAdamW: max_grad_norm={max_grad_norm} must be > 0")
+        self.schedule = schedule
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        self.step_control = schedule is not None or max_grad_norm is not None or self.skip_nonfinite
+        if self.step_control and not capturable:
+            raise ValueError("FusedAdamW: schedule / max_grad_norm / skip_nonfinite need capturable=True (a skipped step leaves the "
+                             "Adam step count where it is, so the count must live on the device)")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable))
         self.static_grads = bool(static_grads)
         self._tables = {}  # group index -> dict(key, table, chunk_tensor, chunk_off, sizes, nchunks, step_dev)
+        # step control: the device block (spv_step_ctl), the per-chunk fp64 partial sums and the device array of the groups' step
+        # count pointers; built on the first step() -- before any capture -- and again after load_state_dict()
+        self._ctl = None
+        self._ctl_ws = None
+        self._ctl_counts = (0, 0)   # (schedule step, skipped steps) a freshly built block starts from
 
     def _table(self, gi, ps):
         """device-side pointer / chunk tables of one parameter group; rebuilt only when a pointer moved (in the steady state the
@@ -73,6 +146,90 @@ class FusedAdamW(torch.optim.Optimizer):
         for st in self.state.values():
             if isinstance(st.get("step"), torch.Tensor):
                 st["step"] = st["step"].float()
+        if self.step_control:   # the control block is rebuilt by the next step(), from the loaded counters
+            sc = state_dict.get("step_control") or {}
+            self._ctl_counts = (int(sc.get("schedule_step", 0)), int(sc.get("skipped_steps", 0)))
+            self._ctl = self._ctl_ws = None
+
+    def state_dict(self):
+        """torch's layout; with step control on, one more top-level entry carries the schedule count and the skipped count, so that a
+        resumed run continues the curve (a host synchronisation).  Without step control: exactly torch's dict."""
+        sd = super().state_dict()
+        if self.step_control:
+            c = self._read_ctl()
+            sd["step_control"] = dict(schedule_step=c["sched_step"], skipped_steps=c["skipped"])
+        return sd
+
+    # -- step control -------------------------------------------------------------------------------------------------------------
+    def _read_ctl(self):
+        """the control block as the last step() left it (synchronises the host: meant for once an epoch)"""
+        if not self.step_control:
+            raise RuntimeError("FusedAdamW: built without schedule / max_grad_norm / skip_nonfinite: there is no step-control block")
+        return dict(zip(("a", "b", "clip_coef", "apply", "grad_norm", "sched_step", "skipped"),
+                        struct.unpack(_CTL_FMT, self.control_block_bytes())))
+
+    def last_lr(self, _ctl=None):
+        """the rate the last step() used, one float per parameter group: float32(a * lr + b), the kernel's own expression"""
+        c = _ctl or self._read_ctl()
+        return [float(np.float32(np.float64(c["a"]) * np.float64(float(g["lr"])) + np.float64(c["b"]))) for g in self.param_groups]
+
+    def last_grad_norm(self):
+        """the L2 norm over all gradients that the last step() saw (before clipping)"""
+        return self._read_ctl()["grad_norm"]
+
+    def skipped_steps(self):
+        return self._read_ctl()["skipped"]
+
+    def schedule_step(self):
+        """step() calls so far, skipped ones included: the schedule's t of the next step"""
+        return self._read_ctl()["sched_step"]
+
+    def control_block_bytes(self):
+        """the 64 raw bytes of the control block: the device's, or (before the first step) the ones it will start from"""
+        if self._ctl is None:
+            return struct.pack(_CTL_FMT, 1.0, 0.0, 1.0, 1, 0.0, *self._ctl_counts)
+        return self._ctl.cpu().numpy().tobytes()
+
+    def _control_workspace(self, active):
+        """control block, partial-sum workspace and step-pointer array for the groups that step this call; rebuilt (never under capture)
+        when a group's chunk count or step tensor changed"""
+        key = tuple((t["nchunks"], t["step"].data_ptr()) for _, t in active)
+        ws = self._ctl_ws
+        if ws is not None and ws["key"] == key and self._ctl is not None:
+            return ws
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW: the step-control workspace has to be (re)built while a HIP graph is being captured: run a "
+                               "warm-up step() before the capture")
+        dev = active[0][1]["step"].device
+        if self._ctl is None:
+            self._ctl = torch.frombuffer(bytearray(self.control_block_bytes()), dtype=torch.uint8).to(dev)
+        offs, n = [], 0
+        for _, t in active:
+            offs.append(n)
+            n += t["nchunks"]
+        ws = dict(key=key, offs=offs, n=n, partials=torch.zeros(max(n, 1), dtype=torch.float64, device=dev),
+                  step_ptrs=torch.tensor([t["step"].data_ptr() for _, t in active], dtype=torch.int64).to(dev))
+        self._ctl_ws = ws
+        return ws
+
+    def _step_controlled(self, active):
+        ws = self._control_workspace(active)
+        st = _stream()
+        for (_, t), off in zip(active, ws["offs"]):
+            _native.call("spv_grad_sumsq", t["table"].data_ptr(), t["chunk_tensor"].data_ptr(), t["chunk_off"].data_ptr(),
+                         t["sizes"].data_ptr(), t["nchunks"], ws["partials"].data_ptr() + 8 * off, st)
+        sch = self.schedule
+        flags = ((_CTL_SCHEDULE if sch is not None else 0) | (_CTL_CLIP if self.max_grad_norm is not None else 0)
+                 | (_CTL_SKIP if self.skip_nonfinite else 0))
+        # (this launch also advances the groups' Adam step counts -- when the step is applied)
+        _native.call("spv_step_control", ws["partials"].data_ptr(), ws["n"], ws["step_ptrs"].data_ptr(), len(active), self._ctl.data_ptr(),
+                     flags, sch.warmup_steps if sch else 0, sch.total_steps if sch else 0, sch.eta_min if sch else 0.0,
+                     self.max_grad_norm or 0.0, st)
+        for group, t in active:
+            b1, b2 = group["betas"]
+            _native.call("spv_adamw_multi_ctl", t["table"].data_ptr(), t["chunk_tensor"].data_ptr(), t["chunk_off"].data_ptr(),
+                         t["sizes"].data_ptr(), t["nchunks"], float(group["lr"]), float(b1), float(b2), 1.0 - b1, 1.0 - b2,
+                         float(group["eps"]), float(group["weight_decay"]), t["step"].data_ptr(), self._ctl.data_ptr(), st)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -80,6 +237,7 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        active = []   # step control: (group, table) of every group that steps, launched together below
         for gi, group in enumerate(self.param_groups):
             t = self._tables.get(gi)
             b1, b2 = group["betas"]
@@ -114,6 +272,11 @@ class FusedAdamW(torch.optim.Optimizer):
                 # what the fast path compares every step: the gradient address of EVERY parameter of the group (0 = no gradient)
                 t["grad_ptrs"] = tuple(0 if p.grad is None else p.grad.data_ptr() for p in group["params"])
                 t["calls"] = 1
+            if self.step_control:
+                if not group["capturable"]:
+                    raise ValueError("FusedAdamW: step control needs capturable=True in every parameter group")
+                active.append((group, t))
+                continue
             if group["capturable"]:
                 t["step"] += 1.0
                 bc1 = bc2 = 0.0
@@ -126,4 +289,6 @@ class FusedAdamW(torch.optim.Optimizer):
             _native.call("spv_adamw_multi", t["table"].data_ptr(), t["chunk_tensor"].data_ptr(), t["chunk_off"].data_ptr(),
                          t["sizes"].data_ptr(), t["nchunks"], float(group["lr"]), float(b1), float(b2), 1.0 - b1, 1.0 - b2,
                          float(group["eps"]), float(group["weight_decay"]), bc1, bc2, step_ptr, _stream())
+        if active:
+            self._step_controlled(active)
         return loss
