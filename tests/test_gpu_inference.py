@@ -248,7 +248,7 @@ def test_padding_rows_do_not_reach_the_valid_rows(mixer):
 def test_outputs_change_only_at_refresh(mixer):
     """a test of values: after an optimizer step, a replaced weight-copy cache (as GraphedTrainStep._warm does), a collection and fresh
     allocations over whatever was freed, the session still returns its old output bit for bit; after refresh() the new weights'"""
-    from spectre_vit import hip_ops
+    from spectre_vit import shadows
     m, cfg, img, labels = fixture_model(mixer)
     dtype = torch.bfloat16
     eager(m, img, dtype)   # (the eager cache holds copies of the weights, as in a run that validated eagerly before)
@@ -262,7 +262,7 @@ def test_outputs_change_only_at_refresh(mixer):
     loss.backward()
     opt.step()
     opt.zero_grad(set_to_none=True)
-    hip_ops._shadows = type(hip_ops._shadows)()
+    shadows.reset_shadow_cache()
     gc.collect()
     total = sum(p.numel() for p in m.parameters())
     junk = [torch.full((total,), 1e4, device=dev()) for _ in range(3)] + [torch.full((total,), 1e4, device=dev(), dtype=torch.bfloat16)

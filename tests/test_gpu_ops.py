@@ -1030,3 +1030,68 @@ def test_fnet_cls_row_matches_the_full_node(dtype, shape):
     assert rel(out.detach(), ref.detach()) < tol
     assert rel(xd.grad, x64.grad) < tol
     assert rel(wd.grad, w64.grad) < tol and rel(bd.grad, b64.grad) < tol
+
+
+# ------------------------------------------------------------------------------------------------ weight shadows
+def test_weight_shadow_providers_agree_with_torch_casts():
+    """The three providers of (W, W^T padded to 8 columns) -- _ShadowCache.get on a cold cache (one launch per weight), a ShadowSet and
+    a PinnedShadows (one spv_weight_shadows_multi launch over a table of 32 x 64 tiles) -- against torch's own casts, exactly: both
+    round to nearest even.  Shapes: (100, 64) has ld = 104 (four tile rows, the last partial), (8, 200) four tile columns, the last
+    partial, in one tile row, (768, 512) is a layer weight (24 x 8 tiles).  Columns n..ld of W^T are padding and not compared."""
+    from spectre_vit import _native, shadows
+    bf16, f32 = torch.bfloat16, torch.float32
+    g = torch.Generator().manual_seed(7)
+    ws = [torch.randn(s, generator=g).to(dev()) for s in ((100, 64), (8, 200), (768, 512))]
+
+    def expect(pairs, dtype, who):
+        for w, (wc, wt) in zip(ws, pairs):
+            n, k = w.shape
+            assert wc.dtype == dtype and wt.dtype == dtype and tuple(wc.shape) == (n, k) and tuple(wt.shape) == (k, (n + 7) // 8 * 8), who
+            assert torch.equal(wc, w.to(dtype)), f"{who}: W {tuple(w.shape)} {dtype}"
+            assert torch.equal(wt[:, :n], w.t().to(dtype)), f"{who}: W^T {tuple(w.shape)} {dtype}"
+            if dtype == f32:
+                assert wc.data_ptr() == w.data_ptr(), f"{who}: the fp32 copy must be the weight's own storage"
+
+    launches = []
+    orig = _native.call
+
+    def spy(name, *a):
+        if name == "spv_weight_shadows":
+            launches.append(name)
+        return orig(name, *a)
+    _native.call = spy
+    try:
+        with torch.no_grad():
+            shadows.reset_shadow_cache()
+            for dtype in (bf16, f32):
+                expect([shadows._shadows.get(w, dtype) for w in ws], dtype, "cache")
+            assert len(launches) == 6
+            shadows._shadows.get(ws[0], bf16)   # outside training a current entry is reused
+            assert len(launches) == 6
+            shadows.reset_shadow_cache()
+            shadows._shadows.get(ws[0], bf16)
+            assert len(launches) == 7, "a reset cache must cast the weight again"
+            shadows.reset_shadow_cache()
+    finally:
+        _native.call = orig
+    sset = shadows.ShadowSet(ws)
+    sset.refresh()
+    expect(sset.bufs, bf16, "set")
+    pinned = shadows.PinnedShadows()
+    seen = {dtype: [pinned.get(w, dtype) for w in ws] for dtype in (bf16, f32)}
+    pinned.refresh()
+    for dtype in (bf16, f32):
+        expect(seen[dtype], dtype, "pinned")
+    addresses = [[(wc.data_ptr(), wt.data_ptr()) for wc, wt in pairs] for pairs in (sset.bufs, seen[bf16], seen[f32])]
+    with torch.no_grad():
+        for w in ws:
+            w.mul_(-1.5).add_(0.25)
+    sset.refresh()
+    pinned.refresh()
+    expect(sset.bufs, bf16, "set, new values")
+    for dtype in (bf16, f32):
+        again = [pinned.get(w, dtype) for w in ws]
+        expect(again, dtype, "pinned, new values")
+    assert addresses == [[(wc.data_ptr(), wt.data_ptr()) for wc, wt in pairs]
+                         for pairs in (sset.bufs, [pinned.get(w, bf16) for w in ws], [pinned.get(w, f32) for w in ws])]
+    shadows.reset_shadow_cache()   # (the set's refresh left "fresh" entries for these weights)

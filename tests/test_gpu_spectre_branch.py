@@ -62,11 +62,11 @@ def np_pool_matrix(L, T):
 @pytest.mark.parametrize("shape", [(3, 3, 32, 32), (2, 1, 28, 28), (2, 3, 17, 9)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_spectrum_log1p(shape, dtype):
-    from spectre_vit import hip_ops
+    from spectre_vit import branch_ops
     x = np.random.default_rng(sum(shape)).standard_normal(shape).astype(np.float32)
     ref = np.log1p(np.abs(np.fft.rfft2(x.astype(np.float64), axes=(-2, -1)))).transpose(0, 2, 3, 1)
     before = count("spectrum")
-    y = hip_ops.spectrum_log1p(t(x), dtype)
+    y = branch_ops.spectrum_log1p(t(x), dtype)
     assert count("spectrum") == before + 1
     assert y.shape == ref.shape and y.dtype == dtype
     if dtype == torch.float32:
@@ -76,15 +76,15 @@ def test_spectrum_log1p(shape, dtype):
 
 
 def test_spectrum_refuses_image_gradients():
-    from spectre_vit import hip_ops
+    from spectre_vit import branch_ops
     with pytest.raises(RuntimeError, match="no backward"):
-        hip_ops.spectrum_log1p(torch.randn(1, 3, 8, 8, device=dev(), requires_grad=True))
+        branch_ops.spectrum_log1p(torch.randn(1, 3, 8, 8, device=dev(), requires_grad=True))
 
 
 @pytest.mark.parametrize("cin,H,W,cout", [(c, h, w, 3 * c) for c, h, w in STAGES] + [(1, 5, 4, 5)])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_conv3x3_fwd_dgrad_wgrad(cin, H, W, cout, dtype):
-    from spectre_vit import hip_ops
+    from spectre_vit import branch_ops
     rng = np.random.default_rng(cin * 100 + H)
     B = 3
     x = rng.standard_normal((B, H, W, cin)).astype(np.float32)
@@ -95,9 +95,9 @@ def test_conv3x3_fwd_dgrad_wgrad(cin, H, W, cout, dtype):
         x, w, dy = bf(x), bf(w), bf(dy)
     xt, wt, bt, dyt = t(x, dtype), t(w), t(b), t(dy, dtype)
     c0 = (count("conv_fwd"), count("conv_dgrad"), count("conv_wgrad"))
-    y = hip_ops.conv3x3_fwd(xt, wt, bt)
-    dx = hip_ops.conv3x3_dgrad(dyt, wt)
-    dw = hip_ops.conv3x3_wgrad(dyt, xt)
+    y = branch_ops.conv3x3_fwd(xt, wt, bt)
+    dx = branch_ops.conv3x3_dgrad(dyt, wt)
+    dw = branch_ops.conv3x3_wgrad(dyt, xt)
     assert (count("conv_fwd"), count("conv_dgrad"), count("conv_wgrad")) == (c0[0] + 1, c0[1] + 1, c0[2] + 1)
     x64, w64, dy64 = x.astype(np.float64), w.astype(np.float64), dy.astype(np.float64)
     refs = dict(y=np_conv(x64, w64, b), dx=np_conv_dgrad(dy64, w64), dw=np_conv_wgrad(dy64, x64))
@@ -113,7 +113,7 @@ def test_conv3x3_fwd_dgrad_wgrad(cin, H, W, cout, dtype):
 @pytest.mark.parametrize("L", [450, 364, 286, 216, 65, 64, 40])
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 def test_token_pool_fwd_bwd(L, dtype):
-    from spectre_vit import hip_ops
+    from spectre_vit import branch_ops
     rng = np.random.default_rng(L)
     B, C, T, ldo = 2, 7, 65, 8
     y = rng.standard_normal((B, L, C)).astype(np.float32)
@@ -123,9 +123,9 @@ def test_token_pool_fwd_bwd(L, dtype):
         y, dout, add = bf(y), bf(dout), bf(add)
     P = np_pool_matrix(L, T)
     before = (count("token_pool"), count("token_unpool"))
-    out = hip_ops.token_pool_fwd(t(y, dtype), T, ldo)
-    dy = hip_ops.token_pool_bwd(t(dout, dtype), L, C)
-    dya = hip_ops.token_pool_bwd(t(dout, dtype), L, C, t(add, dtype))
+    out = branch_ops.token_pool_fwd(t(y, dtype), T, ldo)
+    dy = branch_ops.token_pool_bwd(t(dout, dtype), L, C)
+    dya = branch_ops.token_pool_bwd(t(dout, dtype), L, C, t(add, dtype))
     assert (count("token_pool"), count("token_unpool")) == (before[0] + 1, before[1] + 2)
     ref = np.einsum("tl,blc->btc", P, y.astype(np.float64))
     dref = np.einsum("tl,btc->blc", P, dout[..., :C].astype(np.float64))

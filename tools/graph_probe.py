@@ -10,7 +10,7 @@ sys.path.insert(0, ROOT)
 import torch  # noqa: E402
 
 from bench import SMALL  # noqa: E402
-from spectre_vit import hip_ops  # noqa: E402
+from spectre_vit import shadows  # noqa: E402
 from spectre_vit.models.spectre.spectre import SpectreViT  # noqa: E402
 
 
@@ -52,7 +52,7 @@ def main():
         for _ in range(3):
             step()
     torch.cuda.current_stream().wait_stream(s)
-    hip_ops._shadows = type(hip_ops._shadows)()  # force the weight casts to be recorded
+    shadows.reset_shadow_cache()  # force the weight casts to be recorded
     g = torch.cuda.CUDAGraph()
     opt.zero_grad(set_to_none=True)
     with torch.cuda.graph(g):

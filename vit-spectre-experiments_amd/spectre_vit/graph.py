@@ -35,7 +35,7 @@ import weakref
 
 import torch
 
-from spectre_vit import _native, hip_ops
+from spectre_vit import _native, hip_ops, shadows
 from spectre_vit.dp import GradReducer
 
 _seed_owner = None   # weakref to the live step object whose seed word the library's dropout kernels read
@@ -134,7 +134,7 @@ class GraphedTrainStep:
         # the warm-up steps are REAL training steps on the example batch: a caller that feeds the example batch as its first batch
         # takes the last one's results from here instead of replaying that batch a second time
         self.warm_loss, self.warm_out = loss.detach(), out.detach()
-        hip_ops._shadows = type(hip_ops._shadows)()  # the weight casts must be recorded in the graph, not served from a cache
+        shadows.reset_shadow_cache()  # the weight casts must be recorded in the graph, not served from a cache
 
     def _build(self, warmup):
         self._warm(warmup)
@@ -155,8 +155,8 @@ class GraphedTrainStep:
         self._replay()
         self.replays += 1
         # the replay updated the weights through raw pointers: neither the parameters' version counters nor the optimizer's post-step
-        # hook saw it, so the inference-time cache of bf16 weight copies (hip_ops._ShadowCache) must be told
-        hip_ops.invalidate_weight_shadows()
+        # hook saw it, so the inference-time cache of bf16 weight copies (shadows._ShadowCache) must be told
+        shadows.invalidate_weight_shadows()
         return self.loss
 
     def close(self):

@@ -3,58 +3,28 @@
 Host-side mirror of the arithmetic the reference modules issue as stock ATen ops; every Function
 borrows ``data_ptr()``s, launches on torch's current HIP stream and never synchronises.  Tensors must be
 on a HIP device: a CPU tensor raises (there is deliberately no CPU / eager-PyTorch fallback).
+
+  _launch.py     dtype codes, raw pointers, the current stream's handle, the device check
+  shadows.py     the compute-dtype copies of the weights (_ShadowCache, ShadowSet, PinnedShadows)
+  timing.py      KernelTimer and the work model of every entry point (bench.py's roofline pass)
+  branch_ops.py  the SpectreBranch ops
+  hip_ops.py     the GEMM and weight-gradient dispatch, the held launches of the backward pass, GradSink, the Functions, the flags
 """
 from __future__ import annotations
 
 import collections
-import contextlib
 import ctypes
 import os
 import warnings
 import weakref
+from typing import NamedTuple
 
 import torch
 
-from . import _native
-
-F32, BF16 = 0, 1
-_DT = {torch.float32: F32, torch.bfloat16: BF16}
-
-
-_raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-
-
-def _stream():
-    """raw HIP handle of torch's current stream on the current device (the C getter: torch.cuda.current_stream() builds a Python
-    Stream object per call -- 10 us, 38 times per training step)"""
-    if _raw_stream is not None:
-        return _raw_stream(torch.cuda.current_device())
-    return torch.cuda.current_stream().cuda_stream
-
-
-def _p(t):
-    return 0 if t is None else t.data_ptr()
-
-
-def _dt(t):
-    try:
-        return _DT[t.dtype]
-    except KeyError:
-        raise TypeError(f"libspv_hip kernels take float32 or bfloat16 tensors, got {t.dtype}") from None
-
-
-def _require_gpu(*tensors):
-    """every tensor on a HIP device, and on the CURRENT one: kernels are launched on torch.cuda.current_stream(), which belongs
-    to the current device -- raw pointers of another GPU on that stream would fault or run unordered."""
-    for t in tensors:
-        if t is None:
-            continue
-        if not t.is_cuda:
-            raise RuntimeError("Spectre-ViT HIP kernels need tensors on an AMD GPU (cuda/HIP device); "
-                               "there is no CPU fallback in this package")
-        if t.device.index != torch.cuda.current_device():
-            raise RuntimeError(f"tensor on {t.device} but the current device is cuda:{torch.cuda.current_device()}: call "
-                               "torch.cuda.set_device(local_rank) (or use `with torch.cuda.device(...)`) before the model runs")
+from . import _native, shadows
+from ._launch import _DT, BF16, F32, _dt, _p, _require_gpu, _stream  # noqa: F401  (tools/ and tests read them here)
+from .shadows import invalidate_weight_shadows  # noqa: F401  (the documented name: INTEGRATION.md)
+from .timing import KernelTimer, _timing, set_kernel_timer  # noqa: F401  (bench.py reads the timer here)
 
 
 _warned_fp16 = False
@@ -105,351 +75,6 @@ class _Cast(torch.autograd.Function):
         return _raw_cast(g, ctx.src), None
 
 
-# ------------------------------------------------------------------------------------------------
-# weight shadows: compute-dtype copy of W and of W^T, rebuilt only when the parameter changes
-# ------------------------------------------------------------------------------------------------
-class _ShadowCache:
-    """(weight tensor, dtype) -> (W in dtype, W^T in dtype, padded to 8 columns).
-
-    While a weight is being trained (grad mode on, requires_grad) the shadows are rebuilt at every forward: optimizers may
-    update parameters without touching the tensor's version counter -- ``torch.optim.AdamW(fused=True)`` does exactly that --
-    so no cheap test can prove a cached copy current, and a stale copy would silently freeze the layer.  Outside training
-    (eval / no_grad inference loops) entries are reused, validated by a weak reference to the parameter (ids and addresses
-    are recycled once a tensor dies), its version counter and the global optimizer-step epoch."""
-
-    def __init__(self):
-        self._d = {}
-        self._fresh = {}
-        self.epoch = 0
-
-    def get(self, w: torch.Tensor, dtype: torch.dtype):
-        if _pinned is not None:   # an InferenceSession's forward: its own fixed buffers, never this cache's
-            return _pinned.get(w, dtype)
-        key = (id(w), dtype)
-        ent = self._d.get(key)
-        ver = (w.data_ptr(), w._version, tuple(w.shape), self.epoch)
-        training = torch.is_grad_enabled() and w.requires_grad
-        if not training and ent is not None and ent[0]() is w and ent[1] == ver:
-            return ent[2], ent[3]
-        fresh = self._fresh.pop(key, None)
-        # rebuilt for THIS forward by refresh_weight_shadows (one launch for all weights); void if an optimizer has stepped since
-        if fresh is not None and fresh[0]() is w and fresh[3] == (w._version, self.epoch):
-            return fresh[1], fresh[2]
-        n, k = w.shape
-        wd = w.detach()
-        wc = wd if dtype == torch.float32 else torch.empty((n, k), dtype=dtype, device=w.device)
-        ldt = (n + 7) // 8 * 8
-        wt = torch.empty((k, ldt), dtype=dtype, device=w.device)
-        _native.call("spv_weight_shadows", _p(wd), 0 if wc is wd else _p(wc), _p(wt), n, k, ldt, _DT[dtype], _stream())
-        if len(self._d) > 1024:
-            self._d = {kk: e for kk, e in self._d.items() if e[0]() is not None}
-        self._d[key] = (weakref.ref(w), ver, wc, wt)
-        return wc, wt
-
-
-_shadows = _ShadowCache()
-
-
-class ShadowSet:
-    """Persistent bf16 (W, W^T) copies of a fixed list of fp32 nn.Linear weights, rebuilt by ONE spv_weight_shadows_multi launch
-    per training forward (eight 4.9-us launches and sixteen allocations per step otherwise).  The copies are handed to the layers
-    through _ShadowCache.get, which consumes them once per weight and forward."""
-
-    def __init__(self, weights, dtype=torch.bfloat16):
-        self.weights = [weakref.ref(w) for w in weights]
-        self.dtype = dtype
-        self.key = tuple((w.data_ptr(), tuple(w.shape)) for w in weights)
-        dev = weights[0].device
-        rows, tt, tx, ty = [], [], [], []
-        self.bufs = []
-        for i, w in enumerate(weights):
-            n, k = w.shape
-            ld = (n + 7) // 8 * 8
-            wc = torch.empty((n, k), dtype=dtype, device=dev)
-            wt = torch.empty((k, ld), dtype=dtype, device=dev)
-            self.bufs.append((wc, wt))
-            rows += [w.data_ptr(), wc.data_ptr(), wt.data_ptr(), n | (k << 32), ld]  # {src, plain, tr, (rows, cols), (ld, pad)}
-            for by in range((ld + 31) // 32):
-                for bx in range((k + 63) // 64):
-                    tt.append(i)
-                    tx.append(bx)
-                    ty.append(by)
-        self.table = torch.tensor(rows, dtype=torch.int64).to(dev)
-        self.tt = torch.tensor(tt, dtype=torch.int32).to(dev)
-        self.tx = torch.tensor(tx, dtype=torch.int32).to(dev)
-        self.ty = torch.tensor(ty, dtype=torch.int32).to(dev)
-        self.ntiles = len(tt)
-
-    def refresh(self):
-        _native.call("spv_weight_shadows_multi", self.table.data_ptr(), self.tt.data_ptr(), self.tx.data_ptr(), self.ty.data_ptr(),
-                     self.ntiles, _DT[self.dtype], _stream())
-        for wr, (wc, wt) in zip(self.weights, self.bufs):
-            w = wr()
-            if w is not None:
-                _shadows._fresh[(id(w), self.dtype)] = (wr, wc, wt, (w._version, _shadows.epoch))
-
-
-class PinnedShadows:
-    """(W, W^T) copies at FIXED addresses, owned by one spectre_vit.inference.InferenceSession.  While the session's forward runs
-    (``with pinned_shadows(p):`` -- warm-up and capture) every ``_ShadowCache.get`` is served from here: the eager warm-up allocates
-    and fills a weight's copies on first sight, the capture then finds them and launches nothing, so a replay neither casts a weight
-    nor reads memory that ``invalidate_weight_shadows`` or a replaced cache object could free.  ``refresh()`` recasts every copy in
-    place with one spv_weight_shadows_multi launch per dtype."""
-
-    def __init__(self):
-        self.ent = {}      # (id(w), dtype) -> (w, W in dtype, W^T in dtype); w is held: the session owns the weights it reads
-        self._tables = {}  # dtype -> (entries, table, tile tensors, tiles)
-
-    def get(self, w, dtype):
-        key = (id(w), dtype)
-        e = self.ent.get(key)
-        if e is not None and e[0] is w:
-            return e[1], e[2]
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("a weight asked for its compute-dtype copies for the first time inside a graph capture: the warm-up "
-                               "forward must run the very launch sequence that is captured")
-        n, k = w.shape
-        wd = w.detach()
-        wc = wd if dtype == torch.float32 else torch.empty((n, k), dtype=dtype, device=w.device)
-        ldt = (n + 7) // 8 * 8
-        wt = torch.empty((k, ldt), dtype=dtype, device=w.device)
-        _native.call("spv_weight_shadows", _p(wd), 0 if wc is wd else _p(wc), _p(wt), n, k, ldt, _DT[dtype], _stream())
-        self.ent[key] = (w, wc, wt)
-        return wc, wt
-
-    def _table(self, dtype):
-        ents = [e for (_, dt), e in self.ent.items() if dt == dtype]
-        t = self._tables.get(dtype)
-        if t is not None and t[0] == len(ents):
-            return t
-        dev = ents[0][0].device
-        rows, tt, tx, ty = [], [], [], []
-        for i, (w, wc, wt) in enumerate(ents):
-            n, k = w.shape
-            ld = wt.shape[1]
-            rows += [w.data_ptr(), 0 if wc.data_ptr() == w.data_ptr() else wc.data_ptr(), wt.data_ptr(), n | (k << 32), ld]
-            for by in range((ld + 31) // 32):
-                for bx in range((k + 63) // 64):
-                    tt.append(i)
-                    tx.append(bx)
-                    ty.append(by)
-        t = (len(ents), torch.tensor(rows, dtype=torch.int64).to(dev), torch.tensor(tt, dtype=torch.int32).to(dev),
-             torch.tensor(tx, dtype=torch.int32).to(dev), torch.tensor(ty, dtype=torch.int32).to(dev), len(tt))
-        self._tables[dtype] = t
-        return t
-
-    def refresh(self):
-        for dtype in {dt for _, dt in self.ent}:
-            _, table, tt, tx, ty, ntiles = self._table(dtype)
-            _native.call("spv_weight_shadows_multi", table.data_ptr(), tt.data_ptr(), tx.data_ptr(), ty.data_ptr(), ntiles, _DT[dtype],
-                         _stream())
-
-
-_pinned = None
-
-
-@contextlib.contextmanager
-def pinned_shadows(p):
-    global _pinned
-    prev, _pinned = _pinned, p
-    try:
-        yield p
-    finally:
-        _pinned = prev
-
-
-def refresh_weight_shadows(module, weights_fn):
-    """called at the top of a model's bf16 training forward: module._spv_shadow_set is (re)built when a weight moved or changed shape"""
-    weights = weights_fn()
-    if not weights:
-        return
-    ss = getattr(module, "_spv_shadow_set", None)
-    key = tuple((w.data_ptr(), tuple(w.shape)) for w in weights)
-    if ss is None or ss.key != key:
-        if torch.cuda.is_current_stream_capturing():
-            return  # (tables cannot be uploaded inside a capture: the per-weight path serves this forward)
-        ss = ShadowSet(weights)
-        object.__setattr__(module, "_spv_shadow_set", ss)
-    ss.refresh()
-
-
-def invalidate_weight_shadows(*_args, **_kwargs):
-    """Drop every cached bf16 / transposed weight copy (needed only after updating weights in place, outside autograd's
-    view, between two no_grad forwards).  Registered as a global optimizer post-step hook."""
-    _shadows.epoch += 1
-
-
-from torch.optim.optimizer import register_optimizer_step_post_hook as _register_post_step  # noqa: E402
-
-_register_post_step(invalidate_weight_shadows)  # any torch optimizer's step() invalidates the inference-time cache
-
-
-# ------------------------------------------------------------------------------------------------
-# live kernel timing for bench.py's roofline block: HIP events recorded on the launch stream around EVERY C-ABI entry
-# point that launches (hooked in _native.call; torch.cuda.Event records on torch's current stream == the stream we launch on)
-# ------------------------------------------------------------------------------------------------
-PEAK_TFLOPS = {BF16: 2500.0, F32: 157.3}  # dense MFMA peaks, /opt/skills/guides/MI355X_MICROARCH.md
-PEAK_HBM_GBS = 8000.0
-
-
-def _es(dt):
-    return 2 if dt == BF16 else 4
-
-
-# entry point -> f(ints) -> (label, shape, dtype code, bound, algorithmic work per call: flops (mfma) or compulsory bytes (hbm)).
-# ints are the integer arguments of the C-ABI call in header order (include/spv.h).
-_WORK_MODELS = {
-    "spv_small_sl_fwd": lambda i: ("head_fwd", i[2:5], i[5], "mfma", 2.0 * i[2] * i[3] * i[4]),
-    "spv_small_sl_bwd": lambda i: ("head_bwd", i[0:3], i[3], "mfma", 4.0 * i[0] * i[1] * i[2]),
-    "spv_cross_entropy_fwd": lambda i: ("cross_entropy_fwd", i[0:2], F32, "hbm", i[0] * i[1] * 4.0),
-    "spv_cross_entropy_bwd": lambda i: ("cross_entropy_bwd", i[0:2], F32, "hbm", i[0] * i[1] * 8.0),
-    # student + teacher logits read (forward), read + the gradient written (backward)
-    "spv_distill_loss_fwd": lambda i: ("distill_loss_fwd", i[0:2], F32, "hbm", i[0] * i[1] * 8.0),
-    "spv_distill_loss_bwd": lambda i: ("distill_loss_bwd", i[0:2], F32, "hbm", i[0] * i[1] * 12.0),
-    # (batch, n_src, chans, n, resize, crop, dtype): the uint8 images read, the cropped view written once
-    "spv_teacher_view_u8": lambda i: ("teacher_view", (i[0], i[2], i[3], i[5]), i[6], "hbm",
-                                      1.0 * i[0] * i[2] * (i[3] * i[3] + i[5] * i[5] * _es(i[6]))),
-    "spv_gemm_nt": lambda i: ("gemm_acc" if i[8] else "gemm", i[0:3], i[6], "mfma", 2.0 * i[0] * i[1] * i[2]),
-    "spv_gemm_nt_grouped_rows": lambda i: ("gemm_grouped_rows", i[0:3], i[6], "mfma", 2.0 * i[0] * i[1] * i[2]),
-    "spv_gemm_nt_grouped_rows_drop": lambda i: ("gemm_grouped_rows", i[0:3], i[6], "mfma", 2.0 * i[0] * i[1] * i[2]),
-    "spv_gemm_nt_pool_bwd": lambda i: ("gemm_pool_bwd", i[1:4], i[7], "mfma", 2.0 * i[1] * i[2] * i[3]),
-    "spv_gemm_tn": lambda i: ("gemm_tn", i[0:3], BF16, "mfma", 2.0 * i[0] * i[1] * i[2]),
-    "spv_gemm_tn_fold": lambda i: ("gemm_tn", i[0:3], BF16, "mfma", 2.0 * i[0] * i[1] * i[2]),
-    # (nprob, rows, splits, nfolds, part): the batched weight gradients; the work comes as the caller's hint (sum of 2 m n rows / the
-    # slabs read + the sums written)
-    "spv_gemm_tn_batch_part": lambda i: (("gemm_tn_batch", i[0:3], BF16, "mfma", float(i[-1])) if i[4] == 1 else
-                                         ("splitk_reduce_batch", i[0:4], F32, "hbm", float(i[-1]))),
-    # token-gradient pass of the embedding: read dtok, write the masked copy (when asked for: pointer 2)
-    "spv_embed_bwd": lambda i: ("embed_bwd", i[0:3], i[3], "hbm", 1.0 * i[0] * i[1] * i[2] * _es(i[3]) * (1 if (i[-2] >> 2) & 1 else 2)),
-    "spv_fnet_cls_fwd": lambda i: ("fnet_cls_fwd", i[0:3], i[3], "hbm", 1.0 * i[0] * (i[1] + 1) * i[2] * _es(i[3])),
-    "spv_fnet_cls_bwd": lambda i: ("fnet_cls_bwd", i[0:3], i[3], "hbm", 1.0 * i[0] * (i[1] + 1) * i[2] * _es(i[3])),
-    # one gathered row (n values) + row 0 (embed values) per image, read and written
-    "spv_permut_row0_fwd": lambda i: ("permut_row0_fwd", i[0:4], i[4], "hbm", 2.0 * i[0] * (i[2] + i[3]) * _es(i[4])),
-    # the dense input gradient [batch, d] written once (+ the n + embed values read)
-    "spv_permut_row0_bwd": lambda i: ("permut_row0_bwd", i[0:4], i[4], "hbm", 1.0 * i[0] * (i[1] + i[2] + i[3]) * _es(i[4])),
-    # (B, C, H, W, patch, K, mode, dtype): read the fp32 image, write the patch / token-row matrix
-    "spv_patchify": lambda i: ("patchify", i[0:5], i[7], "hbm",
-                               1.0 * i[0] * i[1] * i[2] * i[3] * 4 + 1.0 * i[0] * ((i[2] // i[4]) * (i[3] // i[4]) + (i[6] == 2)) * i[5] * _es(i[7])),
-    # 32 x 64 tiles: fp32 read, two bf16 copies written
-    "spv_weight_shadows_multi": lambda i: ("weight_shadows_multi", i[0:1], i[1], "hbm", 2048.0 * i[0] * (4 + 2 * _es(i[1]))),
-    # read h [rows,n] + x [rows,k], write out [rows,n]
-    "spv_spectre_tail_fwd": lambda i: ("tail_fwd", i[0:3], i[3], "hbm", i[0] * (2.0 * i[1] + i[2]) * _es(i[3])),
-    # read dout, h; write dh [rows,n] and -- unless the caller passes no dx (MHPermutMix: the pooled skip gradient is added by the data
-    # gradient GEMM's epilogue instead; pointer 7 of the call is NULL then) -- dx_pool [rows,k]
-    "spv_spectre_tail_bwd": lambda i: ("tail_bwd" if not (i[-2] >> 7) & 1 else "tail_bwd_nodx", i[0:3], i[3], "hbm",
-                                       i[0] * (3.0 * i[1] + (0 if (i[-2] >> 7) & 1 else i[2])) * _es(i[3])),
-    # + read dx_add and up_src [rows,k]
-    "spv_spectre_tail_bwd_up": lambda i: ("tail_bwd_up", i[0:3], i[3], "hbm", i[0] * (3.0 * i[1] + 3.0 * i[2]) * _es(i[3])),
-    # read h3, res [rows,n], x [rows,k]; write f3, out2 [rows,n]
-    "spv_spectre_tail_ln_fwd": lambda i: ("tail_ln_fwd", i[0:3], i[3], "hbm", i[0] * (4.0 * i[1] + i[2]) * _es(i[3])),
-    # read dout2, f3, res, h3; write ds, dh3 [rows,n]
-    "spv_spectre_tail_ln_bwd": lambda i: ("tail_ln_bwd", i[0:3], i[3], "hbm", i[0] * 6.0 * i[1] * _es(i[3])),
-    "spv_add_layernorm_fwd": lambda i: ("addln_fwd", i[0:2], i[3], "hbm", 3.0 * i[0] * i[1] * _es(i[3])),
-    "spv_add_layernorm_bwd": lambda i: ("addln_bwd", i[0:2], i[3], "hbm", (3.0 + (i[2] == 1)) * i[0] * i[1] * _es(i[3])),
-    "spv_permut_gather_fwd": lambda i: ("gather_fwd", i[1:4], i[4], "hbm", i[1] * i[3] * (1.0 + i[2]) * _es(i[4])),
-    "spv_permut_gather_bwd": lambda i: ("gather_bwd", i[0:3], i[3], "hbm", i[0] * i[2] * (1.0 + i[1]) * _es(i[3])),
-    "spv_fnet_mix": lambda i: ("fnet_mix", i[0:3], i[3], "hbm", 2.0 * i[0] * i[1] * i[2] * _es(i[3])),
-    # mixer + LayerNorm-1 + residual: read x, write the pre-norm tensor and x1
-    "spv_fnet_ln_fwd": lambda i: ("fnet_ln_fwd", i[0:3], i[3], "hbm", 3.0 * i[0] * i[1] * i[2] * _es(i[3])),
-    # read dout and the pre-norm tensor, write dx
-    "spv_fnet_ln_bwd": lambda i: ("fnet_ln_bwd", i[0:3], i[3], "hbm", 3.0 * i[0] * i[1] * i[2] * _es(i[3])),
-    "spv_haar_ln_fwd": lambda i: ("haar_ln_fwd", i[0:2], i[2], "hbm", 2.0 * i[0] * i[1] * _es(i[2])),
-    "spv_haar_ln_bwd": lambda i: ("haar_ln_bwd", i[0:2], i[2], "hbm", 3.0 * i[0] * i[1] * _es(i[2])),
-    "spv_haar_dwt": lambda i: ("haar_dwt", i[0:3], i[6], "hbm", 2.0 * i[0] * i[1] * i[2] * _es(i[6])),
-    # p, g, m, v read + p, m, v written, 2048 elements per workgroup (the last chunk of a tensor is short: an upper bound)
-    "spv_adamw_multi": lambda i: ("adamw_multi", i[0:1], F32, "hbm", 7.0 * 4 * 2048 * i[0]),
-    # step control: the gradient read once (chunks as above), the per-chunk fp64 partials folded, the optimizer's seven streams
-    "spv_grad_sumsq": lambda i: ("grad_sumsq", i[0:1], F32, "hbm", 4.0 * 2048 * i[0]),
-    "spv_step_control": lambda i: ("step_control", i[0:2], F32, "hbm", 8.0 * i[0] + 64),
-    "spv_adamw_multi_ctl": lambda i: ("adamw_multi_ctl", i[0:1], F32, "hbm", 7.0 * 4 * 2048 * i[0]),
-    "spv_weight_shadows": lambda i: ("weight_shadows", i[0:2], i[3], "hbm", i[0] * i[1] * (4.0 + 2 * _es(i[3]))),
-    "spv_dropout": lambda i: ("dropout", i[0:1], i[1], "hbm", 2.0 * i[0] * _es(i[1])),
-    "spv_axpby": lambda i: ("axpby", i[0:1], i[1], "hbm", 3.0 * i[0] * _es(i[1])),
-    "spv_colsum": lambda i: ("colsum", i[0:2], i[2], "hbm", 1.0 * i[0] * i[1] * _es(i[2])),
-    "spv_cast": lambda i: ("cast", i[2:3], i[1], "hbm", 1.0 * i[2] * (_es(i[0]) + _es(i[1]))),
-}
-
-
-class KernelTimer:
-    def __init__(self):
-        self.records = []  # (name, key, start, end)
-        self.empties = []  # empty pairs recorded BETWEEN the kernel brackets, i.e. with the queue as busy as it is around them
-        self.overhead_s = 0.0
-        self.passes = 0    # steps recorded (bench.py counts them: per-step totals = totals / passes)
-
-    def bracket(self, name, key, launch):
-        e0 = torch.cuda.Event(enable_timing=True)
-        e1 = torch.cuda.Event(enable_timing=True)
-        e0.record()
-        launch()
-        e1.record()
-        self.records.append((name, key, e0, e1))
-        if len(self.records) % 8 == 0:
-            z0, z1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            z0.record()
-            z1.record()
-            self.empties.append((z0, z1))
-
-    def _groups(self):
-        torch.cuda.synchronize()
-        if self.empties:
-            # what a bracket adds to the kernel's own duration: the median of the empty pairs taken inside the pass (a pair on an
-            # idle stream read 5-13 us depending on the box; the in-pass median agrees with rocprofv3's durations)
-            self.overhead_s = sorted(a.elapsed_time(b) for a, b in self.empties)[len(self.empties) // 2] * 1e-3
-            self.empties = []
-        groups = {}
-        for name, key, e0, e1 in self.records:
-            g = groups.setdefault((name, key), [0, 0.0])
-            g[0] += 1
-            # the raw bracket: NOT reduced by the empty-pair overhead (round 2 subtracted 4.5 us per bracket and read the layer GEMM at
-            # 30.85 us where rocprofv3 measured 34.35; the raw bracket is the conservative figure, within a few per cent of rocprofv3)
-            g[1] += max(e0.elapsed_time(e1) * 1e-3, 1e-7)
-        return groups
-
-    @staticmethod
-    def _work(name, key):
-        """-> (label, shape, dtype name, bound or None, algorithmic work per launch, peak per second)"""
-        model = _WORK_MODELS.get(name)
-        if model is not None:
-            label, shape, dt, bound, work = model(key)
-            peak = PEAK_TFLOPS[dt] * 1e12 if bound == "mfma" else PEAK_HBM_GBS * 1e9
-            return label, list(shape), "bf16" if dt == BF16 else "f32", bound, work, peak
-        if name.startswith("torch:") and key and key[0] > 0:  # bench.py's own brackets around torch ops: key = (bytes,)
-            return name, [], "f32", "hbm", float(key[0]), PEAK_HBM_GBS * 1e9
-        return name.replace("spv_", ""), list(key[:4]), "-", None, 0.0, 1.0
-
-    def summary(self):
-        out = []
-        for (name, key), (cnt, tot) in sorted(self._groups().items(), key=lambda kv: -kv[1][1]):
-            label, shape, dt, bound, work, peak = self._work(name, key)
-            d = dict(kernel=label, shape=shape, dtype=dt, launches=cnt, avg_us=round(tot / cnt * 1e6, 2), total_ms=round(tot * 1e3, 3))
-            if bound is not None:
-                ach = work * cnt / tot
-                d.update(bound=bound, achieved=round(ach / (1e12 if bound == "mfma" else 1e9), 2),
-                         unit="TFLOP/s" if bound == "mfma" else "GB/s", frac=round(ach / peak, 4), algorithmic=int(work))
-            out.append(d)
-        return out
-
-    def roofline(self):
-        """the single modelled (kernel, shape) with the largest total time in the recorded steps"""
-        s = [d for d in self.summary() if "bound" in d]
-        if not s:
-            return None
-        d = s[0]
-        peak = (PEAK_TFLOPS[BF16 if d["dtype"] == "bf16" else F32]) if d["bound"] == "mfma" else PEAK_HBM_GBS
-        return dict(bound=d["bound"], achieved=d["achieved"], peak=peak, unit=d["unit"], frac=d["frac"], traffic=None,
-                    kernel=d["kernel"], shape=d["shape"], avg_us=d["avg_us"], launches=d["launches"],
-                    event_overhead_us=round(self.overhead_s * 1e6, 2))
-
-
-def set_kernel_timer(t):
-    _native.timer = t
-
-
-def _timing():
-    return _native.timer is not None
-
-
 def _gemm(a, b, bias, c, M, N, K, lda, ldb, ldc, accumulate=0, splits=1, workspace=None):
     if splits == 1 and K >= 256:
         # a handful of output tiles (the 512 x 100 classifier head: 4) would run on a handful of CUs for the whole K
@@ -462,8 +87,7 @@ def _gemm(a, b, bias, c, M, N, K, lda, ldb, ldc, accumulate=0, splits=1, workspa
             splits = max(1, min(K // 64, 256 // tiles))
             if splits > 1:
                 workspace = torch.empty((splits * M * N,), dtype=torch.float32, device=c.device)
-    _native.call("spv_gemm_nt", _p(a), _p(b), _p(bias), _p(c), M, N, K, lda, ldb, ldc, _dt(a), _dt(c), accumulate, splits,
-                 _p(workspace), _stream())
+    _gemm_launch(a, b, bias, c, M, N, K, lda, ldb, ldc, accumulate, splits, workspace)
 
 
 def _gemm_launch(a, b, bias, c, M, N, K, lda, ldb, ldc, accumulate=0, splits=1, workspace=None):
@@ -501,13 +125,13 @@ def join_side_stream():
 # With data parallelism the bucket hooks need every gradient as soon as its node has run: nothing is held.
 # ------------------------------------------------------------------------------------------------
 PATH_COUNTS = collections.Counter()   # host-side dispatch census (tests assert that the shapes they ran took the batched / side paths)
-_held_folds = []   # (partials, outputs, parts, n)
+_held_folds = []   # _Fold jobs
 _held_task = -2    # the autograd graph task (backward pass) the held folds belong to
 FOLD_RIDERS = 6    # fold jobs a layer's own reduce launch carries
 # Layer weight gradients travel together as well: alone each is 24 tiles of 128 x 128, i.e. ~21 K-slices to fill the chip (25 K-tiles
 # per workgroup, 33 MB of partial sums written and re-read); eight of them in one launch fill it with 5 slices.  Same conditions as a
 # held fold (sink-backed outputs, one process), and only gradients nothing reads before the backward pass ends.
-_held_wgrads = []  # (dh, x, dw address, rows, n, k, fold or None)
+_held_wgrads = []  # _HeldWgrad records
 WGRAD_BATCH = 8    # problems per launch (csrc/spv_gemm.hip TNB_MAX)
 BATCH_FOLDS = 16   # fold jobs the batch's reduce launch carries (FJ_MAX)
 _WGRAD_HOLD = True   # layer weight gradients are held for the batch launch
@@ -532,10 +156,6 @@ def _graph_task_id():
     return _task_id_fn() if _task_id_fn is not None else -1
 
 
-def _queue_end_of_backward(fn):
-    _engine.queue_callback(fn)
-
-
 def _hold_ok():
     if not _HOLD_API:
         return False
@@ -547,13 +167,27 @@ def _hold_ok():
     return not (dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1)
 
 
+_T = torch.Tensor
+# The fold of a row kernel's partial column sums (`parts` slabs of rows of length n) into its parameter gradients, to ride in / be
+# deferred with a weight gradient's reduction.  outs are raw addresses, never tensors: a second reference to a gradient tensor makes
+# AccumulateGrad clone the -- still unfolded -- gradient (see _hold_fold); whoever makes the job holds the tensors until it is issued or held.
+_Fold = NamedTuple("_Fold", [("partials", _T), ("outs", tuple), ("parts", int), ("n", int)])
+# A layer weight gradient dw[n, k] = dh[rows, n]^T . x[rows, k] held for the batch launch at the end of the backward pass: dw is the
+# address of its sink slot, fold the _Fold that rides in its reduce (or None)
+_HeldWgrad = NamedTuple("_HeldWgrad", [("dh", _T), ("x", _T), ("dw", int), ("rows", int), ("n", int), ("k", int), ("fold", object)])
+
+
+def _addrs(tensors):
+    return tuple(t.data_ptr() for t in tensors)
+
+
 def _fold_array(folds):
     arr = (_native.FoldJob * len(folds))()
-    for j, (partials, outs, parts, n) in zip(arr, folds):
-        j.partials = _p(partials)
-        for i, o in enumerate(outs):
-            j.out[i] = o if isinstance(o, int) else _p(o)   # held folds carry raw sink addresses (see _hold_fold)
-        j.parts, j.nsum, j.n = parts, len(outs), n
+    for j, f in zip(arr, folds):
+        j.partials = _p(f.partials)
+        for i, o in enumerate(f.outs):
+            j.out[i] = o
+        j.parts, j.nsum, j.n = f.parts, len(f.outs), f.n
     return arr
 
 
@@ -582,40 +216,38 @@ def _flush_held_wgrads():
     while _held_wgrads:
         # up to eight per launch, the long reductions first; gradients over fewer rows (the CLS-only last layer's: 512) ride in the same
         # launch as short problems -- one workgroup per tile, no split-K, no launch + reduce of their own behind the big one
-        rows = max(w[3] for w in _held_wgrads)
-        group = sorted(_held_wgrads, key=lambda w: -w[3])[:WGRAD_BATCH]
+        rows = max(w.rows for w in _held_wgrads)
+        group = sorted(_held_wgrads, key=lambda w: -w.rows)[:WGRAD_BATCH]
         taken = {id(w) for w in group}
-        _held_wgrads[:] = [w for w in _held_wgrads if id(w) not in taken]   # (by identity: the tuples hold tensors)
+        _held_wgrads[:] = [w for w in _held_wgrads if id(w) not in taken]   # (by identity: the records hold tensors)
         probs = (_native.TnProblem * len(group))()
         tiles = floats = 0
         flops = 0.0
         folds = []
-        for q, (dh, x, dwp, r, n, k, fold) in zip(probs, group):
-            q.a, q.b, q.c, q.m, q.n, q.lda, q.ldb, q.ldc, q.k = _p(dh), _p(x), dwp, n, k, n, k, k, r
-            if r == rows:
+        for q, w in zip(probs, group):
+            n, k = w.n, w.k
+            q.a, q.b, q.c, q.m, q.n, q.lda, q.ldb, q.ldc, q.k = _p(w.dh), _p(w.x), w.dw, n, k, n, k, k, w.rows
+            if w.rows == rows:
                 tiles += ((n + 127) // 128) * ((k + 127) // 128)
                 floats += n * k
-            flops += 2.0 * r * n * k
-            used += [dh, x]
-            if fold is not None:
-                folds.append(fold)
+            flops += 2.0 * w.rows * n * k
+            used += [w.dh, w.x]
+            if w.fold is not None:
+                folds.append(w.fold)
         while _held_folds and len(folds) < BATCH_FOLDS:
             folds.append(_held_folds.pop(0))
         splits = max(1, min(_batch_splits(tiles), rows // 256))   # (the CLS-only last layer: 512 rows)
-        ws = torch.empty((splits * floats,), dtype=torch.float32, device=group[0][0].device)
+        ws = torch.empty((splits * floats,), dtype=torch.float32, device=group[0].dh.device)
         used.append(ws)
-        used += [f[0] for f in folds]   # the folds' partial column sums: read by the reduce launch, long after this function returns
+        used += [f.partials for f in folds]   # the folds' partial column sums: read by the reduce launch, long after this function returns
         arr = _fold_array(folds) if folds else None
+        batch = (ctypes.addressof(probs), len(group), rows, splits, _p(ws), ctypes.addressof(arr) if folds else 0, len(folds))
         if _timing():   # a measuring pass brackets the GEMM launch and the reduce launch separately (same kernels, same order)
-            _native.hint = int(flops)
-            _native.call("spv_gemm_tn_batch_part", ctypes.addressof(probs), len(group), rows, splits, _p(ws), ctypes.addressof(arr) if folds else 0,
-                         len(folds), 1, _stream())
-            _native.hint = int(4.0 * floats * (splits + 1))
-            _native.call("spv_gemm_tn_batch_part", ctypes.addressof(probs), len(group), rows, splits, _p(ws), ctypes.addressof(arr) if folds else 0,
-                         len(folds), 2, _stream())
+            for part, work in ((1, flops), (2, 4.0 * floats * (splits + 1))):
+                _native.hint = int(work)
+                _native.call("spv_gemm_tn_batch_part", *batch, part, _stream())
         else:
-            _native.call("spv_gemm_tn_batch", ctypes.addressof(probs), len(group), rows, splits, _p(ws), ctypes.addressof(arr) if folds else 0,
-                         len(folds), _stream())
+            _native.call("spv_gemm_tn_batch", *batch, _stream())
         PATH_COUNTS["wgrad_batch"] += 1
         PATH_COUNTS["wgrad_batch_problems"] += len(group)
     return used
@@ -627,7 +259,7 @@ def start_held_wgrads():
     launches that leaves most of the chip idle.  The end-of-pass callback joins the streams.  True when something was started."""
     if not (_held_wgrads and _held_task == _graph_task_id()) or _timing():
         return False   # (a timed pass keeps the batch on the main stream: its event brackets must not overlap other kernels)
-    side = _side_stream(_held_wgrads[0][0].device)
+    side = _side_stream(_held_wgrads[0].dh.device)
     side.wait_stream(torch.cuda.current_stream())
     with torch.cuda.stream(side):
         used = _flush_held_wgrads()
@@ -640,21 +272,25 @@ def start_held_wgrads():
     return True
 
 
+def _begin_pass(task):
+    """the first hold of backward pass `task`: leftovers cleared, the end-of-pass callback queued, the task recorded"""
+    global _held_task
+    if _held_task != task:
+        _held_folds.clear()   # leftovers of a backward pass that never finished (an exception): their launch must not ride along
+        _held_wgrads.clear()
+        _engine.queue_callback(flush_held_folds)
+        _held_task = task
+
+
 def _hold_wgrad(dh, x, dw, sink, rows, n, k, fold, fold_sunk):
     """hold a layer weight gradient for the batch launch at the end of this backward pass (see _held_wgrads).  False: not held."""
-    global _held_task
     if not (_WGRAD_HOLD and _hold_ok() and _in_sink(dw, sink) and (fold is None or fold_sunk)):
         return False
     task = _graph_task_id()
     if task < 0:
         return False
-    if _held_task != task:
-        _held_folds.clear()
-        _held_wgrads.clear()
-        _queue_end_of_backward(flush_held_folds)
-        _held_task = task
-    f = None if fold is None else (fold[0], tuple(o.data_ptr() for o in fold[1]), fold[2], fold[3])   # raw sink addresses, as _hold_fold
-    _held_wgrads.append((dh, x, dw.data_ptr(), rows, n, k, f))
+    _begin_pass(task)
+    _held_wgrads.append(_HeldWgrad(dh, x, dw.data_ptr(), rows, n, k, fold))
     return True
 
 
@@ -682,18 +318,13 @@ def _hold_fold(partials, outs, sinks, parts, n):
     """hold a fold for the next weight-gradient reduce of this backward pass.  Only when every output IS its parameter's sink slot
     (memory that outlives the node; autograd adopts the alias without copying), and never by keeping the output tensors themselves:
     a second reference makes AccumulateGrad clone the -- still unfolded -- gradient.  False (not held) otherwise."""
-    global _held_task
-    if not _hold_ok() or any(sk is None or o.data_ptr() != sk.view.data_ptr() for o, sk in zip(outs, sinks)):
+    if not _hold_ok() or not _sunk(outs, sinks):
         return False
     task = _graph_task_id()
     if task < 0:   # not inside a backward pass
         return False
-    if _held_task != task:
-        _held_folds.clear()   # leftovers of a backward pass that never finished (an exception): their launch must not ride along
-        _held_wgrads.clear()
-        _queue_end_of_backward(flush_held_folds)
-        _held_task = task
-    _held_folds.append((partials, tuple(o.data_ptr() for o in outs), parts, n))
+    _begin_pass(task)
+    _held_folds.append(_Fold(partials, _addrs(outs), parts, n))
     return True
 
 
@@ -704,9 +335,8 @@ def _fold_rides(dtype, rows, n, k):
 
 
 def _fold_job(partials, outs, rows, n):
-    """(partials, outputs, partial slabs, row length): the fold of a tail backward's column sums, to ride in / be deferred with the
-    weight gradient's reduction"""
-    return (partials, tuple(outs), _native.call("spv_tail_bwd_parts", rows), n)
+    """the fold of a tail backward's column sums over `rows` rows (the caller holds `outs` until the weight gradient has been issued)"""
+    return _Fold(partials, _addrs(outs), _native.call("spv_tail_bwd_parts", rows), n)
 
 
 def _sunk(outs, sinks):
@@ -805,39 +435,89 @@ def _new_seed():
     return int(torch.randint(0, 2 ** 62, (1,)).item())
 
 
+def _rows2d(x, k):
+    """x as a contiguous [rows, k] matrix (a view where x's memory allows)"""
+    x2 = x.reshape(-1, k)
+    return x2 if x2.is_contiguous() else x2.contiguous()
+
+
+def _row_stats(rows, dev):
+    """(mean, rstd): the fp32 LayerNorm statistics a row kernel writes for its backward"""
+    return torch.empty((rows,), dtype=torch.float32, device=dev), torch.empty((rows,), dtype=torch.float32, device=dev)
+
+
+_CHANNEL_ERRORS = {
+    "SpectreLinear": "SpectreLinear({k}->{n}) in {dt}: channel counts must be multiples of {mult}",
+    "Linear": "Linear({k}->{n}) in {dt}: feature counts must be multiples of {mult}",
+    "MHPermutMix": "MHPermutMix linear ({k}->{n}) in {dt}: channel counts must be multiples of {mult}",
+    "patch embedding": "patch embedding: C*P*P={k} and embed_dim={n} must be multiples of {mult}",
+}
+
+
+def _check_channels(kind, n, k, dt):
+    """the vector width of the kernels: both channel counts in multiples of 8 (bf16) / 4 (fp32)"""
+    mult = 8 if dt == torch.bfloat16 else 4
+    if n % mult or k % mult:
+        raise ValueError(_CHANNEL_ERRORS[kind].format(n=n, k=k, dt=dt, mult=mult))
+
+
+def _colsum(d2, out):
+    rows, n = d2.shape
+    part = torch.empty((min(rows, 512) * n,), dtype=torch.float32, device=d2.device)
+    _native.call("spv_colsum", _p(d2), _p(out), _p(part), rows, n, _dt(d2), _stream())
+    return out
+
+
+def _zero_workspace(cache, dev, floats_entry):
+    """the zeroed counter block of a loss kernel, `floats_entry` floats, kept in `cache`"""
+    key = dev.index   # one loss per step and device; not per stream, so that a graph capture reuses the warm-up's (zeroed) counter
+    ws = cache.get(key)
+    if ws is None:
+        ws = cache[key] = torch.zeros((_native.call(floats_entry),), dtype=torch.float32, device=dev)
+    return ws
+
+
+# Saved-for-backward state of the raw forwards below.  ctx.saved keeps these (not save_for_backward: no version-counter checks).
+# _sl_forward -> _sl_backward; sinks = (weight, bias, gamma, beta)
+_SLSaved = NamedTuple("_SLSaved", [("x2", _T), ("h", _T), ("mean", _T), ("rstd", _T), ("gamma", _T), ("beta", _T), ("wt", _T),
+                                   ("sinks", tuple), ("rows", int), ("n", int), ("k", int), ("p_drop", float), ("seed", int)])
+# _addln_forward -> _addln_backward; sinks = (gamma, beta)
+_AddLNSaved = NamedTuple("_AddLNSaved", [("a2", _T), ("b2", _T), ("mean", _T), ("rstd", _T), ("gamma", _T), ("sinks", tuple),
+                                         ("rows", int), ("n", int), ("mode", int)])
+# LayerNorm-2's share of the fused linear3 tail + LayerNorm-2 kernel (FFResidualFn, beside linear3's _SLSaved); sinks = (n2w, n2b)
+_TailLN2Saved = NamedTuple("_TailLN2Saved", [("f3", _T), ("x1", _T), ("mean2", _T), ("rstd2", _T), ("n2w", _T), ("sinks", tuple)])
+# the fused FNet mixer + LayerNorm-1 kernel (FNetResidualFn); sinks = (n1w, n1b)
+_FNetLN1Saved = NamedTuple("_FNetLN1Saved", [("m", _T), ("mean", _T), ("rstd", _T), ("gamma", _T), ("sinks", tuple)])
+
+
 # ------------------------------------------------------------------------------------------------
 # SpectreLinear: GELU(LN(x W^T + b)) + avgpool(x) [+ dropout]      (reference layers.py:76-101)
 # ------------------------------------------------------------------------------------------------
 def _sl_forward(x2, weight, bias, gamma, beta, p_drop, out_fp32):
-    """raw SpectreLinear forward on a contiguous [rows, k] tensor -> (out [rows, n], saved-for-backward tuple)"""
+    """raw SpectreLinear forward on a contiguous [rows, k] tensor -> (out [rows, n], _SLSaved)"""
     n, k = weight.shape
     rows = x2.shape[0]
     dt = x2.dtype
-    mult = 8 if dt == torch.bfloat16 else 4
-    if n % mult or k % mult:
-        raise ValueError(f"SpectreLinear({k}->{n}) in {dt}: channel counts must be multiples of {mult}")
-    wc, wt = _shadows.get(weight, dt)
+    _check_channels("SpectreLinear", n, k, dt)
+    wc, wt = shadows.get(weight, dt)
     dev = x2.device
     h = torch.empty((rows, n), dtype=dt, device=dev)
     _gemm(x2, wc, bias, h, rows, n, k, k, k, n)
     out = torch.empty((rows, n), dtype=torch.float32 if out_fp32 else dt, device=dev)
-    mean = torch.empty((rows,), dtype=torch.float32, device=dev)
-    rstd = torch.empty((rows,), dtype=torch.float32, device=dev)
+    mean, rstd = _row_stats(rows, dev)
     seed = _new_seed() if p_drop > 0.0 else 0
     _native.call("spv_spectre_tail_fwd", _p(h), _p(x2), _p(gamma), _p(beta), _p(out), _p(mean), _p(rstd), rows, n, k,
                  _dt(h), _dt(out), float(p_drop), seed, _stream())
     sinks = (_sink(weight), _sink(bias), _sink(gamma), _sink(beta))
-    return out, (x2, h, mean, rstd, gamma, beta, wt, sinks, rows, n, k, float(p_drop), seed)
+    return out, _SLSaved(x2, h, mean, rstd, gamma, beta, wt, sinks, rows, n, k, float(p_drop), seed)
 
 
 def _sl_backward(dout2, saved, need_dx=True, dx_add=None, up=None):
-    """raw SpectreLinear backward -> (dx or None, dW, dbias, dgamma, dbeta); dx_add: a gradient of the same input that is
+    """raw SpectreLinear backward of a contiguous dout2 [rows, n] -> (dx or None, dW, dbias, dgamma, dbeta); dx_add: a gradient of the same input that is
     folded into dx by the tail kernel (saves a separate elementwise add); up = (src, p_drop, seed): the skip gradient of the
     layer above, formed here from its source instead of being written by that layer and accumulated by its GEMM"""
     x2, h, mean, rstd, gamma, beta, wt, sinks, rows, n, k, p_drop, seed = saved
     dev = x2.device
-    if not dout2.is_contiguous():
-        dout2 = dout2.contiguous()
     dh = torch.empty_like(h)
     dx = torch.empty_like(x2)
     s_w, s_b, s_g, s_be = sinks
@@ -870,10 +550,7 @@ class SpectreLinearFn(torch.autograd.Function):
         _require_gpu(x, weight)
         n, k = weight.shape
         shape = x.shape
-        x2 = x.reshape(-1, k)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        out, saved = _sl_forward(x2, weight, bias, gamma, beta, p_drop, out_fp32)
+        out, saved = _sl_forward(_rows2d(x, k), weight, bias, gamma, beta, p_drop, out_fp32)
         ctx.saved = saved
         ctx.shape = shape
         return out.reshape(*shape[:-1], n)
@@ -881,8 +558,7 @@ class SpectreLinearFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         saved = ctx.saved
-        rows, n = saved[8], saved[9]
-        dx, dw, dbias, dgamma, dbeta = _sl_backward(dout.reshape(rows, n), saved, ctx.needs_input_grad[0])
+        dx, dw, dbias, dgamma, dbeta = _sl_backward(_rows2d(dout, saved.n), saved, ctx.needs_input_grad[0])
         join_side_stream()
         return (dx.reshape(ctx.shape) if dx is not None else None), dw, dbias, dgamma, dbeta, None, None
 
@@ -897,17 +573,15 @@ def spectre_linear(x, weight, bias, gamma, beta, p_drop=0.0, out_fp32=False):
 def _addln_forward(a2, b2, gamma, beta, mode):
     rows, n = a2.shape
     out = torch.empty_like(a2)
-    mean = torch.empty((rows,), dtype=torch.float32, device=a2.device)
-    rstd = torch.empty_like(mean)
+    mean, rstd = _row_stats(rows, a2.device)
     _native.call("spv_add_layernorm_fwd", _p(a2), _p(b2), _p(gamma), _p(beta), _p(out), _p(mean), _p(rstd), rows, n, mode,
                  _dt(a2), _stream())
-    return out, (a2, b2, mean, rstd, gamma, (_sink(gamma), _sink(beta)), rows, n, mode)
+    return out, _AddLNSaved(a2, b2, mean, rstd, gamma, (_sink(gamma), _sink(beta)), rows, n, mode)
 
 
 def _addln_backward(d2, saved):
+    """d2: contiguous [rows, n]"""
     a2, b2, mean, rstd, gamma, sinks, rows, n, mode = saved
-    if not d2.is_contiguous():
-        d2 = d2.contiguous()
     din = torch.empty_like(a2)
     dgamma = _grad_buf(sinks[0], (n,), a2.device)
     dbeta = _grad_buf(sinks[1], (n,), a2.device)
@@ -922,17 +596,16 @@ class AddLayerNormFn(torch.autograd.Function):
     def forward(ctx, a, b, gamma, beta, mode):
         _require_gpu(a, b)
         n = a.shape[-1]
-        out, saved = _addln_forward(a.reshape(-1, n).contiguous(), b.reshape(-1, n).contiguous(), gamma, beta, mode)
+        out, saved = _addln_forward(_rows2d(a, n), _rows2d(b, n), gamma, beta, mode)
         ctx.saved = saved
         ctx.shape = a.shape
         return out.reshape(a.shape)
 
     @staticmethod
     def backward(ctx, dout):
-        rows, n, mode = ctx.saved[6], ctx.saved[7], ctx.saved[8]
-        din, dgamma, dbeta = _addln_backward(dout.reshape(rows, n), ctx.saved)
+        din, dgamma, dbeta = _addln_backward(_rows2d(dout, ctx.saved.n), ctx.saved)
         din = din.reshape(ctx.shape)
-        return din, (dout if mode == 0 else din), dgamma, dbeta, None
+        return din, (dout if ctx.saved.mode == 0 else din), dgamma, dbeta, None
 
 
 def add_layernorm(a, b, gamma, beta, mode):
@@ -1021,7 +694,7 @@ class RfftRealFn(torch.autograd.Function):
     def forward(ctx, x):
         _require_gpu(x)
         D = x.shape[-1]
-        xc = x.reshape(-1, D).contiguous()
+        xc = _rows2d(x, D)
         y = torch.empty((xc.shape[0], D // 2 + 1), dtype=x.dtype, device=x.device)
         _native.call("spv_rfft_real", _p(xc), _p(y), xc.shape[0], D, 0, _dt(xc), _stream())
         ctx.meta = (x.shape, D)
@@ -1030,7 +703,7 @@ class RfftRealFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dy):
         shape, D = ctx.meta
-        dyc = dy.reshape(-1, D // 2 + 1).contiguous()
+        dyc = _rows2d(dy, D // 2 + 1)
         dx = torch.empty((dyc.shape[0], D), dtype=dy.dtype, device=dy.device)
         _native.call("spv_rfft_real", _p(dyc), _p(dx), dyc.shape[0], D, 1, _dt(dyc), _stream())
         return dx.reshape(shape)
@@ -1124,9 +797,7 @@ class PatchEmbedFn(torch.autograd.Function):
         T = Np + 1
         dev = img.device
         img = img.contiguous() if u8 else img.contiguous().float()
-        mult = 8 if dtype == torch.bfloat16 else 4
-        if K % mult or E % mult:
-            raise ValueError(f"patch embedding: C*P*P={K} and embed_dim={E} must be multiples of {mult}")
+        _check_channels("patch embedding", E, K, dtype)
         st = _stream()
         # token rows [B][T][K], the CLS slot of every image zero: the GEMM below then writes cls + pos[0] there by itself (its row bias
         # holds that sum in row 0), and the backward's TN weight-gradient GEMM reads the same matrix against dtok as both lie in memory
@@ -1417,8 +1088,7 @@ class ClsHeadFn(torch.autograd.Function):
         logits = torch.empty((B, n), dtype=torch.float32, device=dev)
         h = torch.empty((B, n), dtype=torch.float32, device=dev)
         xs = torch.empty((B, E), dtype=torch.float32, device=dev)
-        mean = torch.empty((B,), dtype=torch.float32, device=dev)
-        rstd = torch.empty((B,), dtype=torch.float32, device=dev)
+        mean, rstd = _row_stats(B, dev)
         _native.call("spv_small_sl_fwd", _p(out), N * E, _p(src_cls), src_cls.stride(0), _p(weight), _p(bias), _p(gamma), _p(beta), _p(logits), _p(h),
                      _p(xs), _p(mean), _p(rstd), B, n, E, _dt(out), _stream())
         ctx.save_for_backward(h, xs, mean, rstd, weight, gamma, beta)
@@ -1455,15 +1125,6 @@ class ClsHeadFn(torch.autograd.Function):
 _ce_workspaces = {}
 
 
-def _ce_workspace(dev):
-    key = dev.index   # one loss per step and device; not per stream, so that a graph capture reuses the warm-up's (zeroed) counter
-    ws = _ce_workspaces.get(key)
-    if ws is None:
-        ws = torch.zeros((_native.call("spv_cross_entropy_workspace_floats"),), dtype=torch.float32, device=dev)
-        _ce_workspaces[key] = ws
-    return ws
-
-
 class CrossEntropyFn(torch.autograd.Function):
     """nn.CrossEntropyLoss() with its defaults (mean over rows; reference repl/train.py:196,226): one launch forward (row-wise
     logsumexp, deterministic sum), one backward -- stock torch runs log_softmax, nll_loss, two fills and their two backwards."""
@@ -1478,7 +1139,7 @@ class CrossEntropyFn(torch.autograd.Function):
         rows, C = z.shape
         lse = torch.empty((rows,), dtype=torch.float32, device=z.device)
         loss = torch.empty((), dtype=torch.float32, device=z.device)
-        _native.call("spv_cross_entropy_fwd", _p(z), _p(y), _p(lse), _p(loss), _p(_ce_workspace(z.device)), rows, C, _stream())
+        _native.call("spv_cross_entropy_fwd", _p(z), _p(y), _p(lse), _p(loss), _p(_zero_workspace(_ce_workspaces, z.device, "spv_cross_entropy_workspace_floats")), rows, C, _stream())
         ctx.save_for_backward(z, y, lse)
         return loss
 
@@ -1520,15 +1181,6 @@ def eval_head(logits, labels, n_valid, pred, stats, k=5):
 _distill_workspaces = {}
 
 
-def _distill_workspace(dev):
-    key = dev.index   # as _ce_workspace: one per device, so that a graph capture reuses the warm-up's (zeroed) counter
-    ws = _distill_workspaces.get(key)
-    if ws is None:
-        ws = torch.zeros((_native.call("spv_distill_loss_workspace_floats"),), dtype=torch.float32, device=dev)
-        _distill_workspaces[key] = ws
-    return ws
-
-
 class DistillLossFn(torch.autograd.Function):
     """w_soft T^2 / B sum p_t (log p_t - log p_s) + w_ce CE (reference repl/train.py:300-302, 334-348): one launch forward, one
     backward -- the stock chain is two divisions, softmax, log_softmax, log, subtract, multiply, sum, two scalings, the cross-entropy
@@ -1545,7 +1197,7 @@ class DistillLossFn(torch.autograd.Function):
         rows, C = z.shape
         lse = torch.empty((3, rows), dtype=torch.float32, device=z.device)
         out = torch.empty((3,), dtype=torch.float32, device=z.device)
-        _native.call("spv_distill_loss_fwd", _p(z), _p(t), _p(y), _p(lse), _p(out), _p(_distill_workspace(z.device)), rows, C, float(T),
+        _native.call("spv_distill_loss_fwd", _p(z), _p(t), _p(y), _p(lse), _p(out), _p(_zero_workspace(_distill_workspaces, z.device, "spv_distill_loss_workspace_floats")), rows, C, float(T),
                      float(w_soft), float(w_ce), _stream())
         ctx.save_for_backward(z, t, y, lse)
         ctx.consts = (float(T), float(w_soft), float(w_ce))
@@ -1578,14 +1230,10 @@ class LinearFn(torch.autograd.Function):
     def forward(ctx, x, weight, bias, out_fp32):
         _require_gpu(x, weight)
         n, k = weight.shape
-        x2 = x.reshape(-1, k)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _rows2d(x, k)
         rows = x2.shape[0]
-        mult = 8 if x2.dtype == torch.bfloat16 else 4
-        if n % mult or k % mult:
-            raise ValueError(f"Linear({k}->{n}) in {x2.dtype}: feature counts must be multiples of {mult}")
-        wc, wt = _shadows.get(weight, x2.dtype)
+        _check_channels("Linear", n, k, x2.dtype)
+        wc, wt = shadows.get(weight, x2.dtype)
         y = torch.empty((rows, n), dtype=torch.float32 if out_fp32 else x2.dtype, device=x2.device)
         _gemm(x2, wc, bias, y, rows, n, k, k, k, n)
         ctx.save_for_backward(x2, weight)
@@ -1611,9 +1259,7 @@ class LinearFn(torch.autograd.Function):
             dx = dx.reshape(shape)
         db = None
         if has_bias:
-            db = _grad_buf(ctx.sinks[1], (n,), x2.device)
-            part = torch.empty((min(rows, 512) * n,), dtype=torch.float32, device=x2.device)
-            _native.call("spv_colsum", _p(dy2), _p(db), _p(part), rows, n, _dt(dy2), _stream())
+            db = _colsum(dy2, _grad_buf(ctx.sinks[1], (n,), x2.device))
         join_side_stream()
         return dx, dw, db, None
 
@@ -1742,7 +1388,7 @@ class AttnClsFn(torch.autograd.Function):
         dt = xc.dtype
         x2 = xc.view(B * N, E)
         x0 = xc[:, 0, :].contiguous()
-        wc, wt = _shadows.get(w_in, dt)   # (the cached copies of the whole parameter, sliced: the cache is keyed on the parameter)
+        wc, wt = shadows.get(w_in, dt)   # (the cached copies of the whole parameter, sliced: the cache is keyed on the parameter)
         bq = bk = None
         if b_in is not None:
             bq, bk = b_in[:E], b_in[E:]
@@ -1799,26 +1445,25 @@ class FFResidualFn(torch.autograd.Function):
     def forward(ctx, x1, w1, b1, g1, be1, w3, b3, g3, be3, n2w, n2b, p_drop):
         _require_gpu(x1, w1)
         shape = x1.shape
-        x2d = x1.reshape(-1, shape[-1])
-        if not x2d.is_contiguous():
-            x2d = x2d.contiguous()
+        x2d = _rows2d(x1, shape[-1])
         f1, s1 = _sl_forward(x2d, w1, b1, g1, be1, p_drop, False)
         ctx.shape = shape
         n3, k3 = w3.shape
         if _native.call("spv_tail_ln_supported", n3, k3, _dt(f1)):
             # linear3's GEMM, then ONE row kernel: LayerNorm/GELU/pooled skip/dropout of the SpectreLinear tail, + x1, LayerNorm-2
             rows, dt, dev = f1.shape[0], f1.dtype, f1.device
-            wc3, wt3 = _shadows.get(w3, dt)
+            wc3, wt3 = shadows.get(w3, dt)
             h3 = torch.empty((rows, n3), dtype=dt, device=dev)
             _gemm(f1, wc3, b3, h3, rows, n3, k3, k3, k3, n3)
             f3 = torch.empty_like(h3)
             out = torch.empty_like(h3)
-            mean3, rstd3, mean2, rstd2 = (torch.empty((rows,), dtype=torch.float32, device=dev) for _ in range(4))
+            mean3, rstd3 = _row_stats(rows, dev)
+            mean2, rstd2 = _row_stats(rows, dev)
             seed = _new_seed() if p_drop > 0.0 else 0
             _native.call("spv_spectre_tail_ln_fwd", _p(h3), _p(f1), _p(g3), _p(be3), _p(f3), _p(mean3), _p(rstd3), _p(x2d), _p(n2w),
                          _p(n2b), _p(out), _p(mean2), _p(rstd2), rows, n3, k3, _dt(h3), float(p_drop), seed, _stream())
-            s3 = (f1, h3, mean3, rstd3, g3, be3, wt3, (_sink(w3), _sink(b3), _sink(g3), _sink(be3)), rows, n3, k3, float(p_drop), seed)
-            ctx.saved = (s1, s3, ("fused", f3, x2d, mean2, rstd2, n2w, (_sink(n2w), _sink(n2b))))
+            s3 = _SLSaved(f1, h3, mean3, rstd3, g3, be3, wt3, (_sink(w3), _sink(b3), _sink(g3), _sink(be3)), rows, n3, k3, float(p_drop), seed)
+            ctx.saved = (s1, s3, _TailLN2Saved(f3, x2d, mean2, rstd2, n2w, (_sink(n2w), _sink(n2b))))
             return out.reshape(shape)
         f3, s3 = _sl_forward(f1, w3, b3, g3, be3, p_drop, False)
         out, sn = _addln_forward(f3, x2d, n2w, n2b, 1)
@@ -1828,13 +1473,11 @@ class FFResidualFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, dout):
         s1, s3, sn = ctx.saved
-        if isinstance(sn[0], str):  # ("fused", ...): LayerNorm-2 backward inside the linear3 tail backward
-            _, f3, x1, mean2, rstd2, n2w, sinks2 = sn
+        if isinstance(sn, _TailLN2Saved):  # LayerNorm-2 backward inside the linear3 tail backward
+            f3, x1, mean2, rstd2, n2w, sinks2 = sn
             f1, h3, mean3, rstd3, g3, be3, wt3, sinks3, rows, n, k, p_drop, seed = s3
             dev = f1.device
-            d2 = dout.reshape(rows, n)
-            if not d2.is_contiguous():
-                d2 = d2.contiguous()
+            d2 = _rows2d(dout, n)
             ds = torch.empty_like(f3)
             dh3 = torch.empty_like(h3)
             df1 = torch.empty_like(f1)
@@ -1844,7 +1487,7 @@ class FFResidualFn(torch.autograd.Function):
             partials = torch.empty((_native.call("spv_tail_ln_partial_floats", n),), dtype=torch.float32, device=dev)
             # linear3's skip gradient (its transposed pooling) is taken by linear1's tail backward from `ds` itself when the
             # shapes allow: df1 is then a plain GEMM output (no [rows, 768] tensor written here and re-read by the GEMM)
-            defer = _native.call("spv_tail_up_supported", s1[9], s1[10], _dt(h3)) and s1[9] == k
+            defer = _native.call("spv_tail_up_supported", s1.n, s1.k, _dt(h3)) and s1.n == k
             ride = _fold_rides(dh3.dtype, rows, n, k)   # the five column sums' fold rides in the weight gradient's split-K reduce
             pp = (lambda t: 0) if ride else _p
             _native.call("spv_spectre_tail_ln_bwd", _p(d2), _p(f3), _p(x1), _p(mean2), _p(rstd2), _p(n2w), _p(ds), pp(dn2w), pp(dn2b),
@@ -1853,15 +1496,12 @@ class FFResidualFn(torch.autograd.Function):
             dw3 = _weight_grad(dh3, f1, rows, n, k, s_w, _fold_job(partials, (dg3, dbe3, db3, dn2w, dn2b), rows, n) if ride else None,
                                ride and _sunk((dg3, dbe3, db3, dn2w, dn2b), (s_g, s_be, s_b, sinks2[0], sinks2[1])))
             _gemm(dh3, wt3, None, df1, rows, k, n, n, wt3.shape[1], k, accumulate=0 if defer else 1)
-            if defer:
-                dx1, dw1, db1, dg1, dbe1 = _sl_backward(df1, s1, True, dx_add=ds, up=(ds, p_drop, seed))
-                join_side_stream()
-                return dx1.reshape(ctx.shape), dw1, db1, dg1, dbe1, dw3, db3, dg3, dbe3, dn2w, dn2b, None
+            up = (ds, p_drop, seed) if defer else None
         else:
-            rows, n = sn[6], sn[7]
-            ds, dn2w, dn2b = _addln_backward(dout.reshape(rows, n), sn)      # d(x1 + f3)
+            ds, dn2w, dn2b = _addln_backward(_rows2d(dout, sn.n), sn)      # d(x1 + f3)
             df1, dw3, db3, dg3, dbe3 = _sl_backward(ds, s3, True)
-        dx1, dw1, db1, dg1, dbe1 = _sl_backward(df1, s1, True, dx_add=ds)  # + the residual path, folded in
+            up = None
+        dx1, dw1, db1, dg1, dbe1 = _sl_backward(df1, s1, True, dx_add=ds, up=up)  # + the residual path, folded in
         join_side_stream()
         return dx1.reshape(ctx.shape), dw1, db1, dg1, dbe1, dw3, db3, dg3, dbe3, dn2w, dn2b, None
 
@@ -1880,12 +1520,11 @@ class FNetResidualFn(torch.autograd.Function):
             dev = xc.device
             m = torch.empty_like(xc)
             out = torch.empty_like(xc)
-            mean = torch.empty((B * N,), dtype=torch.float32, device=dev)
-            rstd = torch.empty_like(mean)
+            mean, rstd = _row_stats(B * N, dev)
             tw = _fnet_twiddle(N, dev)
             _native.call("spv_fnet_ln_fwd", _p(xc), _p(m), _p(out), _p(n1w), _p(n1b), _p(mean), _p(rstd), _p(tw), B, N, D, _dt(xc),
                          _stream())
-            ctx.saved = ("fused", m, mean, rstd, n1w, (_sink(n1w), _sink(n1b)))
+            ctx.saved = _FNetLN1Saved(m, mean, rstd, n1w, (_sink(n1w), _sink(n1b)))
             return out
         m = _fnet_raw(xc)
         out, sn = _addln_forward(m.reshape(-1, D), xc.reshape(-1, D), n1w, n1b, 0)
@@ -1896,11 +1535,9 @@ class FNetResidualFn(torch.autograd.Function):
     def backward(ctx, dout):
         sn = ctx.saved
         B, N, D = ctx.shape
-        d2 = dout.reshape(-1, D)
-        if not d2.is_contiguous():
-            d2 = d2.contiguous()
-        if isinstance(sn[0], str):  # ("fused", ...)
-            _, m, mean, rstd, gamma, sinks = sn
+        d2 = _rows2d(dout, D)
+        if isinstance(sn, _FNetLN1Saved):
+            m, mean, rstd, gamma, sinks = sn
             dev = m.device
             dx = torch.empty_like(m)
             dn1w = _grad_buf(sinks[0], (D,), dev)
@@ -1936,8 +1573,7 @@ class FNetClsFn(torch.autograd.Function):
         dev = xc.device
         out = torch.empty((B, D), dtype=xc.dtype, device=dev)
         m0 = torch.empty((B, D), dtype=torch.float32, device=dev)
-        mean = torch.empty((B,), dtype=torch.float32, device=dev)
-        rstd = torch.empty_like(mean)
+        mean, rstd = _row_stats(B, dev)
         _native.call("spv_fnet_cls_fwd", _p(xc), _p(n1w), _p(n1b), _p(out), _p(m0), _p(mean), _p(rstd), B, N, D, _dt(xc), _stream())
         ctx.saved = (m0, mean, rstd, n1w, (_sink(n1w), _sink(n1b)))
         ctx.meta = (B, N, D, xc.dtype)
@@ -1955,7 +1591,7 @@ class FNetClsFn(torch.autograd.Function):
         partials = torch.empty((B * 2 * D,), dtype=torch.float32, device=dev)
         _native.call("spv_fnet_cls_bwd", _p(g), _p(m0), _p(mean), _p(rstd), _p(n1w), _p(dx), _p(partials), B, N, D, _DT[dtype], _stream())
         if not _hold_fold(partials, (dn1w, dn1b), sinks, B, D):   # the batch sums of dgamma / dbeta: with the next reduce, or now
-            arr = _fold_array([(partials, (dn1w, dn1b), B, D)])
+            arr = _fold_array([_Fold(partials, _addrs((dn1w, dn1b)), B, D)])
             _native.call("spv_fold_multi", ctypes.addressof(arr), 1, _stream())
         return dx, dn1w, dn1b
 
@@ -1972,8 +1608,7 @@ class HaarResidualFn(torch.autograd.Function):
         rows = xc.numel() // D
         dev = xc.device
         out = torch.empty_like(xc)
-        mean = torch.empty((rows,), dtype=torch.float32, device=dev)
-        rstd = torch.empty_like(mean)
+        mean, rstd = _row_stats(rows, dev)
         _native.call("spv_haar_ln_fwd", _p(xc), _p(n1w), _p(n1b), _p(out), _p(mean), _p(rstd), rows, D, _dt(xc), _stream())
         ctx.save_for_backward(xc, mean, rstd, n1w)
         ctx.sinks = (_sink(n1w), _sink(n1b))
@@ -2020,9 +1655,7 @@ class PermutMixFn(torch.autograd.Function):
         total = heads * d
         rows = (B * total) // k
         dt = xc.dtype
-        mult = 8 if dt == torch.bfloat16 else 4
-        if n % mult or k % mult:
-            raise ValueError(f"MHPermutMix linear ({k}->{n}) in {dt}: channel counts must be multiples of {mult}")
+        _check_channels("MHPermutMix", n, k, dt)
         pw = k // n if k % n == 0 else 0
         es = 2 if dt == torch.bfloat16 else 4
         can_pool = pw in (4, 8, 16, 32) and (d * es) % 16 == 0 and d * es <= 150 * 1024 and (total // 4) % 1024 == 0 and total % pw == 0
@@ -2033,12 +1666,11 @@ class PermutMixFn(torch.autograd.Function):
         pooled = torch.empty((rows, n), dtype=dt, device=dev) if can_pool else None
         st = _stream()
         _native.call("spv_permut_gather_fwd", _p(xc), _p(idx), _p(g), _p(pooled), pw, B, heads, d, _dt(xc), st)
-        wc, wt = _shadows.get(weight, dt)
+        wc, wt = shadows.get(weight, dt)
         h = torch.empty((rows, n), dtype=dt, device=dev)
         _gemm(g, wc, bias, h, rows, n, k, k, k, n)
         out = torch.empty((rows, n), dtype=dt, device=dev)
-        mean = torch.empty((rows,), dtype=torch.float32, device=dev)
-        rstd = torch.empty((rows,), dtype=torch.float32, device=dev)
+        mean, rstd = _row_stats(rows, dev)
         skip = pooled if can_pool else g
         _native.call("spv_spectre_tail_fwd", _p(h), _p(skip), _p(gamma), _p(beta), _p(out), _p(mean), _p(rstd), rows, n,
                      n if can_pool else k, _dt(h), _dt(out), 0.0, 0, st)
@@ -2052,9 +1684,7 @@ class PermutMixFn(torch.autograd.Function):
         idx, wt, sinks, xshape, B, heads, d, rows, n, k, pw = ctx.aux
         dev = g.device
         st = _stream()
-        d2 = dout.reshape(rows, n)
-        if not d2.is_contiguous():
-            d2 = d2.contiguous()
+        d2 = _rows2d(dout, n)
         s_w, s_b, s_g, s_be = sinks
         dh = torch.empty_like(h)
         dgamma = _grad_buf(s_g, (n,), dev)
@@ -2077,237 +1707,10 @@ class PermutMixFn(torch.autograd.Function):
         return dx.reshape(xshape), None, None, dw, dbias, dgamma, dbeta
 
 
-# ------------------------------------------------------------------------------------------------
-# SpectreBranch  (reference spectre_branch/spectre_branch.py:92-173): spectrum, 3x3 conv chain, token pooling, the two-half projection
-# ------------------------------------------------------------------------------------------------
-def _r8(v):
-    return (v + 7) // 8 * 8
-
-
-def _colsum(d2, out):
-    rows, n = d2.shape
-    part = torch.empty((min(rows, 512) * n,), dtype=torch.float32, device=d2.device)
-    _native.call("spv_colsum", _p(d2), _p(out), _p(part), rows, n, _dt(d2), _stream())
-    return out
-
-
-def _wgrad_into(dh, x, rows, n, k, out, ldc, ldx=None):
-    """out[n, k] (leading dimension ldc, fp32) = dh[rows, n]^T . x[rows, k] (x's leading dimension ldx >= k), split-K and folded in
-    a fixed order, written NOW (never held for the end-of-backward batch: the caller may hand a view of a larger gradient)"""
-    ldx = k if ldx is None else ldx
-    dev = dh.device
-    tiles = ((n + 127) // 128) * ((k + 127) // 128)
-    splits = max(1, min(512 // tiles, (rows + 511) // 512 if tiles >= 8 else (rows + 63) // 64, 64))
-    ws = torch.empty((splits * n * k,), dtype=torch.float32, device=dev) if splits > 1 else None
-    st = _stream()
-    if dh.dtype == torch.bfloat16 and n % 8 == 0 and k % 8 == 0 and ldx % 8 == 0:
-        _native.call("spv_gemm_tn", _p(dh), _p(x), _p(out), n, k, rows, n, ldx, ldc, F32, 0, splits, _p(ws), st)
-        return out
-    ld = _r8(rows)
-    dht = torch.empty((n, ld), dtype=dh.dtype, device=dev)
-    xt = torch.empty((ldx, ld), dtype=x.dtype, device=dev)
-    _native.call("spv_cast_transpose", _p(dh), _dt(dh), _p(dht), _dt(dht), rows, n, ld, 0, 0, 0, st)
-    _native.call("spv_cast_transpose", _p(x), _dt(x), _p(xt), _dt(xt), rows, ldx, ld, 0, 0, 0, st)
-    _native.call("spv_gemm_nt", _p(dht), _p(xt), 0, _p(out), n, k, ld, ld, ld, ldc, _dt(dht), F32, 0, splits, _p(ws), st)
-    return out
-
-
-def spectrum_log1p(img, dtype=torch.float32):
-    """log1p(|rfft2(img)|) of fp32 NCHW images, channels-last (B, H, W//2+1, C) in `dtype` (spectre_branch.py:151).  Forward only."""
-    _require_gpu(img)
-    if img.requires_grad:
-        raise RuntimeError("spectrum_log1p: the SpectreBranch spectrum has no backward (gradients to the input image are not built)")
-    if img.dtype != torch.float32 or img.dim() != 4:
-        raise TypeError(f"spectrum_log1p takes fp32 (B, C, H, W) images, got {img.dtype} {tuple(img.shape)}")
-    img = img.contiguous()
-    B, C, H, W = img.shape
-    out = torch.empty((B, H, W // 2 + 1, C), dtype=dtype, device=img.device)
-    _native.call("spv_spectrum_log1p", _p(img), _p(out), B, C, H, W, _DT[dtype], _stream())
-    return out
-
-
-def conv3x3_fwd(x, weight, bias):
-    """valid 3x3 stride-1 conv of channels-last x (B, H, W, Cin) -> (B, H-2, W-2, Cout) in x's dtype (spectre_branch.py:133)"""
-    _require_gpu(x, weight)
-    B, H, W, cin = x.shape
-    cout = weight.shape[0]
-    kp = _r8(9 * cin)
-    wpack = torch.zeros((cout, kp), dtype=x.dtype, device=x.device)
-    wpack[:, :9 * cin] = weight.detach().reshape(cout, 9 * cin)
-    cols = torch.empty(((B * (H - 2) * (W - 2)) * kp,), dtype=x.dtype, device=x.device)
-    y = torch.empty((B, H - 2, W - 2, cout), dtype=x.dtype, device=x.device)
-    _native.call("spv_conv3x3_fwd", _p(x), _p(wpack), _p(bias), _p(y), _p(cols), B, H, W, cin, cout, _dt(x), _stream())
-    return y
-
-
-def conv3x3_dgrad(dy, weight):
-    """input gradient (B, H, W, Cin) of conv3x3_fwd from dy (B, H-2, W-2, Cout): the full correlation with the kernel"""
-    B, ho, wo, cout = dy.shape
-    cin = weight.shape[1]
-    kd = _r8(9 * cout)
-    wd = torch.zeros((cin, kd), dtype=dy.dtype, device=dy.device)
-    wd[:, :9 * cout] = weight.detach().transpose(0, 1).reshape(cin, 9 * cout)
-    H, W = ho + 2, wo + 2
-    cols = torch.empty((B * H * W * kd,), dtype=dy.dtype, device=dy.device)
-    dx = torch.empty((B, H, W, cin), dtype=dy.dtype, device=dy.device)
-    _native.call("spv_conv3x3_dgrad", _p(dy), _p(wd), _p(dx), _p(cols), B, H, W, cin, cout, _dt(dy), _stream())
-    return dx
-
-
-def conv3x3_wgrad(dy, x, out=None):
-    """weight gradient (Cout, Cin, 3, 3) fp32 of conv3x3_fwd: dy^T . im2col(x) over every output position, split and folded in order"""
-    B, H, W, cin = x.shape
-    cout = dy.shape[-1]
-    M = B * (H - 2) * (W - 2)
-    mp = _r8(M)
-    k = 9 * cin
-    dev = x.device
-    dw = torch.empty((cout, cin, 3, 3), dtype=torch.float32, device=dev) if out is None else out
-    tiles = ((cout + 127) // 128) * ((k + 127) // 128)
-    splits = max(1, min(256 // tiles, mp // 1024, 256))
-    ws = torch.empty((splits * cout * k,), dtype=torch.float32, device=dev) if splits > 1 else None
-    dyt = torch.empty((cout * mp,), dtype=dy.dtype, device=dev)
-    colst = torch.empty((k * mp,), dtype=x.dtype, device=dev)
-    _native.call("spv_conv3x3_wgrad", _p(dy), _p(x), _p(dw), _p(dyt), _p(colst), _p(ws), splits, B, H, W, cin, cout, _dt(x), _stream())
-    return dw
-
-
-def token_pool_fwd(y, tokens, ldo=None):
-    """AdaptiveAvgPool1d(tokens) over the flattened map of channels-last y (B, H, W, C) -> (B, tokens, ldo), columns >= C zero"""
-    _require_gpu(y)
-    B, C = y.shape[0], y.shape[-1]
-    L = y.numel() // (B * C)
-    ldo = C if ldo is None else ldo
-    out = torch.empty((B, tokens, ldo), dtype=y.dtype, device=y.device)
-    _native.call("spv_token_pool_fwd", _p(y), _p(out), B, L, C, tokens, ldo, _dt(y), _stream())
-    return out
-
-
-def token_pool_bwd(dout, L, C, add=None):
-    """transpose of token_pool_fwd: dout (B, T, ldo) -> (B, L, C) (+ add)"""
-    _require_gpu(dout)
-    B, T, ldo = dout.shape
-    dy = torch.empty((B, L, C), dtype=dout.dtype, device=dout.device)
-    _native.call("spv_token_pool_bwd", _p(dout), ldo, _p(add), _p(dy), B, L, C, T, _dt(dout), _stream())
-    return dy
-
-
-class BranchFeatFn(torch.autograd.Function):
-    """SpectreFeatExtractor.forward (spectre_branch.py:147-173) as one autograd node: (x_last, feats[0..S-1]).
-
-    Pool first, then project: pool(W y + b) = W pool(y) + b (a window averages the constant bias to itself), so each 1x1 projection
-    is a (B T, C_k) x (C_k, E) GEMM on the pooled map and the (B, E, H'W') maps are never built.  Backward runs from the last stage
-    to the first: d y_k = unpool(dFeat_k W_k) + dgrad(conv_{k+1}), then conv k's weight / bias gradients and its data gradient.
-    x_last (channels-last storage, NCHW view) carries no gradient."""
-
-    @staticmethod
-    def forward(ctx, img, tokens, dtype, *params):
-        S = len(params) // 4
-        convs = [(params[2 * i], params[2 * i + 1]) for i in range(S)]
-        projs = [(params[2 * S + 2 * i], params[2 * S + 2 * i + 1]) for i in range(S)]
-        x = spectrum_log1p(img, dtype)
-        B = x.shape[0]
-        xs, pooled, wps, feats = [], [], [], []
-        for (cw, cb), (pw, pb) in zip(convs, projs):
-            y = conv3x3_fwd(x, cw, cb)
-            cout, E = y.shape[-1], pw.shape[0]
-            ldo = _r8(cout)
-            pk = token_pool_fwd(y, tokens, ldo)
-            wp = torch.zeros((E, ldo), dtype=dtype, device=x.device)
-            wp[:, :cout] = pw.detach().reshape(E, cout)
-            f = torch.empty((B, tokens, E), dtype=dtype, device=x.device)
-            _gemm(pk, wp, pb, f, B * tokens, E, ldo, ldo, ldo, E)
-            xs.append(x)
-            pooled.append(pk)
-            wps.append(wp)
-            feats.append(f)
-            x = y
-        ctx.saved = (xs, pooled, wps, [cw for cw, _ in convs], [t.shape for t in xs[1:] + [x]])
-        ctx.sinks = [(_sink(cw), _sink(cb)) for cw, cb in convs] + [(_sink(pw), _sink(pb)) for pw, pb in projs]
-        ctx.meta = (S, tokens, B)
-        x_last = x.permute(0, 3, 1, 2)
-        ctx.mark_non_differentiable(x_last)
-        return (x_last, *feats)
-
-    @staticmethod
-    def backward(ctx, _dx_last, *dfeats):
-        xs, pooled, wps, cws, yshapes = ctx.saved
-        S, T, B = ctx.meta
-        dev, dt = xs[0].device, xs[0].dtype
-        conv_grads, proj_grads = [None] * (2 * S), [None] * (2 * S)
-        g_next = None
-        for k in range(S - 1, -1, -1):
-            _, ho, wo, cout = yshapes[k]
-            E, ldo = wps[k].shape
-            rows = B * T
-            df = dfeats[k]
-            df = torch.zeros((rows, E), dtype=dt, device=dev) if df is None else df.reshape(rows, E)
-            df = _raw_cast(df, dt) if df.dtype != dt else df.contiguous()
-            dpool = torch.empty((B, T, ldo), dtype=dt, device=dev)
-            wpt = wps[k].t().contiguous()
-            _gemm(df, wpt, None, dpool, rows, ldo, E, E, E, ldo)
-            (sw, sb), (spw, spb) = ctx.sinks[k], ctx.sinks[S + k]
-            dpw = _grad_buf(spw, (E, cout, 1, 1), dev)
-            _wgrad_into(df, pooled[k], rows, E, cout, dpw, cout, ldo)
-            dpb = _colsum(df, _grad_buf(spb, (E,), dev))
-            dy = token_pool_bwd(dpool, ho * wo, cout, g_next).view(B, ho, wo, cout)
-            dw = conv3x3_wgrad(dy, xs[k], _grad_buf(sw, tuple(cws[k].shape), dev))
-            db = _colsum(dy.reshape(-1, cout), _grad_buf(sb, (cout,), dev))
-            conv_grads[2 * k], conv_grads[2 * k + 1] = dw, db
-            proj_grads[2 * k], proj_grads[2 * k + 1] = dpw, dpb
-            g_next = conv3x3_dgrad(dy, cws[k]) if k > 0 else None
-        return (None, None, None, *conv_grads, *proj_grads)
-
-
-def branch_features(img, convs, projs, tokens, dtype):
-    """(x_last, [feats]) of the SpectreFeatExtractor: convs / projs = [(weight, bias)] per stage"""
-    _require_gpu(img, *[w for w, _ in convs])
-    params = [t for wb in convs for t in wb] + [t for wb in projs for t in wb]
-    out = BranchFeatFn.apply(img, tokens, dtype, *params)
-    return out[0], list(out[1:])
-
-
-class BranchProjectFn(torch.autograd.Function):
-    """spectre_project[i](cat([x, feat], -1)) (+ src) (spectre_branch.py:113-119) without the concat: two NT GEMMs into one output over
-    the column halves of W (ldb = 2E, the second accumulating); backward writes dx and dfeat from the two halves of W^T and the two
-    dW halves through ldc = 2E.  `src` (the encoder's global residual, :119) is folded into the last projection's output."""
-
-    @staticmethod
-    def forward(ctx, x, feat, weight, bias, src):
-        _require_gpu(x, feat, weight)
-        n, k2 = weight.shape
-        k = k2 // 2
-        dt = x.dtype
-        x2, f2 = x.reshape(-1, k).contiguous(), _raw_cast(feat, dt).reshape(-1, k) if feat.dtype != dt else feat.reshape(-1, k).contiguous()
-        rows = x2.shape[0]
-        wc, wt = _shadows.get(weight, dt)
-        out = torch.empty((rows, n), dtype=dt, device=x2.device)
-        acc = 0
-        if src is not None:
-            out.copy_(src.reshape(rows, n))
-            acc = 1
-        _gemm_launch(x2, wc, bias, out, rows, n, k, k, k2, n, acc)
-        _gemm_launch(f2, wc[:, k:], None, out, rows, n, k, k, k2, n, 1)
-        ctx.saved = (x2, f2, wt, (_sink(weight), _sink(bias)), x.shape, feat.dtype, rows, n, k, src is not None)
-        return out.reshape(*x.shape[:-1], n)
-
-    @staticmethod
-    def backward(ctx, dout):
-        x2, f2, wt, sinks, shape, fdt, rows, n, k, has_src = ctx.saved
-        d2 = dout.reshape(rows, n)
-        d2 = _raw_cast(d2, x2.dtype) if d2.dtype != x2.dtype else d2.contiguous()
-        dev = x2.device
-        dx = torch.empty_like(x2)
-        df = torch.empty_like(f2)
-        _gemm(d2, wt, None, dx, rows, k, n, n, wt.shape[1], k)
-        _gemm(d2, wt[k:], None, df, rows, k, n, n, wt.shape[1], k)
-        dw = _grad_buf(sinks[0], (n, 2 * k), dev)
-        _wgrad_into(d2, x2, rows, n, k, dw, 2 * k)
-        _wgrad_into(d2, f2, rows, n, k, dw[:, k:], 2 * k)
-        db = _colsum(d2, _grad_buf(sinks[1], (n,), dev))
-        dsrc = d2.reshape(shape) if has_src else None
-        return dx.reshape(shape), df.reshape(shape), dw, db, dsrc
-
-
-def branch_project(x, feat, weight, bias, src=None):
-    return BranchProjectFn.apply(x, feat, weight, bias, src)
+def __getattr__(name):
+    """the SpectreBranch ops lived here before branch_ops.py: callers that still ask here for one are served from there"""
+    if not name.startswith("_"):
+        from . import branch_ops
+        if hasattr(branch_ops, name):
+            return getattr(branch_ops, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

@@ -13,11 +13,11 @@ the training path's autograd Functions, which is what sets the latency below bat
     python -m spectre_vit.inference --config spectre_vit/configs/spectre_vit_cifar100.py --mixer fft --checkpoint model_best.pt
 
 THE FROZEN-WEIGHTS RULE.  A session's outputs change only at ``refresh()``.  The session reads nothing the model, an optimizer or
-``hip_ops``'s weight-copy cache owns: at construction (and at every ``refresh()``) the model's parameters and buffers are copied into
+``shadows``' weight-copy cache owns: at construction (and at every ``refresh()``) the model's parameters and buffers are copied into
 the session's own eval-mode replica, whose tensors never move, and the compute-dtype (W, W^T) copies the GEMMs read live in buffers
-the session owns as well (``hip_ops.PinnedShadows``; ``refresh()`` recasts them in place with one spv_weight_shadows_multi launch).
-Training the model, stepping an optimizer, replaying a ``GraphedTrainStep`` (which writes weights through raw pointers and replaces
-the cache object) or freeing the model leaves a session's results bit for bit where they were.  The source model is never put into
+the session owns as well (``shadows.PinnedShadows``; ``refresh()`` recasts them in place with one spv_weight_shadows_multi launch).
+Training the model, stepping an optimizer, replaying a ``GraphedTrainStep`` (which writes weights through raw pointers and empties
+that cache) or freeing the model leaves a session's results bit for bit where they were.  The source model is never put into
 another mode: the replica is the module that runs, always in ``eval()``.
 
 WHAT ONE GRAPH HOLDS.  One graph per bucket of ``batch_sizes``, captured on first use, on one stream (the forward has no side-stream
@@ -108,7 +108,7 @@ class InferenceSession:
     the eager forward).  ``return_features=True``: ``s.features`` holds the CLS features of the last call's (last) bucket."""
 
     def __init__(self, model, batch_sizes=DEFAULT_BUCKETS, autocast_dtype=torch.bfloat16, input="float", topk=5, return_features=False):
-        from spectre_vit import hip_ops
+        from spectre_vit import hip_ops, shadows
         from spectre_vit.models.spectre.spectre import SpectreViT
         from spectre_vit.models.spectre_branch.spectre_branch import SpectreBranch
         from spectre_vit.models.vit.vit import ViT
@@ -140,7 +140,7 @@ class InferenceSession:
         self._net = net
         self._dst = dict(net.named_parameters())
         self._dst.update(net.named_buffers())
-        self._pinned = hip_ops.PinnedShadows()
+        self._pinned = shadows.PinnedShadows()
         self._n_valid = torch.zeros(1, dtype=torch.int32, device=self.device)
         self._rows_word = 0   # the host's copy of the device word
         self._stats = hip_ops.eval_head_stats(self.device)
@@ -188,7 +188,7 @@ class InferenceSession:
         b = self._b.get(rows)
         if b is not None:
             return b
-        from spectre_vit import hip_ops
+        from spectre_vit import shadows
         if self._sample_shape is None:
             self._sample_shape = tuple(like.shape[1:])
         b = _Bucket()
@@ -203,11 +203,11 @@ class InferenceSession:
         self._n_valid.zero_()
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side), hip_ops.pinned_shadows(self._pinned):
+        with torch.cuda.stream(side), shadows.pinned_shadows(self._pinned):
             self._forward(b)
         torch.cuda.current_stream().wait_stream(side)
         b.graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(b.graph), hip_ops.pinned_shadows(self._pinned):
+        with torch.cuda.graph(b.graph), shadows.pinned_shadows(self._pinned):
             b.logits, b.features = self._forward(b)
         self._n_valid.copy_(keep)
         self._b[rows] = b

@@ -11,7 +11,7 @@ import torch
 import torch.nn as nn
 from torch.nn.modules.transformer import _get_activation_fn, _get_clones
 
-from spectre_vit import hip_ops
+from spectre_vit import hip_ops, shadows
 from spectre_vit.models.spectre.layers import MHPermutMix, SpectreLinear
 from spectre_vit.modules.mixers import FNetMixer, HaarDWTMixer, SelfAttentionMixer
 
@@ -239,7 +239,7 @@ class SpectreViT(nn.Module):
 
     def forward(self, x, return_features=False):
         if torch.is_grad_enabled() and x.is_cuda and torch.is_autocast_enabled("cuda"):
-            hip_ops.refresh_weight_shadows(self, self._shadow_weights)  # all layers' bf16 weight copies in one launch
+            shadows.refresh_weight_shadows(self, self._shadow_weights)  # all layers' bf16 weight copies in one launch
         x = self.embeddings_block(x)
         if self._observed():
             x = self.encoder_blocks(x)

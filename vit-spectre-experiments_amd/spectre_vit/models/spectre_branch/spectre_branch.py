@@ -14,7 +14,7 @@ import torch
 import torch.nn as nn
 from torch.nn.modules.transformer import _get_activation_fn, _get_clones
 
-from spectre_vit import hip_ops
+from spectre_vit import branch_ops, hip_ops
 from spectre_vit.models.spectre.spectre import Transpose
 from spectre_vit.modules.patch_embeddings import PatchEmbedding
 
@@ -94,13 +94,13 @@ class SpectreBranchEncoder(nn.Module):
         for idx, mod in enumerate(self.layers):
             proj = self.spectre_project[idx]
             # the global residual `output + src` (:119) folds into the last projection's output
-            out = hip_ops.branch_project(mod(out), feats[idx], proj.weight, proj.bias, src if idx == last else None)
+            out = branch_ops.branch_project(mod(out), feats[idx], proj.weight, proj.bias, src if idx == last else None)
         return out
 
 
 class SpectreFeatExtractor(nn.Module):
     """x = log1p(|rfft2(img)|); per stage k: x = Conv2d(c, 3c, 3)(x), feats[k] = pool_T(Conv2d(3c, E, 1)(x)) as (B, T, E)
-    (reference :122-173).  Runs as one autograd node (hip_ops.BranchFeatFn): the 1x1 projection is applied to the pooled map
+    (reference :122-173).  Runs as one autograd node (branch_ops.BranchFeatFn): the 1x1 projection is applied to the pooled map
     (exact: pooling and a per-position affine map commute), and the image receives no gradient."""
 
     def __init__(self, in_channels, embed_dim, num_tokens, reduction=1, num_stages=1) -> None:
@@ -132,7 +132,7 @@ class SpectreFeatExtractor(nn.Module):
                              f"{H}x{x.shape[-1]} image (spectre_branch.py:130-137)")
         convs = [(s[0].weight, s[0].bias) for s in self.net]
         projs = [(p[0].weight, p[0].bias) for p in self.project]
-        return hip_ops.branch_features(x, convs, projs, self.num_tokens, hip_ops.compute_dtype(x))
+        return branch_ops.branch_features(x, convs, projs, self.num_tokens, hip_ops.compute_dtype(x))
 
 
 class SpectreBranch(nn.Module):
