@@ -19,6 +19,7 @@
 #ifndef SPV_H
 #define SPV_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -56,7 +57,7 @@ enum {
     SPV_PATH_TOKEN_UNPOOL = 19,  /* spv_token_pool_bwd */
     SPV_PATH_ATTN_ROW0_FWD = 20, /* spv_attention_row0_fwd (the attention mixer's CLS-only last layer) */
     SPV_PATH_ATTN_ROW0_BWD = 21, /* spv_attention_row0_bwd */
-    SPV_PATH_AUGMENT = 22,       /* spv_augment_u8 (the training transform chain, one workgroup per image) */
+    SPV_PATH_AUGMENT = 22,       /* spv_augment_u8 (one workgroup per image) or spv_augment_tiled_u8 (output tiles): one per call */
     SPV_PATH_TEACHER_VIEW = 23,  /* spv_teacher_view_u8 (the distillation teacher's 224 view, one workgroup per image and row band) */
     SPV_PATH_COUNT = 24
 };
@@ -559,7 +560,7 @@ typedef struct spv_augment_cfg {   /* a HOST struct, read during the call */
 int spv_augment_params(float* params, int batch, int chans, int height, int width, const spv_augment_cfg* cfg, uint64_t seed,
                        uint64_t step, void* stream);
 /* 1 when spv_augment_u8 can stage the image: chans 1 or 3, height and width >= 2, and two fp32 copies of the image within the 64 KiB
- * of LDS a workgroup may take (3 x 32 x 32 and 1 x 28 x 28 fit; 224 x 224 does not). */
+ * of LDS a workgroup may take (3 x 32 x 32 and 1 x 28 x 28 fit; 224 x 224 does not: spv_augment_tiled_u8 below takes it). */
 int spv_augment_supported(int chans, int height, int width);
 /* Applies the chain: out_nchw[b] (fp32 [chans][height][width], normalised) from src_nhwc[index[b]] (uint8 [height][width][chans], the
  * loader's layout as spv_patchify_u8 takes it; index == NULL: rows 0..batch-1) and params[b].  A pure function of its arguments.
@@ -572,6 +573,27 @@ int spv_augment_supported(int chans, int height, int width);
  * reads nothing for such a row and writes NaN to its whole image. */
 int spv_augment_u8(const unsigned char* src_nhwc, const int64_t* index, const float* params, const float* mean, const float* inv_std,
                    float* out_nchw, int batch, int n_src, int chans, int height, int width, void* stream);
+/* The same chain on output tiles, for images spv_augment_u8 cannot stage (64 x 64 ... 224 x 224 ... 512 x 512): same definition,
+ * parameter table and random stream; every pixel comparable with tests/augment_ref.py under the same rule.
+ * spv_augment_plan: 0 = refused by both, 1 = spv_augment_u8 takes it (spv_augment_supported), 2 = only spv_augment_tiled_u8 does.
+ * The tiled kernels take chans 1 or 3 and 2 <= height, width <= 512.  The upper bound is one of CORRECTNESS, not of memory: the
+ * rotation's nearest-neighbour source coordinate cs X + sn Y + t is evaluated in fp32, whose rounding error grows with the coordinate
+ * (about 2^-15 at 512, three terms), and it has to stay far below the 1e-3 window round an integer coordinate inside which the checks
+ * treat a pixel as a rounding tie; at 224 the fp32 and float64 floors agree on every pixel outside that window.
+ * Two launches per call.  (1) Partial sums of the contrast mean: workgroup (image, chunk of 4096 / width rows) adds the grey values of
+ * its pixels after the jitter ops in front of contrast -- fp32 over a thread's <= 16 pixels, a wave, four waves, no atomics -- into
+ * workspace[image][chunk]; a sample whose contrast factor is exactly 1 is skipped.  (2) Workgroup (image, 16 x 64 output tile): adds the
+ * image's partials in index order in float64 (every tile of an image gets the same bits of the mean), evaluates the chain up to the
+ * rotation at each pixel's gathered source position (read from global memory, mirrored if flip), blurs through a one-pixel halo held in
+ * LDS when the sample blurs, normalises, erases, stores (16-byte stores when width % 4 == 0 and out_nchw is 16-byte aligned).
+ * workspace: spv_augment_tiled_ws_bytes(batch, height, width) bytes (0 for a refused shape), 4-byte aligned, written and read inside
+ * the call.  Accepts every shape with plan >= 1 (a 32 x 32 image may be forced through it).  Counts ONE SPV_PATH_AUGMENT per call.
+ * Everything else is refused on the host before any launch; an index outside [0, n_src) writes NaN to its image, as above. */
+int spv_augment_plan(int chans, int height, int width);
+size_t spv_augment_tiled_ws_bytes(int batch, int height, int width);
+int spv_augment_tiled_u8(const unsigned char* src_nhwc, const int64_t* index, const float* params, const float* mean,
+                         const float* inv_std, float* out_nchw, int batch, int n_src, int chans, int height, int width, void* workspace,
+                         size_t workspace_bytes, void* stream);
 
 /* ---- paired-view distillation: spectre_vit/repl/train.py:92-100, 139-141 (the teacher's view), 300-302, 334-348 (the loss) ------
  * spv_teacher_view_u8: out[b] = Normalize(ToTensor(CenterCrop(crop)(Resize(resize, BICUBIC)(src[index[b]])))) from the resident uint8

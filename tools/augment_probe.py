@@ -11,7 +11,10 @@ over a CIFAR-sized resident set (50 000 uint8 images):
 Prints one JSON line.  Not a bench.py line.  `--pkg DIR` times another checkout's package (its own library, e.g. the parent commit's:
 only the `off` windows exist there), so that two builds can alternate inside one GPU job.
 
-    python tools/augment_probe.py [--rounds 4] [--kernels-only] [--pkg DIR]
+`--img-size N` times the kernels on N x N images (the tiled apply path above the LDS kernel's limit; give a `--set-size` that fits
+the card: 2048 images of 224 x 224 are 308 MB) and implies `--kernels-only`: the harness windows are the Small preset's.
+
+    python tools/augment_probe.py [--rounds 4] [--kernels-only] [--pkg DIR] [--img-size 224 --set-size 2048]
 """
 import argparse
 import json
@@ -34,26 +37,41 @@ def event_ms(fn, n):
     return a.elapsed_time(b) / n
 
 
-def kernels(dev, n_set, bs):
+def kernels(dev, n_set, bs, img_size=32):
+    """HIP-event time per launch of the parameter draw, the apply path(s) this size can take ("lds" and / or "tiled": at 32 both, so
+    that the default of "auto" there can be judged) and the yardstick -- the un-augmented batch as the harness makes it from torch ops
+    (index gather, cast, divide, subtract, divide) -- beside the byte floor: fp32 output + uint8 source at 6.3 TB/s."""
     import torch
-    from spectre_vit import harness
+    from spectre_vit import _native, harness
     from spectre_vit.augment import TrainAugment
     g = torch.Generator().manual_seed(0)
-    nhwc = torch.randint(0, 256, (n_set, 32, 32, 3), generator=g, dtype=torch.uint8).to(dev)
+    nhwc = torch.randint(0, 256, (n_set, img_size, img_size, 3), generator=g, dtype=torch.uint8).to(dev)
+    nchw = nhwc.permute(0, 3, 1, 2).contiguous()
     index = torch.randperm(n_set, generator=g)[:bs].to(dev)
-    aug = TrainAugment(harness.CIFAR_MEAN, harness.CIFAR_STD, seed=1)
-    table = aug.draw(bs, 0)
+    mean = torch.tensor(harness.CIFAR_MEAN, device=dev).view(1, 3, 1, 1)
+    std = torch.tensor(harness.CIFAR_STD, device=dev).view(1, 3, 1, 1)
+    tiled_built = "spv_augment_plan" in _native.SIGNATURES   # False in a --pkg checkout from before the tiled path
+    plan = _native.call("spv_augment_plan", 3, img_size, img_size) if tiled_built else 1
+    paths = ["tiled"] if plan == 2 else (["lds", "tiled"] if tiled_built else ["lds"])
+    kw = lambda k: dict(kernel=k) if tiled_built else {}
+    augs = {k: TrainAugment(harness.CIFAR_MEAN, harness.CIFAR_STD, seed=1, **kw(k)) for k in paths}
+    auto = TrainAugment(harness.CIFAR_MEAN, harness.CIFAR_STD, seed=1)
+    table = auto.draw(bs, 0, height=img_size, width=img_size)
     step = [0]
 
     def draw():
         step[0] += 1
-        aug.draw(bs, step[0])
+        auto.draw(bs, step[0], height=img_size, width=img_size)
 
-    out = {}
-    for name, fn in (("params_us", draw), ("apply_us", lambda: aug(nhwc, index, params=table)),
-                     ("params_and_apply_us", lambda: aug(nhwc, index, step=3))):
-        event_ms(fn, 20)
-        out[name] = [round(1e3 * event_ms(fn, 200), 2) for _ in range(3)]
+    fns = [("params_us", draw)]
+    fns += [(f"apply_{k}_us", lambda a=a: a(nhwc, index, params=table)) for k, a in augs.items()]
+    fns += [("params_and_apply_us", lambda: auto(nhwc, index, step=3)),
+            ("torch_ops_unaugmented_us", lambda: (nchw[index].float() / 255.0 - mean) / std)]
+    n = 200 if img_size <= 64 else 50
+    out = {"img_size": img_size, "paths": paths, "byte_floor_us": round(bs * 3 * img_size * img_size * 5 / 6.3e6, 2)}
+    for name, fn in fns:
+        event_ms(fn, 10)
+        out[name] = [round(1e3 * event_ms(fn, n), 2) for _ in range(3)]
     return out
 
 
@@ -128,6 +146,7 @@ def main():
     ap.add_argument("--pkg", default=os.path.join(ROOT, "vit-spectre-experiments_amd"), help="the package directory to time")
     ap.add_argument("--set-size", type=int, default=50000)
     ap.add_argument("--batch", type=int, default=512)
+    ap.add_argument("--img-size", type=int, default=32, help="side of the images the kernels are timed on (not 32: kernels only)")
     a = ap.parse_args()
     sys.path.insert(0, os.path.abspath(a.pkg))
     os.chdir(os.path.abspath(a.pkg))
@@ -142,8 +161,8 @@ def main():
     out = {"pkg": os.path.abspath(a.pkg), "preset": "small", "mixer": "fft", "batch": a.batch, "dtype": "bf16", "graph": True,
            "set_size": a.set_size, "augment_built": have_augment}
     if have_augment:
-        out["kernels"] = kernels(dev, a.set_size, a.batch)
-    if not a.kernels_only:
+        out["kernels"] = kernels(dev, a.set_size, a.batch, a.img_size)
+    if not a.kernels_only and a.img_size == 32:
         out["harness"] = harness_windows(dev, a.set_size, a.batch, a.rounds, have_augment)
     print(json.dumps(out))
 

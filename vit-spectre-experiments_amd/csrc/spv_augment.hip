@@ -3,6 +3,7 @@
 // RandomErasing) as two kernels: spv_augment_params draws the per-sample parameter table, spv_augment_u8 applies it, one workgroup per
 // image with the image staged in LDS.  Definitions: include/spv.h and DESIGN.md section 4c.
 #include "spv_common.h"
+#include "spv_augment_core.h"   // clamp01, grey_of, hue_shift: shared with the tiled kernels
 #include <math.h>
 
 constexpr int AUG_THREADS = 256;
@@ -90,35 +91,6 @@ extern "C" int spv_augment_params(float* params, int batch, int chans, int heigh
 }
 
 // ---------------------------------------------------------------- the chain
-__device__ __forceinline__ float clamp01(float x) { return fminf(fmaxf(x, 0.0f), 1.0f); }
-__device__ __forceinline__ float grey_of(float r, float g, float b) { return 0.2989f * r + 0.587f * g + 0.114f * b; }
-
-// torchvision's _rgb2hsv / _hsv2rgb (the hexcone formulas) with h := frac(h + shift) between them
-__device__ __forceinline__ void hue_shift(float& r, float& g, float& b, float shift) {
-    const float mx = fmaxf(r, fmaxf(g, b)), mn = fminf(r, fminf(g, b));
-    const float d = mx - mn;
-    const bool flat = d == 0.0f;
-    const float v = mx;
-    const float s = flat ? 0.0f : d / mx;
-    const float dd = flat ? 1.0f : d;
-    const float rc = (mx - r) / dd, gc = (mx - g) / dd, bc = (mx - b) / dd;
-    const float h6 = mx == r ? bc - gc : (mx == g ? 2.0f + rc - bc : 4.0f + gc - rc);
-    float h = h6 / 6.0f + 1.0f;
-    h -= floorf(h);
-    h += shift;
-    h -= floorf(h);
-    const float h6b = h * 6.0f;
-    const float fi = floorf(h6b);
-    const float f = h6b - fi;
-    int i = (int)fi % 6;
-    const float p = clamp01(v * (1.0f - s));
-    const float q = clamp01(v * (1.0f - s * f));
-    const float t = clamp01(v * (1.0f - s * (1.0f - f)));
-    r = i == 0 ? v : (i == 1 ? q : (i == 2 ? p : (i == 3 ? p : (i == 4 ? t : v))));
-    g = i == 0 ? t : (i == 1 ? v : (i == 2 ? v : (i == 3 ? q : (i == 4 ? p : p))));
-    b = i == 0 ? p : (i == 1 ? p : (i == 2 ? t : (i == 3 ? v : (i == 4 ? v : q))));
-}
-
 // LDS: two planar [C][H][W] fp32 images (12 KiB each at 3 x 32 x 32) + the reduction slots.  Planar, so that the per-pixel passes touch
 // consecutive addresses per channel (no bank conflict) and the result leaves as it lies (NCHW).  The rotation's gather reads address
 // sy * W + sx: at W = 32 and |angle| <= 30 degrees two lanes of a 32-lane group (one output row) meet on a bank only with equal sx and

@@ -3,10 +3,12 @@
     RandomHorizontalFlip(0.5) -> ColorJitter(0.4, 0.4, 0.4, 0.1) -> RandomGrayscale(0.2) -> RandomAffine(30)
     -> RandomApply([GaussianBlur(3)]) -> ToTensor -> Normalize(mean, std) -> RandomErasing(0.5)
 
-as two HIP kernels (csrc/spv_augment.hip): ``spv_augment_params`` draws a per-sample parameter table on the device and
-``spv_augment_u8`` applies it, one workgroup per image, reading the resident uint8 NHWC set through the batch's index and writing the
-normalised fp32 NCHW batch the models take.  The ops are torchvision's definitions on float tensors (no rounding to 8 bits between
-them, which the reference's PIL pipeline does); the random stream is the library's counter hash keyed by (seed, step, sample, draw),
+as HIP kernels: ``spv_augment_params`` draws a per-sample parameter table on the device and an apply kernel runs it, reading the
+resident uint8 NHWC set through the batch's index and writing the normalised fp32 NCHW batch the models take.  Two apply paths with one
+definition: ``spv_augment_u8`` (csrc/spv_augment.hip), one workgroup per image staged whole in LDS -- CIFAR and MNIST sizes -- and
+``spv_augment_tiled_u8`` (csrc/spv_augment_tiled.hip), a contrast-mean pre-pass plus one workgroup per 16 x 64 output tile, for
+everything larger up to 512 x 512 (the 224 view the reference distils at).  The ops are torchvision's definitions on float tensors (no
+rounding to 8 bits between them, which the reference's PIL pipeline does); the random stream is the library's counter hash keyed by (seed, step, sample, draw),
 not torch's generator.  include/spv.h has the table layout, DESIGN.md section 4c the formulas.
 """
 from __future__ import annotations
@@ -39,10 +41,18 @@ class TrainAugment:
         img = aug(train_u8_nhwc, index, step=global_step)        # float32 (B, C, H, W), normalised
 
     ``draw(batch, step)`` returns the (batch, 16) parameter table; ``aug(images, index, params=table)`` applies a given table: the
-    apply kernel is a pure function of (images, index, params)."""
+    apply kernel is a pure function of (images, index, params).
+
+    ``kernel``: "auto" (the default) takes the whole-image LDS kernel where ``spv_augment_supported`` says it fits and the tiled one
+    otherwise; "lds" and "tiled" force one (a forced kernel that cannot take the image raises in the call)."""
+
+    KERNELS = ("auto", "lds", "tiled")
 
     def __init__(self, mean, std, *, flip=0.5, jitter=(0.4, 0.4, 0.4, 0.1), grayscale=0.2, degrees=30, blur=0.5, blur_sigma=(0.1, 2.0),
-                 erase=0.5, erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3), seed=0):
+                 erase=0.5, erase_scale=(0.02, 0.33), erase_ratio=(0.3, 3.3), seed=0, kernel="auto"):
+        if kernel not in self.KERNELS:
+            raise ValueError(f"kernel is one of {self.KERNELS}, got {kernel!r}")
+        self.kernel = kernel
         self.mean = tuple(float(m) for m in mean)
         self.std = tuple(float(s) for s in std)
         if len(self.mean) != len(self.std) or len(self.mean) not in (1, 3):
@@ -101,13 +111,21 @@ class TrainAugment:
         else:
             batch = params.shape[0] if params is not None else n
         _require_gpu(x, index, params)
-        if not _native.call("spv_augment_supported", C, H, W):
-            raise ValueError(f"a {C} x {H} x {W} image does not fit the augment kernel's LDS staging (two fp32 copies within 64 KiB)")
+        plan = _native.call("spv_augment_plan", C, H, W)
+        if plan == 0 or (self.kernel == "lds" and plan != 1):
+            raise ValueError(f"a {C} x {H} x {W} image does not fit the augment kernel's LDS staging (two fp32 copies within 64 KiB)"
+                             + (" and kernel='lds' rules the tiled one out" if plan else " nor the tiled kernel (sides 2 .. 512)"))
+        tiled = self.kernel == "tiled" or plan == 2
         if params is None:
             params = self.draw(batch, step, height=H, width=W, device=x.device)
         elif params.dtype != torch.float32 or tuple(params.shape) != (batch, NPARAM) or not params.is_contiguous():
             raise TypeError(f"params is a contiguous float32 ({batch}, {NPARAM}) table, got {params.dtype} {tuple(params.shape)}")
         mean, inv_std = self.norm(x.device)
         out = torch.empty((batch, C, H, W), dtype=torch.float32, device=x.device)
-        _native.call("spv_augment_u8", _p(x), _p(index), _p(params), _p(mean), _p(inv_std), _p(out), batch, n, C, H, W, _stream())
+        if tiled:
+            ws = torch.empty(_native.call("spv_augment_tiled_ws_bytes", batch, H, W), dtype=torch.uint8, device=x.device)
+            _native.call("spv_augment_tiled_u8", _p(x), _p(index), _p(params), _p(mean), _p(inv_std), _p(out), batch, n, C, H, W, _p(ws),
+                         ws.numel(), _stream())
+        else:
+            _native.call("spv_augment_u8", _p(x), _p(index), _p(params), _p(mean), _p(inv_std), _p(out), batch, n, C, H, W, _stream())
         return out

@@ -153,8 +153,8 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     The default is the reference's own loop shape (train.py:216-238) with the overlapped bucket exchange under data parallelism.
     augment=True: every training batch goes through the reference's transform chain (train.py:100-115) on the GPU -- the training set
     kept once as uint8 NHWC, the shuffled batch index, the global step and augment_seed(config seed, rank) handed to
-    spectre_vit.augment.TrainAugment; validation batches stay ToTensor + Normalize (eval_transform_spectre).  With graph=True its two
-    launches run on the step's stream in front of the replay.  Not with uint8_input (the chain's output is float) or distill.
+    spectre_vit.augment.TrainAugment; validation batches stay ToTensor + Normalize (eval_transform_spectre).  With graph=True its
+    launches (draw and apply; above the LDS kernel's size also the contrast mean's pre-pass) run on the step's stream in front of the replay.  Not with uint8_input (the chain's output is float) or distill.
     batch_hook(kind, step, img, label), kind "train" / "val": called with every batch as the model is about to see it (test seam).
     graph_eval=True: the epoch's validation runs through one spectre_vit.inference.InferenceSession -- a graph replay per batch (buckets:
     the validation batch size and the tail rounded up to a multiple of 8), accuracy and loss accumulated on the device by its metrics
