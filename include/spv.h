@@ -43,8 +43,8 @@ enum {
     SPV_PATH_TAIL_LN = 5,        /* spv_spectre_tail_ln_fwd / _bwd */
     SPV_PATH_FNET_MFMA = 6,      /* fnet_mfma_kernel (bf16, dim 512) */
     SPV_PATH_GATHER_LDS = 7,     /* LDS-staged MHPermutMix gather */
+    SPV_PATH_DISTILL_CACHED = 8, /* spv_distill_loss_idx_fwd (the distillation loss against the resident teacher-logit cache): one per launch */
     SPV_PATH_GEMM_TN_WIDE = 9,   /* gemm_tn_wide_kernel (256 x 128 tile; M % 256 == 0, N % 128 == 0) */
-    /* index 8 is unused */
     SPV_PATH_GEMM_TN_BATCH = 10, /* gemm_tn_batch_kernel: up to eight weight gradients in one launch (spv_gemm_tn_batch) */
     SPV_PATH_GEMM_STRIP_POOL = 11, /* gemm_nt_strip_kernel<*, 2 / 3>: data gradient + pooled-broadcast term (spv_gemm_nt_pool_bwd) */
     SPV_PATH_GEMM_ROWS = 13,     /* gemm_nt_rows_kernel: few-rows NT GEMM, one 32 x 32 tile per workgroup, no split-K (the CLS-only last layer) */
@@ -628,6 +628,25 @@ int spv_distill_loss_fwd(const float* student, const float* teacher, const int64
                          int rows, int classes, float T, float w_soft, float w_ce, void* stream);
 int spv_distill_loss_bwd(const float* student, const float* teacher, const int64_t* labels, const float* lse3, const float* grad_out,
                          float* dlogits, int rows, int classes, float T, float w_soft, float w_ce, void* stream);
+/* The cached teacher ("cached teacher"): the frozen teacher's logits of every sample, computed once, kept as a
+ * dense fp32 matrix cache [n_cache][classes] and read by the sample's index.
+ * spv_logit_cache_store: cache[index[r]][:] = logits[r][:] for r < rows (index == NULL: rows 0..rows-1, rows <= n_cache checked on the
+ * host).  A row whose index lies outside [0, n_cache) is skipped: nothing is written, nothing is read out of bounds.  16-byte accesses
+ * when classes % 4 == 0 and both bases are 16-byte aligned, 4-byte accesses otherwise (10 classes: 40-byte rows).  Plain stores, no
+ * atomics: when an index repeats within a call, one of its rows wins.
+ * spv_distill_loss_idx_fwd / _bwd: spv_distill_loss_fwd / _bwd with the teacher row of sample r taken at cache + index[r] * classes
+ * (index: int64 [rows] on the device).  One device row body, the same grid, workspace and join as the dense entry points: the result is,
+ * bit for bit, that of the dense call on the gathered matrix cache[index].  An index outside [0, n_cache) cannot be seen by the host:
+ * the kernel reads nothing of the cache for that row; out3[0] and out3[1] become NaN, out3[2] (the cross-entropy) keeps its true value,
+ * lse3[2][r] is NaN, and the backward writes NaN to that row of dlogits.  An unfilled cache row (NaN) poisons the loss the same way.
+ * Refused on the host, before any launch: a missing pointer, rows / classes / n_cache <= 0, T not positive and finite, a weight not
+ * finite.  Counts one SPV_PATH_DISTILL_CACHED per forward launch. */
+int spv_logit_cache_store(float* cache, const int64_t* index, const float* logits, int rows, int n_cache, int classes, void* stream);
+int spv_distill_loss_idx_fwd(const float* student, const float* cache, const int64_t* index, const int64_t* labels, float* lse3, float* out3,
+                             float* workspace, int rows, int n_cache, int classes, float T, float w_soft, float w_ce, void* stream);
+int spv_distill_loss_idx_bwd(const float* student, const float* cache, const int64_t* index, const int64_t* labels, const float* lse3,
+                             const float* grad_out, float* dlogits, int rows, int n_cache, int classes, float T, float w_soft, float w_ce,
+                             void* stream);
 
 /* The end of an inference / validation batch, one launch (csrc/spv_infer.hip): logits [rows][classes] (dtype: SPV_F32 or SPV_BF16),
  * labels int64 [rows], *n_valid an int32 DEVICE word (read by the kernel, so a captured launch follows it), 1 <= k <= 8.

@@ -7,16 +7,23 @@ over a CIFAR-sized resident set (50 000 uint8 images).  One mode per process, so
                    normalise (NOT Pillow-exact: float bicubic with a = -0.75, one rounding) -- alternating; the fused loss forward +
                    backward against distillation_loss() + autograd at [512, 100].  HIP-event time of a run of back-to-back calls divided
                    by their number; the kernels' own durations and launch counts come from
-                   `rocprofv3 --kernel-trace --stats -- python tools/distill_probe.py --mode kernels`.
+                   `rocprofv3 --kernel-trace --stats -- python tools/distill_probe.py --mode kernels`.  Where the package has the cached
+                   teacher: the indexed loss (the teacher's rows read from a [set, 100] cache through a shuffled index) beside the dense
+                   one, and spv_logit_cache_store of one batch.
   --mode eager     the step of harness.train_distill(graph=False): index -> augmented student view + teacher view -> teacher forward ->
                    student forward, fused loss, backward, torch AdamW.
   --mode graph     the same with the student's step replayed by GraphedDistillStep + FusedAdamW.
+  --mode cached-eager   the eager step with the teacher's logits resident (TeacherLogitCache, filled before the windows; the fill is
+                   timed and reported apart): index -> augmented student view -> student forward, indexed fused loss, backward, AdamW.
+                   No teacher view, no teacher forward.
+  --mode cached-graph   the same replayed by GraphedDistillStep in cache mode: the augmentation launches, an index copy, one replay.
   --mode parent    the step harness.train(distill=True) runs (also on the parent commit): the teacher sees F.interpolate(img, 64,
                    "bicubic") of the student's own normalised batch -- a 64 x 64 view, 12 times fewer teacher pixels than the 224 view --
                    and the loss is distillation_loss()'s torch-op chain.
 
 The step modes time windows of --steps steps (host clock around a window that ends in a device synchronise) and print every window.
-Prints one JSON line.  Not a bench.py line.  `--pkg DIR` times another checkout's package (only --mode parent exists on the parent).
+Prints one JSON line.  Not a bench.py line.  `--pkg DIR` times another checkout's package (a package from before the paired-view step
+has --mode parent only; one from before the cached teacher lacks the cached modes).
 
     python tools/distill_probe.py --mode graph [--windows 5] [--steps 97] [--pkg DIR]
 """
@@ -73,6 +80,17 @@ def kernels(dev, n_set, bs, rounds):
 
     fns = {"teacher_view_fp32_us": lambda: v32(nhwc, index), "teacher_view_bf16_us": lambda: v16(nhwc, index),
            "torch_ops_view_fp32_us": torch_ops, "fused_loss_fwd_bwd_us": fused, "torch_chain_loss_fwd_bwd_us": chain}
+    if hasattr(hip_ops, "distill_loss_cached"):
+        from spectre_vit.distillation import TeacherLogitCache
+        cache = TeacherLogitCache(n_set, 100, dev)
+        cache.store(None, (3 * torch.randn(n_set, 100, generator=g)).to(dev))
+
+        def indexed():
+            z.grad = None
+            hip_ops.distill_loss_cached(z, cache.logits, index, y)[0].backward()
+
+        fns["indexed_loss_fwd_bwd_us"] = indexed
+        fns["logit_cache_store_us"] = lambda: cache.store(index, t)
     out = {k: [] for k in fns}
     for fn in fns.values():
         event_us(fn, 5)
@@ -101,6 +119,7 @@ def step_windows(dev, mode, n_set, bs, windows, steps):
     aug = TrainAugment(harness.CIFAR_MEAN, harness.CIFAR_STD, seed=harness.augment_seed(42, 0))
     k = [0]
     gstep = None
+    extra = {}
     if mode == "parent":
         opt = torch.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=0.01)
         red = GradReducer(m)
@@ -128,7 +147,42 @@ def step_windows(dev, mode, n_set, bs, windows, steps):
                 tl, _ = teacher(view(nhwc, sel), return_features=True)
             return img, data.labels[sel].long(), tl
 
-        if mode == "eager":
+        if mode.startswith("cached"):
+            from spectre_vit.distillation import TeacherLogitCache
+            cache = TeacherLogitCache(n_set, c.num_classes, dev)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            calls = cache.fill(teacher, view, nhwc, batch_size=bs)
+            torch.cuda.synchronize()
+            extra["fill"] = {"seconds": round(time.perf_counter() - t0, 4), "teacher_batches": calls, "complete": cache.complete(),
+                             "cache_bytes": cache.logits.numel() * 4}
+
+            def student_view(sel):
+                img = aug(nhwc, sel, step=k[0])
+                k[0] += 1
+                return img, data.labels[sel].long()
+
+        if mode == "cached-eager":
+            opt = torch.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=0.01)
+            red = GradReducer(m)
+
+            def one(sel):
+                img, label = student_view(sel)
+                loss = crit(m(img), cache, label, index=sel)
+                red.zero_grad()
+                loss.backward()
+                red.finish()
+                opt.step()
+        elif mode == "cached-graph":
+            from spectre_vit.graph import GraphedDistillStep
+            from spectre_vit.optim import FusedAdamW
+            opt = FusedAdamW(m.parameters(), lr=1e-4, weight_decay=0.01, capturable=True, static_grads=True)
+            sel0 = next(iter(data.index_batches(bs, True, torch.Generator().manual_seed(1))))
+            gstep = GraphedDistillStep(m, opt, crit, *student_view(sel0), autocast_dtype=None, teacher_cache=cache, example_index=sel0)
+
+            def one(sel):
+                gstep(*student_view(sel), index=sel)
+        elif mode == "eager":
             opt = torch.optim.AdamW(m.parameters(), lr=1e-4, weight_decay=0.01)
             red = GradReducer(m)
 
@@ -164,7 +218,7 @@ def step_windows(dev, mode, n_set, bs, windows, steps):
 
     try:
         window()
-        return {"ms_per_step": [window() for _ in range(windows)], "steps_per_window": steps}
+        return dict({"ms_per_step": [window() for _ in range(windows)], "steps_per_window": steps}, **extra)
     finally:
         if gstep is not None:
             gstep.close()
@@ -172,7 +226,7 @@ def step_windows(dev, mode, n_set, bs, windows, steps):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--mode", choices=("kernels", "eager", "graph", "parent"), default="kernels")
+    ap.add_argument("--mode", choices=("kernels", "eager", "graph", "cached-eager", "cached-graph", "parent"), default="kernels")
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--steps", type=int, default=97)
     ap.add_argument("--rounds", type=int, default=4)

@@ -188,11 +188,16 @@ constexpr int DL_MAX_WG = 64;
 // A teacher probability that underflows contributes 0 (the limit), where log(softmax) gives 0 * -inf.
 // Rows are joined as in ce_fwd_kernel: per-workgroup partial sums, the last workgroup to arrive adds them in a fixed order and re-arms
 // the counter.
+// INDEXED (spv_distill_loss_idx_fwd): t is the resident logit cache [n_cache][C] and row r's teacher row is t + index[r] * C -- the one
+// difference, so the indexed launch returns the bits of the dense launch on cache[index].  A row whose index lies outside [0, n_cache)
+// forms no cache address: the wave runs the row body on the student row in the teacher's place (its CE and the student's two
+// log-sum-exps are the true ones) and then poisons what depends on the teacher: the row's soft term and lse3[2][r].
+template <bool INDEXED>
 __global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
-                                                                 const int64_t* __restrict__ labels, float* __restrict__ lse3,
-                                                                 float* __restrict__ out3, float* __restrict__ partial,
-                                                                 unsigned* __restrict__ counter, int rows, int C, float T, float w_soft,
-                                                                 float w_ce) {
+                                                                 const int64_t* __restrict__ index, const int64_t* __restrict__ labels,
+                                                                 float* __restrict__ lse3, float* __restrict__ out3,
+                                                                 float* __restrict__ partial, unsigned* __restrict__ counter, int rows,
+                                                                 int n_cache, int C, float T, float w_soft, float w_ce) {
     __shared__ float ws[2][DL_WAVES];
     __shared__ bool last;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -201,6 +206,12 @@ __global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __
     for (int r = blockIdx.x * DL_WAVES + wave; r < rows; r += gridDim.x * DL_WAVES) {
         const float* zr = z + (size_t)r * C;
         const float* tr = t + (size_t)r * C;
+        bool held = true;   // wave uniform
+        if constexpr (INDEXED) {
+            const int64_t row = index[r];
+            held = row >= 0 && row < (int64_t)n_cache;
+            tr = held ? t + (size_t)row * C : zr;
+        }
         float mz = -INFINITY, mt = -INFINITY, dmax = 0.0f;
         for (int c = lane; c < C; c += 64) {
             const float a = zr[c], b = tr[c];
@@ -235,8 +246,8 @@ __global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __
         if (lane == 0) {
             lse3[r] = lz;
             lse3[rows + r] = lzt;
-            lse3[2 * rows + r] = ltt;
-            acc_soft += pu / s3 - gap;
+            lse3[2 * rows + r] = held ? ltt : __builtin_nanf("");
+            acc_soft += held ? pu / s3 - gap : __builtin_nanf("");
             acc_ce += (y >= 0 && y < C) ? lz - zr[y] : __builtin_nanf("");   // a label outside [0, C) poisons the loss instead of reading wild
         }
     }
@@ -275,19 +286,55 @@ __global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __
 }
 
 // dz = go / rows * (w_soft T (softmax(z / T) - softmax(t / T)) + w_ce (softmax(z) - onehot))
+// INDEXED: the teacher's element is t[index[r] * C + c]; a row whose index lies outside [0, n_cache) reads nothing of t and is NaN.
+template <bool INDEXED>
 __global__ __launch_bounds__(DL_THREADS) void distill_bwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
-                                                                 const int64_t* __restrict__ labels, const float* __restrict__ lse3,
-                                                                 const float* __restrict__ go, float* __restrict__ dz, int rows, int C,
-                                                                 float T, float w_soft, float w_ce) {
+                                                                 const int64_t* __restrict__ index, const int64_t* __restrict__ labels,
+                                                                 const float* __restrict__ lse3, const float* __restrict__ go,
+                                                                 float* __restrict__ dz, int rows, int n_cache, int C, float T,
+                                                                 float w_soft, float w_ce) {
     const float scale = go[0] / (float)rows, invT = 1.0f / T;
     const float ks = w_soft * T;
     const int64_t total = (int64_t)rows * C;
     for (int64_t e = (int64_t)blockIdx.x * DL_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * DL_THREADS) {
         const int r = (int)(e / C), c = (int)(e - (int64_t)r * C);
         const float a = z[e];
-        const float q = expf(a * invT - lse3[rows + r]), p = expf(t[e] * invT - lse3[2 * rows + r]);
+        float b;
+        if constexpr (INDEXED) {
+            const int64_t row = index[r];
+            if (row < 0 || row >= (int64_t)n_cache) {
+                dz[e] = __builtin_nanf("");
+                continue;
+            }
+            b = t[(size_t)row * C + c];
+        } else {
+            b = t[e];
+        }
+        const float q = expf(a * invT - lse3[rows + r]), p = expf(b * invT - lse3[2 * rows + r]);
         const float s = expf(a - lse3[r]);
         dz[e] = (ks * (q - p) + w_ce * (s - (labels[r] == c ? 1.0f : 0.0f))) * scale;
+    }
+}
+
+// ================================================================ resident teacher logits
+constexpr int LC_THREADS = 256;
+
+// cache[index[r]][:] = logits[r][:], V floats per lane (V = 4: 16-byte loads and stores, rows of a multiple of 16 bytes at 16-byte
+// aligned bases; V = 1: everything else, e.g. 10 classes = 40-byte rows).  A row whose index lies outside [0, n_cache) is skipped:
+// nothing is read of it and nothing written.  Plain stores: when an index repeats, one of its rows wins.
+template <int V>
+__global__ __launch_bounds__(LC_THREADS) void logit_cache_store_kernel(float* __restrict__ cache, const int64_t* __restrict__ index,
+                                                                       const float* __restrict__ logits, int rows, int n_cache, int C) {
+    const int per_row = C / V;
+    const int64_t total = (int64_t)rows * per_row;
+    for (int64_t e = (int64_t)blockIdx.x * LC_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * LC_THREADS) {
+        const int r = (int)(e / per_row), c = (int)(e - (int64_t)r * per_row) * V;
+        const int64_t row = index != nullptr ? index[r] : (int64_t)r;
+        if (row < 0 || row >= (int64_t)n_cache) continue;
+        const float* s = logits + (size_t)r * C + c;
+        float* d = cache + (size_t)row * C + c;
+        if constexpr (V == 4) *reinterpret_cast<float4*>(d) = *reinterpret_cast<const float4*>(s);
+        else *d = *s;
     }
 }
 
@@ -347,8 +394,9 @@ extern "C" int spv_distill_loss_fwd(const float* student, const float* teacher, 
                                     float* workspace, int rows, int classes, float T, float w_soft, float w_ce, void* stream) {
     if (int rc = distill_check("spv_distill_loss_fwd", student, teacher, labels, lse3, out3, workspace, rows, classes, T, w_soft, w_ce)) return rc;
     const int wgs = std::min(cdiv(rows, DL_WAVES), DL_MAX_WG);
-    hipLaunchKernelGGL(distill_fwd_kernel, dim3(wgs), dim3(DL_THREADS), 0, static_cast<hipStream_t>(stream), student, teacher, labels, lse3,
-                       out3, workspace, reinterpret_cast<unsigned*>(workspace + 2 * DL_MAX_WG), rows, classes, T, w_soft, w_ce);
+    hipLaunchKernelGGL(distill_fwd_kernel<false>, dim3(wgs), dim3(DL_THREADS), 0, static_cast<hipStream_t>(stream), student, teacher,
+                       (const int64_t*)nullptr, labels, lse3, out3, workspace, reinterpret_cast<unsigned*>(workspace + 2 * DL_MAX_WG), rows,
+                       0, classes, T, w_soft, w_ce);
     SPV_LAUNCH_CHECK("spv_distill_loss_fwd");
     return 0;
 }
@@ -358,8 +406,60 @@ extern "C" int spv_distill_loss_bwd(const float* student, const float* teacher, 
                                     void* stream) {
     if (int rc = distill_check("spv_distill_loss_bwd", student, teacher, labels, lse3, grad_out, dlogits, rows, classes, T, w_soft, w_ce)) return rc;
     const int64_t total = (int64_t)rows * classes;
-    hipLaunchKernelGGL(distill_bwd_kernel, dim3((unsigned)std::min<int64_t>((total + DL_THREADS - 1) / DL_THREADS, 1024)), dim3(DL_THREADS), 0,
-                       static_cast<hipStream_t>(stream), student, teacher, labels, lse3, grad_out, dlogits, rows, classes, T, w_soft, w_ce);
+    hipLaunchKernelGGL(distill_bwd_kernel<false>, dim3((unsigned)std::min<int64_t>((total + DL_THREADS - 1) / DL_THREADS, 1024)),
+                       dim3(DL_THREADS), 0, static_cast<hipStream_t>(stream), student, teacher, (const int64_t*)nullptr, labels, lse3, grad_out,
+                       dlogits, rows, 0, classes, T, w_soft, w_ce);
     SPV_LAUNCH_CHECK("spv_distill_loss_bwd");
+    return 0;
+}
+
+// ---- the same loss with the teacher's rows read from the resident cache through the batch's index
+static int distill_idx_check(const char* name, const void* index, int n_cache) {
+    SPV_CHECK(index != nullptr, "%s: index missing", name);
+    SPV_CHECK(n_cache > 0, "%s: empty cache (n_cache=%d)", name, n_cache);
+    return 0;
+}
+
+extern "C" int spv_distill_loss_idx_fwd(const float* student, const float* cache, const int64_t* index, const int64_t* labels, float* lse3,
+                                        float* out3, float* workspace, int rows, int n_cache, int classes, float T, float w_soft, float w_ce,
+                                        void* stream) {
+    if (int rc = distill_check("spv_distill_loss_idx_fwd", student, cache, labels, lse3, out3, workspace, rows, classes, T, w_soft, w_ce)) return rc;
+    if (int rc = distill_idx_check("spv_distill_loss_idx_fwd", index, n_cache)) return rc;
+    const int wgs = std::min(cdiv(rows, DL_WAVES), DL_MAX_WG);
+    hipLaunchKernelGGL(distill_fwd_kernel<true>, dim3(wgs), dim3(DL_THREADS), 0, static_cast<hipStream_t>(stream), student, cache, index,
+                       labels, lse3, out3, workspace, reinterpret_cast<unsigned*>(workspace + 2 * DL_MAX_WG), rows, n_cache, classes, T,
+                       w_soft, w_ce);
+    SPV_LAUNCH_CHECK("spv_distill_loss_idx_fwd");
+    SPV_COUNT_PATH(SPV_PATH_DISTILL_CACHED);
+    return 0;
+}
+
+extern "C" int spv_distill_loss_idx_bwd(const float* student, const float* cache, const int64_t* index, const int64_t* labels,
+                                        const float* lse3, const float* grad_out, float* dlogits, int rows, int n_cache, int classes, float T,
+                                        float w_soft, float w_ce, void* stream) {
+    if (int rc = distill_check("spv_distill_loss_idx_bwd", student, cache, labels, lse3, grad_out, dlogits, rows, classes, T, w_soft, w_ce)) return rc;
+    if (int rc = distill_idx_check("spv_distill_loss_idx_bwd", index, n_cache)) return rc;
+    const int64_t total = (int64_t)rows * classes;
+    hipLaunchKernelGGL(distill_bwd_kernel<true>, dim3((unsigned)std::min<int64_t>((total + DL_THREADS - 1) / DL_THREADS, 1024)),
+                       dim3(DL_THREADS), 0, static_cast<hipStream_t>(stream), student, cache, index, labels, lse3, grad_out, dlogits, rows,
+                       n_cache, classes, T, w_soft, w_ce);
+    SPV_LAUNCH_CHECK("spv_distill_loss_idx_bwd");
+    return 0;
+}
+
+extern "C" int spv_logit_cache_store(float* cache, const int64_t* index, const float* logits, int rows, int n_cache, int classes,
+                                     void* stream) {
+    SPV_CHECK(rows > 0 && n_cache > 0 && classes > 0, "spv_logit_cache_store: empty (rows=%d n_cache=%d classes=%d)", rows, n_cache, classes);
+    SPV_CHECK(cache != nullptr && logits != nullptr, "spv_logit_cache_store: cache / logits missing");
+    SPV_CHECK(index != nullptr || rows <= n_cache, "spv_logit_cache_store: index == NULL writes rows 0..rows-1, but rows=%d > n_cache=%d", rows,
+              n_cache);
+    SPV_CHECK(((uintptr_t)cache & 3) == 0 && ((uintptr_t)logits & 3) == 0, "spv_logit_cache_store: cache / logits must be 4-byte aligned");
+    const bool vec = classes % 4 == 0 && (((uintptr_t)cache | (uintptr_t)logits) & 15) == 0;
+    const int64_t total = (int64_t)rows * (vec ? classes / 4 : classes);
+    const dim3 grid((unsigned)std::min<int64_t>((total + LC_THREADS - 1) / LC_THREADS, 1024)), block(LC_THREADS);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (vec) hipLaunchKernelGGL(logit_cache_store_kernel<4>, grid, block, 0, st, cache, index, logits, rows, n_cache, classes);
+    else hipLaunchKernelGGL(logit_cache_store_kernel<1>, grid, block, 0, st, cache, index, logits, rows, n_cache, classes);
+    SPV_LAUNCH_CHECK("spv_logit_cache_store");
     return 0;
 }

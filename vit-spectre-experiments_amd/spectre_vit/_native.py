@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("SPV_LIB_PATH") or os.path.join(os.path.dirname(_HERE)
 c_vp, c_i, c_i64, c_u64, c_f, c_d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_uint64, ctypes.c_float, ctypes.c_double
 
 # indices of include/spv.h's SPV_PATH_* enum (dispatch census, test aid)
-PATH = dict(gemm_strip=0, gemm_strip_acc=1, gemm_tn=2, tail_lc=3, tail_up=4, tail_ln=5, fnet_mfma=6, gather_lds=7, gemm_tn_wide=9,
+PATH = dict(gemm_strip=0, gemm_strip_acc=1, gemm_tn=2, tail_lc=3, tail_up=4, tail_ln=5, fnet_mfma=6, gather_lds=7, distill_cached=8, gemm_tn_wide=9,
             gemm_tn_batch=10, gemm_strip_pool=11, permut_row0=12, gemm_rows=13,
             spectrum=14, conv_fwd=15, conv_dgrad=16, conv_wgrad=17, token_pool=18, token_unpool=19, attn_row0_fwd=20, attn_row0_bwd=21, augment=22, teacher_view=23)
 
@@ -127,6 +127,9 @@ SIGNATURES = {
     "spv_distill_loss_workspace_floats": [],
     "spv_distill_loss_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_f, c_f, c_f, c_vp],
     "spv_distill_loss_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_f, c_f, c_f, c_vp],
+    "spv_logit_cache_store": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp],
+    "spv_distill_loss_idx_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_f, c_f, c_f, c_vp],
+    "spv_distill_loss_idx_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_f, c_f, c_f, c_vp],
     "spv_eval_head_stats_words": [],
     "spv_eval_head": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp],
 }

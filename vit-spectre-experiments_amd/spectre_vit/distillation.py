@@ -10,6 +10,8 @@ The paired-view step (reference train.py:139-141, 298-361) on the HIP path (csrc
 ``TeacherView`` is the teacher's transform -- Resize(256, BICUBIC) -> CenterCrop(224) -> ToTensor -> Normalize of the raw 8-bit
 sample (train.py:92-100), Pillow's integer resampling bit for bit -- read from the resident uint8 NHWC set through the batch's index;
 ``DistillationLoss`` is the soft-target + cross-entropy loss as one launch each way (``hip_ops.distill_loss``).
+``TeacherLogitCache`` keeps the frozen teacher's logits of every sample resident on the GPU (the teacher's view has no random op and
+the teacher is frozen, so they are a function of the sample index alone): filled once, read by ``DistillationLoss(..., index=...)``.
 """
 import math
 
@@ -216,8 +218,142 @@ class DistillationLoss(nn.Module):
         self.T, self.soft_target_loss_weight, self.ce_loss_weight = float(T), float(soft_target_loss_weight), float(ce_loss_weight)
         self.soft = self.ce = None
 
-    def forward(self, student_logits, teacher_logits, labels):
+    def forward(self, student_logits, teacher_logits, labels, index=None):
+        """index (int64 [rows], on the device): ``teacher_logits`` is then the resident cache -- a TeacherLogitCache or its [n, classes]
+        matrix -- and row r's teacher logits are cache[index[r]], read inside the kernel (``hip_ops.distill_loss_cached``)."""
         from . import hip_ops
+        if index is not None:
+            cache = teacher_logits.logits if isinstance(teacher_logits, TeacherLogitCache) else teacher_logits
+            loss, self.soft, self.ce = hip_ops.distill_loss_cached(student_logits, cache, index, labels, self.T,
+                                                                   self.soft_target_loss_weight, self.ce_loss_weight)
+            return loss
         loss, self.soft, self.ce = hip_ops.distill_loss(student_logits, teacher_logits, labels, self.T, self.soft_target_loss_weight,
                                                         self.ce_loss_weight)
         return loss
+
+
+# ---------------------------------------------------------------- the cached teacher (DESIGN.md section 4d)
+def fill_plan(n, batch_size, rank=0, world=1):
+    """The row blocks [start, stop) of an n-row cache that ``rank`` of ``world`` computes: the rows are cut into blocks of batch_size
+    (the last one short) and block k belongs to rank k % world, so a rank's j-th block is block j * world + rank -- round j of the
+    exchange.  Over all ranks every row is in exactly one block."""
+    n, batch_size, rank, world = int(n), int(batch_size), int(rank), int(world)
+    if n <= 0 or batch_size <= 0 or world <= 0 or not 0 <= rank < world:
+        raise ValueError(f"fill_plan: n={n}, batch_size={batch_size}, rank={rank}, world={world}")
+    blocks = (n + batch_size - 1) // batch_size
+    return [(k * batch_size, min((k + 1) * batch_size, n)) for k in range(rank, blocks, world)]
+
+
+class TeacherLogitCache:
+    """The frozen teacher's logits of every sample of a resident set, fp32 [n, classes] on the device, NaN until filled (an unfilled
+    row poisons the loss that reads it).  ``.logits`` is allocated once: a captured graph may read it by address.
+
+        cache = TeacherLogitCache(n_train, num_classes, device)
+        cache.fill(teacher, view, train_u8_nhwc)                  # ceil(n / 512) teacher calls, once
+        loss = criterion(student_logits, cache, labels, index=sel)"""
+
+    META = ("n", "classes", "resize", "crop", "tag")
+
+    def __init__(self, n, classes, device):
+        n, classes = int(n), int(classes)
+        if n <= 0 or classes <= 0:
+            raise ValueError(f"TeacherLogitCache: n={n}, classes={classes}")
+        self.n, self.classes = n, classes
+        self.logits = torch.full((n, classes), float("nan"), dtype=torch.float32, device=device)
+
+    def store(self, index, logits):
+        """logits fp32 [rows, classes] -> rows ``index`` (int64 [rows]; None: rows 0..rows-1) of the cache: one launch.  A row whose
+        index lies outside the cache is skipped by the kernel."""
+        from spectre_vit import _native
+        from spectre_vit.hip_ops import _p, _require_gpu, _stream
+        if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[1] != self.classes:
+            raise ValueError(f"TeacherLogitCache.store: fp32 logits [rows, {self.classes}] expected, got {logits.dtype} {tuple(logits.shape)}")
+        if index is not None and (index.dtype != torch.int64 or index.shape != logits.shape[:1]):
+            raise ValueError(f"TeacherLogitCache.store: index is an int64 vector of {logits.shape[0]} rows, got {index.dtype} {tuple(index.shape)}")
+        _require_gpu(self.logits, logits, index)
+        logits = logits.detach().contiguous()
+        index = None if index is None else index.contiguous()
+        _native.call("spv_logit_cache_store", _p(self.logits), _p(index), _p(logits), logits.shape[0], self.n, self.classes, _stream())
+
+    def fill(self, teacher, view, images_u8_nhwc, batch_size=512, rank=0, world=1, process_group=None, batch_hook=None):
+        """Every row of the cache: ``view(images, idx)`` -> ``teacher(img, return_features=True)[0].float()`` under no_grad -> ``store``,
+        over the row blocks of ``fill_plan``.  Draws from no torch generator.  world > 1: a rank computes its own blocks only, and round
+        by round the ranks exchange them with an all-gather (a copy: every rank ends with every row, bits unchanged).
+        batch_hook("teacher_fill", k, img_teacher, idx), k the block's number (test seam).  -> the teacher calls of this rank."""
+        if getattr(teacher, "training", False):
+            raise ValueError("TeacherLogitCache.fill: the teacher is in train mode -- its output is then not a function of the sample "
+                             "(dropout, batch statistics); call teacher.eval()")
+        if images_u8_nhwc.shape[0] != self.n:
+            raise ValueError(f"TeacherLogitCache.fill: {images_u8_nhwc.shape[0]} images for a cache of {self.n} rows")
+        dev = self.logits.device
+        mine = fill_plan(self.n, batch_size, rank, world)
+        rounds = ((self.n + batch_size - 1) // batch_size + world - 1) // world
+        calls = 0
+        for j in range(rounds):
+            out = None
+            if j < len(mine):
+                start, stop = mine[j]
+                idx = torch.arange(start, stop, dtype=torch.int64, device=dev)
+                with torch.no_grad():
+                    img = view(images_u8_nhwc, idx)
+                    if batch_hook is not None:
+                        batch_hook("teacher_fill", j * world + rank, img, idx)
+                    out = teacher(img, return_features=True)[0].float()
+                if out.shape != (stop - start, self.classes):
+                    raise ValueError(f"TeacherLogitCache.fill: the teacher returned {tuple(out.shape)} for {stop - start} samples of "
+                                     f"{self.classes} classes")
+                self.store(idx, out)
+                calls += 1
+            if world > 1:
+                self._exchange(j, out, batch_size, rank, world, process_group)
+        return calls
+
+    def _exchange(self, j, out, batch_size, rank, world, process_group):
+        """round j: every rank hands in its block (padded to batch_size rows) and stores the others' at their rows"""
+        import torch.distributed as dist
+        dev = self.logits.device
+        # gloo gathers host tensors; RCCL device tensors.  Either way the rows are copied, never summed.
+        where = torch.device("cpu") if dist.get_backend(process_group) == "gloo" else dev
+        send = torch.full((batch_size, self.classes), float("nan"), dtype=torch.float32, device=where)
+        if out is not None:
+            send[:out.shape[0]].copy_(out)
+        recv = [torch.empty_like(send) for _ in range(world)]
+        dist.all_gather(recv, send, group=process_group)
+        for r in range(world):
+            start = (j * world + r) * batch_size
+            stop = min(start + batch_size, self.n)
+            if r != rank and start < stop:
+                self.store(torch.arange(start, stop, dtype=torch.int64, device=dev), recv[r][:stop - start].to(dev))
+
+    def complete(self):
+        """no NaN left: one host read"""
+        return not bool(torch.isnan(self.logits).any().item())
+
+    def save(self, path, **meta):
+        """torch.save of {"logits", "meta"}; meta: resize, crop, tag (what the rows were computed from), n and classes are the cache's"""
+        unknown = set(meta) - set(self.META[2:])
+        if unknown:
+            raise ValueError(f"TeacherLogitCache.save: unknown meta field(s) {sorted(unknown)} (resize, crop, tag)")
+        m = {"n": self.n, "classes": self.classes, "resize": None, "crop": None, "tag": None}
+        m.update(meta)
+        torch.save({"logits": self.logits.detach().cpu(), "meta": m}, path)
+
+    @classmethod
+    def load(cls, path, device, **expect):
+        """The cache saved at ``path`` on ``device``.  Every field of ``expect`` (n, classes, resize, crop, tag) must equal the file's;
+        a file with NaN rows is refused."""
+        blob = torch.load(path, map_location="cpu", weights_only=True)
+        logits, meta = blob["logits"], blob["meta"]
+        for k, v in expect.items():
+            if k not in cls.META:
+                raise ValueError(f"TeacherLogitCache.load: unknown meta field {k!r}")
+            if meta.get(k) != v:
+                raise ValueError(f"TeacherLogitCache.load: {path} was saved with {k}={meta.get(k)!r}, expected {k}={v!r}")
+        if logits.dtype != torch.float32 or tuple(logits.shape) != (meta["n"], meta["classes"]):
+            raise ValueError(f"TeacherLogitCache.load: {path} holds {logits.dtype} {tuple(logits.shape)}, its meta says fp32 "
+                             f"[{meta['n']}, {meta['classes']}]")
+        if bool(torch.isnan(logits).any()):
+            raise ValueError(f"TeacherLogitCache.load: {path} is incomplete ({int(torch.isnan(logits).any(dim=1).sum())} rows hold NaN)")
+        cache = cls(meta["n"], meta["classes"], device)
+        cache.logits.copy_(logits)
+        return cache

@@ -208,22 +208,41 @@ class GraphedDPStep(GraphedTrainStep):
 
 class GraphedDistillStep(GraphedTrainStep):
     """The distillation step of reference train.py:298-361 replayed from one graph: zero_grad, student forward, the fused loss
-    (``spectre_vit.distillation.DistillationLoss``) against a fixed-address ``teacher_logits`` buffer, backward, optimizer.  The teacher
-    is NOT captured -- a real backbone is arbitrary user code -- it runs eagerly under no_grad in front of the replay, on the step's
-    stream:
+    (``spectre_vit.distillation.DistillationLoss``), backward, optimizer.  Two forms:
+
+    teacher logits per step -- the loss reads a fixed-address ``teacher_logits`` buffer.  The teacher is NOT captured -- a real backbone
+    is arbitrary user code -- it runs eagerly under no_grad in front of the replay, on the step's stream:
 
         step = GraphedDistillStep(model, optimizer, DistillationLoss(), img, labels, teacher_logits, autocast_dtype=None)
         loss = step(img, labels, teacher_logits)      # step.soft / step.ce / step.out: the other captured outputs
 
+    cached teacher -- the loss reads the resident ``TeacherLogitCache`` through a fixed-address int64 ``index`` buffer the step owns; a
+    step is the index copy and the replay, no teacher and no view kernel:
+
+        step = GraphedDistillStep(model, optimizer, DistillationLoss(), img, labels, teacher_cache=cache, example_index=sel)
+        loss = step(img, labels, index=sel)
+
     Single process only: a graph-replayed data-parallel distillation rank is not built."""
 
-    def __init__(self, model, optimizer, criterion, example_img, example_labels, example_teacher_logits, autocast_dtype=None, warmup=3,
-                 process_group=None):
+    def __init__(self, model, optimizer, criterion, example_img, example_labels, example_teacher_logits=None, autocast_dtype=None, warmup=3,
+                 process_group=None, *, teacher_cache=None, example_index=None):
         import torch.distributed as dist
+        if (example_teacher_logits is None) == (teacher_cache is None):
+            raise ValueError("GraphedDistillStep takes example_teacher_logits (the teacher runs in front of every replay) or "
+                             "teacher_cache (its logits are resident), one of the two")
+        if (teacher_cache is None) != (example_index is None):
+            raise ValueError("GraphedDistillStep: teacher_cache and example_index go together")
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
             raise RuntimeError("GraphedDistillStep is the single-process step: GraphedDPStep is not built for distillation "
                                "(run the ranks of a torch.distributed job with the eager step)")
-        self.teacher_logits = example_teacher_logits.detach().clone()
+        self.teacher_cache = teacher_cache
+        if teacher_cache is None:
+            self.teacher_logits, self.index = example_teacher_logits.detach().clone(), None
+        else:
+            if example_index.dtype != torch.int64 or example_index.shape != example_labels.shape[:1]:
+                raise ValueError(f"GraphedDistillStep: example_index is an int64 vector of the batch's {example_labels.shape[0]} rows, got "
+                                 f"{example_index.dtype} {tuple(example_index.shape)}")
+            self.teacher_logits, self.index = None, example_index.detach().clone()
         super().__init__(model, optimizer, criterion, example_img, example_labels, autocast_dtype=autocast_dtype, warmup=warmup,
                          process_group=process_group)
 
@@ -232,7 +251,10 @@ class GraphedDistillStep(GraphedTrainStep):
         self.reducer.zero_grad()
         with torch.autocast("cuda", dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None):
             out = self.model(self.img)
-        loss = self.criterion(out, self.teacher_logits, self.labels)   # on the fp32 logits, outside autocast
+        if self.index is None:
+            loss = self.criterion(out, self.teacher_logits, self.labels)   # on the fp32 logits, outside autocast
+        else:
+            loss = self.criterion(out, self.teacher_cache, self.labels, index=self.index)
         loss.backward(self._one)
         return loss, out
 
@@ -244,7 +266,14 @@ class GraphedDistillStep(GraphedTrainStep):
         super()._build(warmup)
         self.soft, self.ce = self.criterion.soft, self.criterion.ce
 
-    def __call__(self, img=None, labels=None, teacher_logits=None):
-        if teacher_logits is not None and not self._closed:
-            self.teacher_logits.copy_(teacher_logits, non_blocking=True)
+    def __call__(self, img=None, labels=None, teacher_logits=None, *, index=None):
+        if not self._closed:
+            if teacher_logits is not None:
+                if self.teacher_logits is None:
+                    raise ValueError("this step reads the teacher cache: pass index=, not teacher logits")
+                self.teacher_logits.copy_(teacher_logits, non_blocking=True)
+            if index is not None:
+                if self.index is None:
+                    raise ValueError("this step takes the teacher's logits per step: it was built without teacher_cache")
+                self.index.copy_(index, non_blocking=True)
         return super().__call__(img, labels)

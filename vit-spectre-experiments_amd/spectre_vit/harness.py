@@ -323,10 +323,31 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     return model, history
 
 
+def _teacher_cache(teacher, view, train_nhwc, classes, device, path, resize, crop, rank, world, batch_hook, batch_size):
+    """train_distill's cached teacher: loaded from `path` when that file exists and was saved for this set size, class count and view;
+    filled otherwise (every rank its share of the rows, then exchanged) and saved by rank 0.  -> (cache, the "TeacherCache" record)"""
+    from spectre_vit.distillation import TeacherLogitCache
+    n = train_nhwc.shape[0]
+    tag = type(teacher).__name__
+    if path is not None and os.path.exists(path):
+        cache = TeacherLogitCache.load(path, device, n=n, classes=int(classes), resize=int(resize), crop=int(crop), tag=tag)
+        calls, loaded = 0, True
+    else:
+        cache = TeacherLogitCache(n, classes, device)
+        calls = cache.fill(teacher, view, train_nhwc, batch_size=batch_size, rank=rank, world=world, batch_hook=batch_hook)
+        loaded = False
+    if not cache.complete():
+        raise RuntimeError("the teacher cache holds NaN rows after its fill: the teacher returned NaN, or rows were left out")
+    if path is not None and not loaded and rank == 0:
+        cache.save(path, resize=int(resize), crop=int(crop), tag=tag)
+    return cache, {"rows": n, "teacher_batches": calls, "seconds": 0.0, "loaded": loaded}
+
+
 def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
                   use_amp=False, graph=False, augment=True, teacher=None, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75,
                   resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False,
-                  lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False):
+                  lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False, cache_teacher=False,
+                  teacher_cache_path=None):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -338,10 +359,17 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     sample (train.py:365-383).  The three per-batch losses the reference logs (train.py:355-359) are kept on the device and written
     once per epoch as {"step", "Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE"} lines: no host synchronisation per step.
     batch_hook(kind, step, img, label), kind "train" / "teacher" / "val" (test seam).  graph_eval, lr_schedule, warmup_steps, eta_min,
-    clip_grad_norm, skip_nonfinite: as in train()."""
+    clip_grad_norm, skip_nonfinite: as in train().
+    cache_teacher=True: the teacher's view has no random op and the teacher is frozen, so its logits are a function of the sample alone;
+    they are computed once before epoch 0 into a resident spectre_vit.distillation.TeacherLogitCache (sharded over the ranks; loaded from
+    teacher_cache_path when that file exists and matches, saved there by rank 0 otherwise), a {"TeacherCache": ...} line is logged, and
+    the epochs call neither the view nor the teacher: the loss reads the cache through the batch's index (no "teacher" hook then; the
+    fill calls batch_hook("teacher_fill", block, img_teacher, index)).  Eager, as a data-parallel rank, and graph=True."""
     from spectre_vit import _native
     c = parse_config(config_path)
     world = int(os.environ.get("WORLD_SIZE", "1"))
+    if teacher_cache_path is not None and not cache_teacher:
+        raise ValueError("teacher_cache_path names the file of the cached teacher's logits: it needs cache_teacher=True")
     if graph and world > 1:
         raise ValueError("graph=True replays the single-process distillation step (GraphedDistillStep); a data-parallel rank runs it eagerly")
     if not _native.call("spv_teacher_view_supported", int(c.in_channels), int(c.img_size), int(resize), int(crop)):
@@ -396,6 +424,15 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     global_step = 0
     autocast_dtype = torch.bfloat16 if use_amp else None
     start = time.perf_counter()
+    cache = None
+    if cache_teacher:
+        # filled in blocks of the training batch: the teacher then sees the batch shape it would see inside the epochs
+        cache, cache_rec = _teacher_cache(teacher, view, train_nhwc, c.num_classes, device, teacher_cache_path, resize, crop, rank, world,
+                                          batch_hook, batch_size)
+        cache_rec["seconds"] = time.perf_counter() - start
+        if rank == 0:
+            log_f.write(json.dumps({"TeacherCache": cache_rec}) + "\n")
+            log_f.flush()
     for epoch in range(epochs):
         model.train()
         correct = torch.zeros((), device=device, dtype=torch.int64)
@@ -408,27 +445,34 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                 img = aug(train_nhwc, sel, step=global_step)
             else:
                 img = (train_set.images[sel].float() / 255.0 - train_set.mean) / train_set.std
-            img_teacher = view(train_nhwc, sel)
+            if cache is None:
+                img_teacher = view(train_nhwc, sel)
             if batch_hook is not None:
                 batch_hook("train", global_step, img, label)
-                batch_hook("teacher", global_step, img_teacher, label)
+                if cache is None:
+                    batch_hook("teacher", global_step, img_teacher, label)
             global_step += 1
-            with torch.no_grad():   # train.py:326-327
-                teacher_logits, _ = teacher(img_teacher, return_features=True)
-            teacher_logits = teacher_logits.float()
+            if cache is None:
+                with torch.no_grad():   # train.py:326-327
+                    teacher_logits, _ = teacher(img_teacher, return_features=True)
+                teacher_logits = teacher_logits.float()
             if graph:
                 if gstep is None:   # built on the first batch; its warm-up step WAS this batch's training step
                     from spectre_vit.graph import GraphedDistillStep
-                    gstep = GraphedDistillStep(model, optimizer, criterion, img, label.long(), teacher_logits, autocast_dtype=autocast_dtype,
-                                               warmup=1)
+                    teacher_args = dict(example_teacher_logits=teacher_logits) if cache is None else dict(teacher_cache=cache, example_index=sel)
+                    gstep = GraphedDistillStep(model, optimizer, criterion, img, label.long(), autocast_dtype=autocast_dtype, warmup=1,
+                                               **teacher_args)
                     loss, soft, ce, y_pred = gstep.warm_loss, gstep.warm_soft, gstep.warm_ce, gstep.warm_out
                 else:
-                    loss = gstep(img, label.long(), teacher_logits)
+                    loss = gstep(img, label.long(), teacher_logits) if cache is None else gstep(img, label.long(), index=sel)
                     soft, ce, y_pred = gstep.soft, gstep.ce, gstep.out
             else:
                 with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
                     y_pred = model(img)
-                loss = criterion(y_pred.float(), teacher_logits, label.long())
+                if cache is None:
+                    loss = criterion(y_pred.float(), teacher_logits, label.long())
+                else:
+                    loss = criterion(y_pred.float(), cache, label.long(), index=sel)
                 soft, ce = criterion.soft, criterion.ce
                 reducer.zero_grad()
                 loss.backward()
@@ -512,6 +556,11 @@ def build_parser():
                     help="the reference's distillation loop with its two views per sample (train_distill): the student's augmented view "
                          "and the teacher's Resize(256) -> CenterCrop(224) view, fused KD loss; with --graph, --no-augment")
     ap.add_argument("--no-augment", action="store_true", help="--distill-paired: the student's view is ToTensor + Normalize only")
+    ap.add_argument("--cache-teacher", action="store_true",
+                    help="--distill-paired: compute the frozen teacher's logits of every sample once, keep them on the GPU and read them "
+                         "by index (no teacher view and no teacher forward inside the epochs)")
+    ap.add_argument("--teacher-cache", default=None, metavar="PATH",
+                    help="--cache-teacher: load the logits from PATH when it exists and matches, save them there otherwise")
     ap.add_argument("--graph-eval", action="store_true",
                     help="validate through a graph-replayed InferenceSession with on-device metrics (spectre_vit.inference)")
     ap.add_argument("--lr-schedule", default=None, choices=("cosine",),
@@ -530,7 +579,7 @@ def main(argv=None):
                    skip_nonfinite=a.skip_nonfinite)
     if a.distill_paired:
         train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out,
-                      graph_eval=a.graph_eval, **control)
+                      graph_eval=a.graph_eval, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache, **control)
         return
     train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph,
           model=a.model, augment=a.augment, graph_eval=a.graph_eval, **control)

@@ -1220,6 +1220,52 @@ def distill_loss(student_logits, teacher_logits, labels, T=2.0, w_soft=0.25, w_c
     return DistillLossFn.apply(student_logits, teacher_logits, labels, T, w_soft, w_ce)
 
 
+class DistillLossIdxFn(torch.autograd.Function):
+    """DistillLossFn with the teacher's rows read from the resident logit cache [n_cache, classes] through the batch's index (int64
+    [rows]): the bits of DistillLossFn on cache[index], without the gather.  The cache and the index are read by address -- a captured
+    launch follows whatever they hold at replay.  A row whose index lies outside the cache, or whose cache row was never filled (NaN),
+    poisons the loss."""
+
+    @staticmethod
+    def forward(ctx, student_logits, cache, index, labels, T, w_soft, w_ce):
+        _require_gpu(student_logits, cache, index, labels)
+        z = student_logits
+        if (z.dim() != 2 or z.dtype != torch.float32 or cache.dim() != 2 or cache.dtype != torch.float32 or cache.shape[1] != z.shape[1]
+                or cache.shape[0] < 1 or not cache.is_contiguous() or labels.dtype != torch.int64 or labels.shape != z.shape[:1]
+                or index.dtype != torch.int64 or index.shape != z.shape[:1]):
+            raise ValueError("distill_loss_cached: fp32 student logits [rows, classes], a contiguous fp32 cache [n, classes], int64 index "
+                             "[rows] and int64 labels [rows] expected")
+        z, t, idx, y = z.contiguous(), cache.detach(), index.contiguous(), labels.contiguous()
+        rows, C = z.shape
+        lse = torch.empty((3, rows), dtype=torch.float32, device=z.device)
+        out = torch.empty((3,), dtype=torch.float32, device=z.device)
+        _native.call("spv_distill_loss_idx_fwd", _p(z), _p(t), _p(idx), _p(y), _p(lse), _p(out),
+                     _p(_zero_workspace(_distill_workspaces, z.device, "spv_distill_loss_workspace_floats")), rows, t.shape[0], C, float(T),
+                     float(w_soft), float(w_ce), _stream())
+        ctx.save_for_backward(z, y, lse)
+        ctx.resident = (t, idx)   # read by address again in the backward; not save_for_backward: the cache is written in place by design
+        ctx.consts = (float(T), float(w_soft), float(w_ce))
+        loss, soft, ce = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(soft, ce)
+        return loss, soft, ce
+
+    @staticmethod
+    def backward(ctx, go, _gsoft, _gce):
+        z, y, lse = ctx.saved_tensors
+        t, idx = ctx.resident
+        T, w_soft, w_ce = ctx.consts
+        go = go.reshape(1).float().contiguous()
+        dz = torch.empty_like(z)
+        _native.call("spv_distill_loss_idx_bwd", _p(z), _p(t), _p(idx), _p(y), _p(lse), _p(go), _p(dz), z.shape[0], t.shape[0], z.shape[1], T,
+                     w_soft, w_ce, _stream())
+        return dz, None, None, None, None, None, None
+
+
+def distill_loss_cached(student_logits, cache, index, labels, T=2.0, w_soft=0.25, w_ce=0.75):
+    """distill_loss(student_logits, cache[index], labels, ...) without materialising cache[index]: (loss, soft, ce)"""
+    return DistillLossIdxFn.apply(student_logits, cache, index, labels, T, w_soft, w_ce)
+
+
 # ------------------------------------------------------------------------------------------------
 # baseline ViT pieces: plain Linear, GELU, softmax attention core  (reference vit.py:30-40)
 # ------------------------------------------------------------------------------------------------
