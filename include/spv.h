@@ -326,6 +326,22 @@ int spv_adamw_multi(const void* table, const int* chunk_tensor, const int* chunk
                     float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
                     float bias_correction1, float bias_correction2, const float* step_dev, void* stream);
 
+/* spv_adamw_multi plus an exponential moving average (EMA) of the weights, updated in the same thread from the registers that hold
+ * the new weight p' -- one more 4-byte read and write per element, no extra launch.  p, g, m, v and the step count come out bit for
+ * bit as from spv_adamw_multi.  ema_table: DEVICE array of one float* per tensor of `table` (the fp32 EMA buffer, shaped like p; a
+ * NULL entry: that tensor is not averaged).  Per averaged element
+ *     e' = fmaf(w_t, p' - e, e)          (the difference rounded to fp32, then one fused multiply-add: torch's e.lerp_(p', w_t))
+ *     w_t = ema_weight                                          ema_warmup == 0
+ *     w_t = max(ema_weight, 9.0f / (10.0f + s))                 ema_warmup != 0  (timm ModelEmaV2: decay = min(d, (1 + n) / (10 + n)))
+ * ema_weight = 1 - decay, formed in double and rounded once by the caller (as one_minus_beta1/2), in (0, 1].  s = this step's count,
+ * 1 on the first step: *step_dev when step_dev != NULL (so a replayed graph follows the warm-up), else ema_step passed by value.
+ * The caller initialises e (a copy of p gives e_1 = p_0 + w_1 (p_1 - p_0)).  An EMA buffer that is not 16-byte aligned is read and
+ * written element by element; the arithmetic, and so the result, is the same. */
+int spv_adamw_multi_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr,
+                        float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                        float bias_correction1, float bias_correction2, const float* step_dev, float* const* ema_table, float ema_weight,
+                        int ema_warmup, float ema_step, void* stream);
+
 /* ---- on-device step control: LR schedule, gradient clipping, non-finite skip --------------------------------
  * What the reference's loop does on the host around optimizer.step() -- CosineAnnealingLR (spectre_vit/repl/train.py:202-203),
  * GradScaler's dropped step on an inf / NaN gradient (train.py:205,236-238) and the usual torch.nn.utils.clip_grad_norm_ -- decided
@@ -375,6 +391,13 @@ int spv_step_control(const double* partials, int npartials, float* const* step_p
 int spv_adamw_multi_ctl(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, double base_lr,
                         float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
                         const float* step_dev, const spv_step_ctl* ctl, void* stream);
+
+/* spv_adamw_multi_ctl plus the moving average of spv_adamw_multi_ema (ema_table / ema_weight / ema_warmup as there; s = *step_dev, which
+ * spv_step_control advanced).  A dropped step (ctl->apply == 0) writes nothing, the average included. */
+int spv_adamw_multi_ctl_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, double base_lr,
+                            float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                            const float* step_dev, const spv_step_ctl* ctl, float* const* ema_table, float ema_weight, int ema_warmup,
+                            void* stream);
 
 /* ---- Walsh-Hadamard butterflies along the last axis -----------------------------------
  * spectre_vit/models/spectre/hadamar.py: fwht :12-32 / hadamard_transform :83-112 (mode 0, natural order; scale = n^-1/2

@@ -359,6 +359,20 @@ __global__ __launch_bounds__(256) void adamw_multi_kernel(const AdamTensor* __re
     const int n = sizes[t];
     adamw_chunk<false>(a, n, off, lr, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2, step_dev, 1.0f);
 }
+
+// The same launch with the weights' moving average updated from the registers that hold the new weight (spv_adamw_core.h: EMA).
+__global__ __launch_bounds__(256) void adamw_multi_ema_kernel(const AdamTensor* __restrict__ tab, const int* __restrict__ chunk_tensor,
+                                                              const int* __restrict__ chunk_off, const int* __restrict__ sizes, float lr,
+                                                              float beta1, float beta2, float omb1, float omb2, float eps, float wd,
+                                                              float bc1, float bc2, const float* __restrict__ step_dev,
+                                                              float* const* __restrict__ ema_tab, float ema_w, int ema_warmup, float ema_step) {
+    const int t = chunk_tensor[blockIdx.x];
+    const int off = chunk_off[blockIdx.x];
+    const AdamTensor a = tab[t];
+    const int n = sizes[t];
+    adamw_chunk<false, true>(a, n, off, lr, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2, step_dev, 1.0f, ema_tab[t], ema_w, ema_warmup,
+                             ema_step);
+}
 }  // namespace
 
 extern "C" int spv_adamw_multi(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr,
@@ -372,6 +386,26 @@ extern "C" int spv_adamw_multi(const void* table, const int* chunk_tensor, const
                        static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, lr, beta1, beta2, one_minus_beta1,
                        one_minus_beta2, eps, weight_decay, bias_correction1, bias_correction2, step_dev);
     SPV_LAUNCH_CHECK("spv_adamw_multi");
+    return 0;
+}
+
+extern "C" int spv_adamw_multi_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr,
+                                   float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                                   float bias_correction1, float bias_correction2, const float* step_dev, float* const* ema_table,
+                                   float ema_weight, int ema_warmup, float ema_step, void* stream) {
+    SPV_CHECK(nchunks >= 0, "spv_adamw_multi_ema: nchunks = %d", nchunks);
+    SPV_CHECK(table && chunk_tensor && chunk_off && sizes, "spv_adamw_multi_ema: null table");
+    SPV_CHECK(ema_table, "spv_adamw_multi_ema: null ema_table (use spv_adamw_multi for a group that is not averaged)");
+    SPV_CHECK(step_dev != nullptr || (bias_correction1 > 0.0f && bias_correction2 > 0.0f), "spv_adamw_multi_ema: bias corrections must be > 0");
+    SPV_CHECK(ema_weight > 0.0f && ema_weight <= 1.0f, "spv_adamw_multi_ema: ema_weight = %g must be in (0, 1]", (double)ema_weight);
+    SPV_CHECK(!ema_warmup || step_dev != nullptr || ema_step >= 1.0f, "spv_adamw_multi_ema: ema_step = %g must be >= 1 (the step count of this step)",
+              (double)ema_step);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(adamw_multi_ema_kernel, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, lr, beta1, beta2, one_minus_beta1,
+                       one_minus_beta2, eps, weight_decay, bias_correction1, bias_correction2, step_dev, ema_table, ema_weight, ema_warmup,
+                       ema_step);
+    SPV_LAUNCH_CHECK("spv_adamw_multi_ema");
     return 0;
 }
 

@@ -111,6 +111,22 @@ __global__ __launch_bounds__(256) void adamw_multi_ctl_kernel(const AdamTensor* 
     const int n = sizes[t];
     adamw_chunk<true>(a, n, off, lr, beta1, beta2, omb1, omb2, eps, wd, 0.0f, 0.0f, step_dev, ctl->clip_coef);
 }
+
+// The same launch with the weights' moving average (spv_adamw_core.h: EMA); a dropped step leaves the average where it is.
+__global__ __launch_bounds__(256) void adamw_multi_ctl_ema_kernel(const AdamTensor* __restrict__ tab, const int* __restrict__ chunk_tensor,
+                                                                  const int* __restrict__ chunk_off, const int* __restrict__ sizes, double base_lr,
+                                                                  float beta1, float beta2, float omb1, float omb2, float eps, float wd,
+                                                                  const float* __restrict__ step_dev, const spv_step_ctl* __restrict__ ctl,
+                                                                  float* const* __restrict__ ema_tab, float ema_w, int ema_warmup) {
+    if (ctl->apply == 0) return;
+    const float lr = (float)__dadd_rn(__dmul_rn(ctl->a, base_lr), ctl->b);
+    const int t = chunk_tensor[blockIdx.x];
+    const int off = chunk_off[blockIdx.x];
+    const AdamTensor a = tab[t];
+    const int n = sizes[t];
+    adamw_chunk<true, true>(a, n, off, lr, beta1, beta2, omb1, omb2, eps, wd, 0.0f, 0.0f, step_dev, ctl->clip_coef, ema_tab[t], ema_w,
+                            ema_warmup, 0.0f);
+}
 }  // namespace
 
 extern "C" int spv_grad_sumsq(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
@@ -155,5 +171,23 @@ extern "C" int spv_adamw_multi_ctl(const void* table, const int* chunk_tensor, c
                        static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, base_lr, beta1, beta2, one_minus_beta1,
                        one_minus_beta2, eps, weight_decay, step_dev, ctl);
     SPV_LAUNCH_CHECK("spv_adamw_multi_ctl");
+    return 0;
+}
+
+extern "C" int spv_adamw_multi_ctl_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
+                                       double base_lr, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                                       float weight_decay, const float* step_dev, const spv_step_ctl* ctl, float* const* ema_table,
+                                       float ema_weight, int ema_warmup, void* stream) {
+    SPV_CHECK(nchunks >= 0, "spv_adamw_multi_ctl_ema: nchunks = %d", nchunks);
+    SPV_CHECK(table && chunk_tensor && chunk_off && sizes, "spv_adamw_multi_ctl_ema: null table");
+    SPV_CHECK(step_dev && ctl, "spv_adamw_multi_ctl_ema: null step count / control block");
+    SPV_CHECK(ema_table, "spv_adamw_multi_ctl_ema: null ema_table (use spv_adamw_multi_ctl for a group that is not averaged)");
+    SPV_CHECK(base_lr >= 0.0, "spv_adamw_multi_ctl_ema: base_lr = %g must be >= 0", base_lr);
+    SPV_CHECK(ema_weight > 0.0f && ema_weight <= 1.0f, "spv_adamw_multi_ctl_ema: ema_weight = %g must be in (0, 1]", (double)ema_weight);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(adamw_multi_ctl_ema_kernel, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, base_lr, beta1, beta2, one_minus_beta1,
+                       one_minus_beta2, eps, weight_decay, step_dev, ctl, ema_table, ema_weight, ema_warmup);
+    SPV_LAUNCH_CHECK("spv_adamw_multi_ctl_ema");
     return 0;
 }

@@ -104,9 +104,11 @@ SIGNATURES = {
     "spv_set_seed_device_ptr": [c_vp],
     "spv_seed_advance": [c_vp, c_vp],
     "spv_adamw_multi": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp],
+    "spv_adamw_multi_ema": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_f, c_i, c_f, c_vp],
     "spv_grad_sumsq": [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_vp],
     "spv_step_control": [c_vp, c_i, c_vp, c_i, c_vp, c_i, c_i, c_i, c_d, c_f, c_vp],
     "spv_adamw_multi_ctl": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_vp],
+    "spv_adamw_multi_ctl_ema": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_vp, c_f, c_i, c_vp],
     "spv_fwht": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp],
     "spv_axpby": [c_vp, c_vp, c_vp, c_f, c_f, c_i64, c_i, c_vp],
     "spv_spectrum_floats": [c_i, c_i],

@@ -118,6 +118,39 @@ def _step_control_record(optimizer):
     return {"LR": optimizer.last_lr(c)[0], "GradNorm": c["grad_norm"], "SkippedSteps": c["skipped"]}
 
 
+def _ema_args(ema_decay, ema_warmup):
+    """the harness's two averaging arguments -> FusedAdamW keywords; {} when averaging is off.  Raises before any device is touched."""
+    if ema_decay is None:
+        if ema_warmup:
+            raise ValueError("ema_warmup=True needs ema_decay")
+        return {}
+    if isinstance(ema_decay, bool) or not 0.0 <= float(ema_decay) < 1.0:
+        raise ValueError(f"ema_decay={ema_decay!r} must be None or a float in [0, 1)")
+    return dict(ema_decay=float(ema_decay), ema_warmup=bool(ema_warmup))
+
+
+def _eager_validate(model, batches, criterion, amp, batch_hook, world, device, float_logits=False):
+    """one eager validation pass: every sample of the rank's shard, the loss sample-weighted (the tail batch is short), the sums kept on
+    the device and read once.  -> (accuracy, loss, samples)"""
+    v_correct = torch.zeros((), device=device, dtype=torch.int64)
+    v_loss = torch.zeros((), device=device)
+    v_total, v_steps = 0, 0
+    with torch.no_grad():
+        for img, label in batches:
+            if batch_hook is not None:
+                batch_hook("val", v_steps, img, label)
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=amp):
+                y_pred = model(img)
+            v_correct += (label == torch.argmax(y_pred, dim=1)).sum()
+            v_loss += criterion(y_pred.float() if float_logits else y_pred, label.long()) * label.size(0)
+            v_total += label.size(0)
+            v_steps += 1
+    stats = torch.stack([v_correct.float(), torch.tensor(float(v_total), device=device), v_loss])
+    if world > 1:
+        dist.all_reduce(stats)
+    return (stats[0] / stats[1].clamp(min=1)).item(), (stats[2] / stats[1].clamp(min=1)).item(), int(stats[1].item())
+
+
 def _graph_validate(session, batches, batch_hook, world):
     """one validation pass through a spectre_vit.inference.InferenceSession: the model's current weights are taken (refresh), every batch
     is one graph replay that ends in the on-device metrics kernel, and the epoch costs ONE host read.  -> (accuracy, loss, samples)"""
@@ -146,7 +179,7 @@ def _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, uint8):
 def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
           use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
           augment=False, batch_hook=None, graph_eval=False, lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None,
-          skip_nonfinite=False):
+          skip_nonfinite=False, ema_decay=None, ema_warmup=False):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
@@ -163,9 +196,15 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     lr_schedule="cosine" (with warmup_steps, eta_min), clip_grad_norm, skip_nonfinite: the optimizer's on-device step control
     (spectre_vit.optim: CosineSchedule over total_steps = steps per epoch * epochs as train.py:202-203, gradient clipping, a step with
     an inf / NaN gradient dropped as GradScaler does, train.py:236-238).  With any of them the optimizer is FusedAdamW(capturable=True)
-    on the eager path too, and the epoch record gains "LR" (the last step's rate), "GradNorm" (the last step's) and "SkippedSteps"."""
+    on the eager path too, and the epoch record gains "LR" (the last step's rate), "GradNorm" (the last step's) and "SkippedSteps".
+    ema_decay (with ema_warmup): the optimizer keeps an exponential moving average of the weights inside its own launch
+    (spectre_vit.optim.FusedAdamW(ema_decay=...), capturable=True on the eager path too).  After each epoch's validation a second pass
+    runs on the averaged weights (inside optimizer.ema_weights(); through the same session with graph_eval=True) and the record gains
+    "Accuracy/ValidationEMA" and "Loss/ValidationEMA"; model_ema_best.pt holds optimizer.ema_state_dict(model) of the best such epoch.
+    Every other entry of the record is what it is without averaging."""
     if augment and (uint8_input or distill):
         raise ValueError("augment=True yields normalised float batches for the plain training step: not with uint8_input or distill")
+    ema = _ema_args(ema_decay, ema_warmup)
     c = parse_config(config_path)
     seed = getattr(c, "random_seed", 42)
     lr = getattr(c, "learning_rate", 1e-3)
@@ -196,11 +235,12 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     if graph:
         from spectre_vit.optim import FusedAdamW
         optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
-                               static_grads=True, **control)
+                               static_grads=True, **control, **ema)
         reducer = None   # the graphed step owns its own (fixed-address) gradient buffer
-    elif control:
+    elif control or ema:
         from spectre_vit.optim import FusedAdamW
-        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True, **control)
+        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True, **control,
+                               **ema)
         reducer = GradReducer(model)
     else:
         optimizer = optim.AdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay)  # train.py:199-201
@@ -209,7 +249,7 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     os.makedirs(out_dir, exist_ok=True)
     log_f = open(os.path.join(out_dir, "scalars.jsonl"), "a") if rank == 0 else None
     gen = torch.Generator().manual_seed(seed)
-    best_acc, history = 0.0, []
+    best_acc, best_ema_acc, history = 0.0, 0.0, []
     global_step = 0
     aug = train_nhwc = None
     if augment:
@@ -276,35 +316,23 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         model.eval()
         val_batch = min(getattr(c, "val_batch_size", batch_size), n_val)
         val_uint8 = uint8_input and not distill
-        if graph_eval:
-            if session is None:
-                session = _eval_session(model, n_val, val_batch, rank, world, torch.bfloat16 if use_amp and not distill else None, val_uint8)
-            val_acc, val_loss, val_samples = _graph_validate(
-                session, val_set.batches(val_batch, False, None, rank, world, raw_uint8=val_uint8, drop_last=False), batch_hook, world)
-        else:
-            v_correct = torch.zeros((), device=device, dtype=torch.int64)
-            v_loss = torch.zeros((), device=device)
-            v_total, v_steps = 0, 0
-            with torch.no_grad():
-                for img, label in val_set.batches(val_batch, False, None, rank, world, raw_uint8=val_uint8, drop_last=False):
-                    if batch_hook is not None:
-                        batch_hook("val", v_steps, img, label)
-                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp and not distill):
-                        y_pred = model(img)
-                    v_correct += (label == torch.argmax(y_pred, dim=1)).sum()
-                    v_loss += criterion(y_pred, label.long()) * label.size(0)  # sample-weighted: the tail batch is short
-                    v_total += label.size(0)
-                    v_steps += 1
-            stats = torch.stack([v_correct.float(), torch.tensor(float(v_total), device=device), v_loss])
-            if world > 1:
-                dist.all_reduce(stats)
-            val_acc = (stats[0] / stats[1].clamp(min=1)).item()
-            val_loss = (stats[2] / stats[1].clamp(min=1)).item()
-            val_samples = int(stats[1].item())
+
+        def validate(hook):
+            batches = val_set.batches(val_batch, False, None, rank, world, raw_uint8=val_uint8, drop_last=False)
+            if graph_eval:
+                return _graph_validate(session, batches, hook, world)
+            return _eager_validate(model, batches, criterion, use_amp and not distill, hook, world, device)
+
+        if graph_eval and session is None:
+            session = _eval_session(model, n_val, val_batch, rank, world, torch.bfloat16 if use_amp and not distill else None, val_uint8)
+        val_acc, val_loss, val_samples = validate(batch_hook)
         rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
                "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
         if control:
             rec.update(_step_control_record(optimizer))
+        if ema:   # the same pass on the averaged weights (a session keeps its own copies: leaving the context does not disturb it)
+            with optimizer.ema_weights():
+                rec["Accuracy/ValidationEMA"], rec["Loss/ValidationEMA"], _ = validate(None)
         history.append(rec)
         if rank == 0:
             log_f.write(json.dumps(rec) + "\n")
@@ -313,6 +341,9 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
             if val_acc > best_acc or epoch == 0:  # train.py:288-290
                 best_acc = max(best_acc, val_acc)
                 torch.save(model.state_dict(), os.path.join(out_dir, "model_best.pt"))
+            if ema and (rec["Accuracy/ValidationEMA"] > best_ema_acc or epoch == 0):
+                best_ema_acc = max(best_ema_acc, rec["Accuracy/ValidationEMA"])
+                torch.save(optimizer.ema_state_dict(model), os.path.join(out_dir, "model_ema_best.pt"))
     if gstep is not None:
         gstep.close()
     if session is not None:
@@ -346,8 +377,8 @@ def _teacher_cache(teacher, view, train_nhwc, classes, device, path, resize, cro
 def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
                   use_amp=False, graph=False, augment=True, teacher=None, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75,
                   resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False,
-                  lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False, cache_teacher=False,
-                  teacher_cache_path=None):
+                  lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False, ema_decay=None,
+                  ema_warmup=False, cache_teacher=False, teacher_cache_path=None):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -359,13 +390,14 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     sample (train.py:365-383).  The three per-batch losses the reference logs (train.py:355-359) are kept on the device and written
     once per epoch as {"step", "Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE"} lines: no host synchronisation per step.
     batch_hook(kind, step, img, label), kind "train" / "teacher" / "val" (test seam).  graph_eval, lr_schedule, warmup_steps, eta_min,
-    clip_grad_norm, skip_nonfinite: as in train().
+    clip_grad_norm, skip_nonfinite, ema_decay, ema_warmup: as in train().
     cache_teacher=True: the teacher's view has no random op and the teacher is frozen, so its logits are a function of the sample alone;
     they are computed once before epoch 0 into a resident spectre_vit.distillation.TeacherLogitCache (sharded over the ranks; loaded from
     teacher_cache_path when that file exists and matches, saved there by rank 0 otherwise), a {"TeacherCache": ...} line is logged, and
     the epochs call neither the view nor the teacher: the loss reads the cache through the batch's index (no "teacher" hook then; the
     fill calls batch_hook("teacher_fill", block, img_teacher, index)).  Eager, as a data-parallel rank, and graph=True."""
     from spectre_vit import _native
+    ema = _ema_args(ema_decay, ema_warmup)
     c = parse_config(config_path)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if teacher_cache_path is not None and not cache_teacher:
@@ -408,11 +440,12 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     if graph:
         from spectre_vit.optim import FusedAdamW
         optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
-                               static_grads=True, **control)
+                               static_grads=True, **control, **ema)
         reducer = None   # the graphed step owns its own (fixed-address) gradient buffer
-    elif control:
+    elif control or ema:
         from spectre_vit.optim import FusedAdamW
-        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True, **control)
+        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True, **control,
+                               **ema)
         reducer = GradReducer(model)
     else:
         optimizer = optim.AdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay)  # train.py:307-309
@@ -420,7 +453,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     os.makedirs(out_dir, exist_ok=True)
     log_f = open(os.path.join(out_dir, "scalars.jsonl"), "a") if rank == 0 else None
     gen = torch.Generator().manual_seed(seed)
-    best_acc, history = 0.0, []
+    best_acc, best_ema_acc, history = 0.0, 0.0, []
     global_step = 0
     autocast_dtype = torch.bfloat16 if use_amp else None
     start = time.perf_counter()
@@ -490,35 +523,23 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
 
         model.eval()
         val_batch = min(getattr(c, "val_batch_size", batch_size), n_val)
-        if graph_eval:
-            if session is None:
-                session = _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, False)
-            val_acc, val_loss, val_samples = _graph_validate(session, val_set.batches(val_batch, False, None, rank, world, drop_last=False),
-                                                             batch_hook, world)
-        else:
-            v_correct = torch.zeros((), device=device, dtype=torch.int64)
-            v_loss = torch.zeros((), device=device)
-            v_total, v_steps = 0, 0
-            with torch.no_grad():
-                for img, label in val_set.batches(val_batch, False, None, rank, world, drop_last=False):
-                    if batch_hook is not None:
-                        batch_hook("val", v_steps, img, label)
-                    with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
-                        y_pred = model(img)
-                    v_correct += (label == torch.argmax(y_pred, dim=1)).sum()
-                    v_loss += val_criterion(y_pred.float(), label.long()) * label.size(0)
-                    v_total += label.size(0)
-                    v_steps += 1
-            stats = torch.stack([v_correct.float(), torch.tensor(float(v_total), device=device), v_loss])
-            if world > 1:
-                dist.all_reduce(stats)
-            val_acc = (stats[0] / stats[1].clamp(min=1)).item()
-            val_loss = (stats[2] / stats[1].clamp(min=1)).item()
-            val_samples = int(stats[1].item())
+
+        def validate(hook):
+            batches = val_set.batches(val_batch, False, None, rank, world, drop_last=False)
+            if graph_eval:
+                return _graph_validate(session, batches, hook, world)
+            return _eager_validate(model, batches, val_criterion, use_amp, hook, world, device, float_logits=True)
+
+        if graph_eval and session is None:
+            session = _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, False)
+        val_acc, val_loss, val_samples = validate(batch_hook)
         rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
                "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
         if control:
             rec.update(_step_control_record(optimizer))
+        if ema:
+            with optimizer.ema_weights():
+                rec["Accuracy/ValidationEMA"], rec["Loss/ValidationEMA"], _ = validate(None)
         history.append(rec)
         if rank == 0:
             for k, (lt, ld, lc) in enumerate(per_batch):
@@ -529,6 +550,9 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
             if val_acc > best_acc or epoch == 0:  # as train (train.py:288-290); the reference's distillation cell keeps no checkpoint
                 best_acc = max(best_acc, val_acc)
                 torch.save(model.state_dict(), os.path.join(out_dir, "model_best.pt"))
+            if ema and (rec["Accuracy/ValidationEMA"] > best_ema_acc or epoch == 0):
+                best_ema_acc = max(best_ema_acc, rec["Accuracy/ValidationEMA"])
+                torch.save(optimizer.ema_state_dict(model), os.path.join(out_dir, "model_ema_best.pt"))
     if gstep is not None:
         gstep.close()
     if session is not None:
@@ -569,6 +593,10 @@ def build_parser():
     ap.add_argument("--eta-min", type=float, default=0.0, help="--lr-schedule cosine: the rate the schedule ends at")
     ap.add_argument("--clip-grad-norm", type=float, default=None, help="clip the global gradient norm (on the device, inside the optimizer step)")
     ap.add_argument("--skip-nonfinite", action="store_true", help="drop a step whose gradients hold an inf or a NaN (GradScaler's rule)")
+    ap.add_argument("--ema-decay", type=float, default=None,
+                    help="keep an exponential moving average of the weights inside the optimizer launch, validate it after every epoch "
+                         "and save model_ema_best.pt")
+    ap.add_argument("--ema-warmup", action="store_true", help="--ema-decay: the decay warms up as min(decay, (1 + step) / (10 + step))")
     ap.add_argument("--out", default="runs/spectre_vit")
     return ap
 
@@ -576,7 +604,7 @@ def build_parser():
 def main(argv=None):
     a = build_parser().parse_args(argv)
     control = dict(lr_schedule=a.lr_schedule, warmup_steps=a.warmup_steps, eta_min=a.eta_min, clip_grad_norm=a.clip_grad_norm,
-                   skip_nonfinite=a.skip_nonfinite)
+                   skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup)
     if a.distill_paired:
         train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out,
                       graph_eval=a.graph_eval, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache, **control)

@@ -11,16 +11,22 @@ Step control (``schedule=``, ``max_grad_norm=``, ``skip_nonfinite=``): what the 
 (train.py:205,236-238), and the usual ``clip_grad_norm_`` -- decided on the device from the step count and the gradient, so a
 replayed graph follows the schedule instead of keeping the captured rate.  Per step: ``spv_grad_sumsq`` per group, one
 ``spv_step_control`` that fills a 64-byte control block (include/spv.h: spv_step_ctl), ``spv_adamw_multi_ctl`` per group.
+
+Weight averaging (``ema_decay=``): an exponential moving average of every parameter, kept as ``state[p]["ema"]`` and updated by the
+optimizer launch itself from the registers that hold the new weight (``spv_adamw_multi_ema`` / ``spv_adamw_multi_ctl_ema``): no extra
+launch, nothing for the host to do between two graph replays, and a dropped step leaves the average where it is.
+``ema_weights()`` / ``ema_state_dict()`` take the averaged weights to validation and into a checkpoint.
 """
 from __future__ import annotations
 
+import contextlib
 import math
 import struct
 
 import numpy as np
 import torch
 
-from spectre_vit import _native
+from spectre_vit import _native, hip_ops
 from spectre_vit.hip_ops import _stream
 
 _CHUNK = 2048
@@ -62,9 +68,28 @@ class CosineSchedule:
         return f"CosineSchedule(total_steps={self.total_steps}, warmup_steps={self.warmup_steps}, eta_min={self.eta_min})"
 
 
+def ema_weight_at(step, decay, warmup=False):
+    """The weight w_t of the new parameters in the average at Adam step count `step` (1 on the first applied step), as the kernel
+    forms it: w = float32(1 - decay) from a double difference; with warm-up max(w, float32(9) / float32(10 + step)) in fp32 --
+    timm ModelEmaV2's decay_t = min(decay, (1 + step) / (10 + step)).  The average moves by e' = fmaf(w_t, p' - e, e).
+    Returns the fp32 value as a Python float."""
+    w = np.float32(1.0 - float(decay))
+    if not warmup:
+        return float(w)
+    return float(max(w, np.float32(9.0) / np.float32(10.0 + int(step))))
+
+
+def _check_ema_decay(d):
+    if d is None:
+        return None
+    if isinstance(d, bool) or not 0.0 <= float(d) < 1.0:
+        raise ValueError(f"FusedAdamW: ema_decay={d!r} must be None or a float in [0, 1)")
+    return float(d)
+
+
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False, static_grads=False,
-                 schedule=None, max_grad_norm=None, skip_nonfinite=False):
+                 schedule=None, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, ema_exclude=None):
         """static_grads=True: the caller expects fixed gradient addresses (spectre_vit.dp.GradReducer(model, always=True), or a
         captured graph): after two identical look-ups a step only COMPARES the gradient addresses with the table's (one tuple of
         ``p.grad.data_ptr()`` per group, every step: a caller that swapped a ``.grad`` gets a rebuilt table, never a write through a
@@ -78,7 +103,21 @@ class FusedAdamW(torch.optim.Optimizer):
                           optimizer kernel's registers); read the norm with last_grad_norm().
           skip_nonfinite  a step whose gradients hold an inf or a NaN changes no parameter, no moment and not the Adam step count
                           (GradScaler.step()'s rule); skipped_steps() counts them and the schedule count still advances.
-        Without skip_nonfinite a non-finite norm under clipping acts as torch's does (NaN weights)."""
+        Without skip_nonfinite a non-finite norm under clipping acts as torch's does (NaN weights).
+
+        ema_decay=d in [0, 1): every parameter gets an fp32 average ``state[p]["ema"]``, updated inside the optimizer launch:
+        e' = fmaf(w_t, p' - e, e) with w_t = ema_weight_at(Adam step count, d, ema_warmup) -- torch's ``e.lerp_(p', 1 - d)``.  A group
+        default: a parameter group's own ``ema_decay`` overrides it, None = that group is not averaged.  Works with and without
+        capturable, step control and static_grads; a step dropped by skip_nonfinite does not move the average.
+          ema_warmup      w_t = max(1 - d, 9 / (10 + step)) (timm ModelEmaV2's warm-up); under capturable the count is read on the
+                          device, so a replayed graph follows it.
+          ema_exclude     parameters that are never averaged although their group is (no ``"ema"`` state; ema_state_dict() takes the
+                          live values).
+        The average starts as a bit copy of p, made together with the moments at the first step() (or the first ema_parameters() /
+        ema_weights() / ema_state_dict()), so e_1 = p_0 + w_1 (p_1 - p_0).  state_dict() carries ``"ema"`` with the moments and a
+        resumed run continues the average bit for bit; loading a state that has no ``"ema"`` entries (a torch.optim.AdamW
+        checkpoint, or one saved with averaging off) keeps this optimizer's ema_decay and starts the average from the current
+        parameters at the next step().  With averaging off in every group state_dict() is exactly what it was without the feature."""
         if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError(f"FusedAdamW: invalid hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         if schedule is not None and not isinstance(schedule, CosineSchedule):
@@ -92,7 +131,21 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.step_control and not capturable:
             raise ValueError("FusedAdamW: schedule / max_grad_norm / skip_nonfinite need capturable=True (a skipped step leaves the "
                              "Adam step count where it is, so the count must live on the device)")
-        super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable))
+        defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable)
+        params = list(params)
+        # a group default like the others -- but only where averaging is asked for: without it the groups keep exactly their old keys
+        if ema_decay is not None or any(isinstance(g, dict) and "ema_decay" in g for g in params):
+            defaults["ema_decay"] = _check_ema_decay(ema_decay)
+        super().__init__(params, defaults)
+        for group in self.param_groups:
+            _check_ema_decay(group.get("ema_decay"))
+        self.ema_warmup = bool(ema_warmup)
+        if self.ema_warmup and not self.ema_enabled:
+            raise ValueError("FusedAdamW: ema_warmup=True needs ema_decay in at least one parameter group")
+        self._ema_exclude = frozenset(id(p) for p in (ema_exclude or ()))
+        if self._ema_exclude and not self.ema_enabled:
+            raise ValueError("FusedAdamW: ema_exclude needs ema_decay in at least one parameter group")
+        self._ema_swapped = False
         self.static_grads = bool(static_grads)
         self._tables = {}  # group index -> dict(key, table, chunk_tensor, chunk_off, sizes, nchunks, step_dev)
         # step control: the device block (spv_step_ctl), the per-chunk fp64 partial sums and the device array of the groups' step
@@ -107,6 +160,10 @@ class FusedAdamW(torch.optim.Optimizer):
         # (the moment tensors are part of the key: load_state_dict() on an optimizer that has already stepped replaces them)
         key = tuple((p.data_ptr(), p.grad.data_ptr(), p.numel(), self.state[p]["exp_avg"].data_ptr(), self.state[p]["exp_avg_sq"].data_ptr())
                     for p in ps)
+        # the averages' addresses belong to the key just as the moments' do
+        emas = [self.state[p].get("ema") if self._averaged(p, self.param_groups[gi]) else None for p in ps]
+        if any(e is not None for e in emas):
+            key += tuple(0 if e is None else e.data_ptr() for e in emas)
         t = self._tables.get(gi)
         if t is not None and t["key"] == key:
             return t
@@ -120,6 +177,9 @@ class FusedAdamW(torch.optim.Optimizer):
             st = self.state[p]
             if not p.grad.is_contiguous() or p.grad.dtype != torch.float32:
                 raise RuntimeError("FusedAdamW needs contiguous fp32 gradients")
+            e = emas[i]
+            if e is not None and (not e.is_cuda or e.dtype != torch.float32 or not e.is_contiguous() or e.shape != p.shape):
+                raise RuntimeError("FusedAdamW: state['ema'] must be a contiguous fp32 tensor on the GPU, shaped like its parameter")
             rows += [p.data_ptr(), p.grad.data_ptr(), st["exp_avg"].data_ptr(), st["exp_avg_sq"].data_ptr()]
             n = p.numel()
             sizes.append(n)
@@ -130,6 +190,8 @@ class FusedAdamW(torch.optim.Optimizer):
                  table=torch.tensor(rows, dtype=torch.int64).to(dev), chunk_tensor=torch.tensor(ct, dtype=torch.int32).to(dev),
                  chunk_off=torch.tensor(co, dtype=torch.int32).to(dev), sizes=torch.tensor(sizes, dtype=torch.int32).to(dev),
                  nchunks=len(ct))
+        if any(e is not None for e in emas):   # one float* per table row, NULL = not averaged (include/spv.h: spv_adamw_multi_ema)
+            t["ema_table"] = torch.tensor([0 if e is None else e.data_ptr() for e in emas], dtype=torch.int64).to(dev)
         prev = self._tables.get(gi)
         if prev is not None:  # the step counter outlives a table rebuild
             for k in ("step", "host_step"):
@@ -140,8 +202,18 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def load_state_dict(self, state_dict):
         """torch's loader replaces the per-parameter state (moments, step count): drop the device tables so that the next step() reads
-        the loaded step count and points at the loaded moment tensors (in-place resume / rollback of an optimizer that has stepped)."""
+        the loaded step count and points at the loaded moment tensors (in-place resume / rollback of an optimizer that has stepped).
+        Averaging: a group's ``ema_decay`` comes from the loaded group when it has one and stays this optimizer's otherwise; parameters
+        that arrive without ``"ema"`` start their average from their current values at the next step()."""
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW: load_state_dict() inside ema_weights(): the parameters hold the averaged weights")
+        mine = [g["ema_decay"] for g in self.param_groups] if "ema_decay" in self.defaults else None
         super().load_state_dict(state_dict)
+        for i, g in enumerate(self.param_groups):
+            if "ema_decay" in g:
+                _check_ema_decay(g["ema_decay"])
+            elif mine is not None:
+                g["ema_decay"] = mine[i]
         self._tables = {}
         for st in self.state.values():
             if isinstance(st.get("step"), torch.Tensor):
@@ -153,12 +225,89 @@ class FusedAdamW(torch.optim.Optimizer):
 
     def state_dict(self):
         """torch's layout; with step control on, one more top-level entry carries the schedule count and the skipped count, so that a
-        resumed run continues the curve (a host synchronisation).  Without step control: exactly torch's dict."""
+        resumed run continues the curve (a host synchronisation).  Without step control: exactly torch's dict.  The averages travel
+        as ``state[...]["ema"]``; with averaging off in every group the groups carry no ``ema_decay`` key."""
         sd = super().state_dict()
+        if not self.ema_enabled:
+            sd["param_groups"] = [{k: v for k, v in g.items() if k != "ema_decay"} for g in sd["param_groups"]]
         if self.step_control:
             c = self._read_ctl()
             sd["step_control"] = dict(schedule_step=c["sched_step"], skipped_steps=c["skipped"])
         return sd
+
+    # -- weight averaging ---------------------------------------------------------------------------------------------------------
+    @property
+    def ema_enabled(self):
+        return any(g.get("ema_decay") is not None for g in self.param_groups)
+
+    def _averaged(self, p, group):
+        return group.get("ema_decay") is not None and id(p) not in self._ema_exclude
+
+    def _init_state(self, p, group):
+        """moments and (in an averaged group) the average of one parameter, created together; the average alone where a loaded state
+        came without one.  Never under a graph capture: the new addresses change the table key, and _table refuses there."""
+        st = self.state[p]
+        if "exp_avg" not in st:
+            st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
+            st.setdefault("step", None)
+        if "ema" not in st and self._averaged(p, group):
+            st["ema"] = p.detach().clone(memory_format=torch.contiguous_format)   # a bit copy: e_0 = p_0
+
+    def _ema_pairs(self):
+        """(parameter, average) of every averaged parameter, in parameter order (state created where a parameter has none yet)"""
+        pairs = []
+        for group in self.param_groups:
+            for p in group["params"]:
+                if self._averaged(p, group) and p.is_cuda:
+                    self._init_state(p, group)
+                    pairs.append((p, self.state[p]["ema"]))
+        return pairs
+
+    def ema_parameters(self):
+        """the averages, in parameter order (the tensors themselves, not copies)"""
+        return [e for _, e in self._ema_pairs()]
+
+    def ema_state_dict(self, model):
+        """``model.state_dict()`` with every averaged parameter replaced by a clone of its average; buffers (the permutation tables,
+        signs, indices: they are not parameters and not averaged) and parameters that are not averaged are the model's own.  Loads
+        with strict=True into a fresh model.  Inside ema_weights() the two are exchanged and this returns the live weights."""
+        ema = {id(p): e for p, e in self._ema_pairs()}
+        sd = model.state_dict()
+        for name, p in model.named_parameters(remove_duplicate=False):
+            if id(p) in ema and name in sd:
+                sd[name] = ema[id(p)].detach().clone()
+        return sd
+
+    def _exchange(self, ps, es):
+        with torch.no_grad():
+            tmp = [torch.empty_like(p) for p in ps]
+            torch._foreach_copy_(tmp, ps)
+            torch._foreach_copy_(ps, es)
+            torch._foreach_copy_(es, tmp)
+        hip_ops.invalidate_weight_shadows()
+
+    @contextlib.contextmanager
+    def ema_weights(self):
+        """``with optimizer.ema_weights(): validate(model)``: the CONTENTS of every averaged parameter and its average are exchanged in
+        place and exchanged back on exit (an exception included), bit for bit.  No address changes, so captured graphs, GradReducer
+        buckets and the pointer tables stay valid; the cached compute-dtype weight copies are invalidated both times.  step() inside
+        the context raises, and so does nesting.  Three _foreach_copy_ through a temporary: meant for once an epoch."""
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.ema_weights() does not nest: the parameters already hold the averaged weights")
+        if not self.ema_enabled:
+            raise RuntimeError("FusedAdamW.ema_weights(): built without ema_decay: there is no average")
+        if torch.cuda.is_available() and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW.ema_weights() cannot run inside a graph capture")
+        pairs = self._ema_pairs()
+        ps, es = [p.detach() for p, _ in pairs], [e for _, e in pairs]   # (detach: p's version counter moves with the copy)
+        self._exchange(ps, es)
+        self._ema_swapped = True
+        try:
+            yield self
+        finally:
+            self._exchange(ps, es)
+            self._ema_swapped = False
 
     # -- step control -------------------------------------------------------------------------------------------------------------
     def _read_ctl(self):
@@ -227,9 +376,13 @@ class FusedAdamW(torch.optim.Optimizer):
                      self.max_grad_norm or 0.0, st)
         for group, t in active:
             b1, b2 = group["betas"]
-            _native.call("spv_adamw_multi_ctl", t["table"].data_ptr(), t["chunk_tensor"].data_ptr(), t["chunk_off"].data_ptr(),
-                         t["sizes"].data_ptr(), t["nchunks"], float(group["lr"]), float(b1), float(b2), 1.0 - b1, 1.0 - b2,
-                         float(group["eps"]), float(group["weight_decay"]), t["step"].data_ptr(), self._ctl.data_ptr(), st)
+            args = (t["table"].data_ptr(), t["chunk_tensor"].data_ptr(), t["chunk_off"].data_ptr(), t["sizes"].data_ptr(), t["nchunks"],
+                    float(group["lr"]), float(b1), float(b2), 1.0 - b1, 1.0 - b2, float(group["eps"]), float(group["weight_decay"]),
+                    t["step"].data_ptr(), self._ctl.data_ptr())
+            if "ema_table" in t:
+                _native.call("spv_adamw_multi_ctl_ema", *args, t["ema_table"].data_ptr(), 1.0 - group["ema_decay"], int(self.ema_warmup), st)
+            else:
+                _native.call("spv_adamw_multi_ctl", *args, st)
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -237,6 +390,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
+        if self._ema_swapped:
+            raise RuntimeError("FusedAdamW.step() inside ema_weights(): the parameters hold the averaged weights")
         active = []   # step control: (group, table) of every group that steps, launched together below
         for gi, group in enumerate(self.param_groups):
             t = self._tables.get(gi)
@@ -252,11 +407,7 @@ class FusedAdamW(torch.optim.Optimizer):
                 for p in ps:
                     if not p.is_cuda or p.dtype != torch.float32 or not p.is_contiguous():
                         raise RuntimeError("FusedAdamW: parameters must be contiguous fp32 tensors on the GPU (no CPU fallback)")
-                    st = self.state[p]
-                    if not st:
-                        st["exp_avg"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                        st["exp_avg_sq"] = torch.zeros_like(p, memory_format=torch.preserve_format)
-                        st["step"] = None
+                    self._init_state(p, group)
                 had = t is not None
                 old_key = t["key"] if had else None
                 t = self._table(gi, ps)
@@ -286,9 +437,14 @@ class FusedAdamW(torch.optim.Optimizer):
                 t["step"].fill_(float(t["host_step"]))
                 bc1, bc2 = 1.0 - b1 ** t["host_step"], 1.0 - b2 ** t["host_step"]
                 step_ptr = 0
-            _native.call("spv_adamw_multi", t["table"].data_ptr(), t["chunk_tensor"].data_ptr(), t["chunk_off"].data_ptr(),
-                         t["sizes"].data_ptr(), t["nchunks"], float(group["lr"]), float(b1), float(b2), 1.0 - b1, 1.0 - b2,
-                         float(group["eps"]), float(group["weight_decay"]), bc1, bc2, step_ptr, _stream())
+            args = (t["table"].data_ptr(), t["chunk_tensor"].data_ptr(), t["chunk_off"].data_ptr(), t["sizes"].data_ptr(), t["nchunks"],
+                    float(group["lr"]), float(b1), float(b2), 1.0 - b1, 1.0 - b2, float(group["eps"]), float(group["weight_decay"]),
+                    bc1, bc2, step_ptr)
+            if "ema_table" in t:   # (the host's count is read only without a device-side one)
+                _native.call("spv_adamw_multi_ema", *args, t["ema_table"].data_ptr(), 1.0 - group["ema_decay"], int(self.ema_warmup),
+                             float(t["host_step"]), _stream())
+            else:
+                _native.call("spv_adamw_multi", *args, _stream())
         if active:
             self._step_controlled(active)
         return loss

@@ -82,6 +82,9 @@ _WORK_MODELS = {
     "spv_haar_dwt": lambda i: ("haar_dwt", i[0:3], i[6], "hbm", 2.0 * i[0] * i[1] * i[2] * _es(i[6])),
     # p, g, m, v read + p, m, v written, 2048 elements per workgroup (the last chunk of a tensor is short: an upper bound)
     "spv_adamw_multi": lambda i: ("adamw_multi", i[0:1], F32, "hbm", 7.0 * 4 * 2048 * i[0]),
+    # ... plus the moving average read and written (every tensor averaged: an upper bound)
+    "spv_adamw_multi_ema": lambda i: ("adamw_multi_ema", i[0:1], F32, "hbm", 9.0 * 4 * 2048 * i[0]),
+    "spv_adamw_multi_ctl_ema": lambda i: ("adamw_multi_ctl_ema", i[0:1], F32, "hbm", 9.0 * 4 * 2048 * i[0]),
     # step control: the gradient read once (chunks as above), the per-chunk fp64 partials folded, the optimizer's seven streams
     "spv_grad_sumsq": lambda i: ("grad_sumsq", i[0:1], F32, "hbm", 4.0 * 2048 * i[0]),
     "spv_step_control": lambda i: ("step_control", i[0:2], F32, "hbm", 8.0 * i[0] + 64),
