@@ -59,7 +59,10 @@ enum {
     SPV_PATH_ATTN_ROW0_BWD = 21, /* spv_attention_row0_bwd */
     SPV_PATH_AUGMENT = 22,       /* spv_augment_u8 (one workgroup per image) or spv_augment_tiled_u8 (output tiles): one per call */
     SPV_PATH_TEACHER_VIEW = 23,  /* spv_teacher_view_u8 (the distillation teacher's 224 view, one workgroup per image and row band) */
-    SPV_PATH_COUNT = 24
+    SPV_PATH_ATTN_V1 = 24,       /* spv_attention_fwd / _bwd served by the general kernels (attn_*_kernel): one per call */
+    SPV_PATH_ATTN_V2 = 25,       /* ... by the LDS-staged kernels (attn2_*_kernel; head dim 16 / 32 / 64) */
+    SPV_PATH_ATTN_V3 = 26,       /* ... by the bf16 MFMA flash kernels (attn3_*_kernel; head dim 32 / 64) */
+    SPV_PATH_COUNT = 27
 };
 long long spv_path_count(int which);
 const char* spv_last_error(void);

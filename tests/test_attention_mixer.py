@@ -198,4 +198,5 @@ def test_census_indices_match_header(built):
     src = open(os.path.join(ROOT, "include", "spv.h")).read()
     assert int(re.search(r"SPV_PATH_ATTN_ROW0_FWD = (\d+)", src).group(1)) == _native.PATH["attn_row0_fwd"] == 20
     assert int(re.search(r"SPV_PATH_ATTN_ROW0_BWD = (\d+)", src).group(1)) == _native.PATH["attn_row0_bwd"] == 21
-    assert int(re.search(r"SPV_PATH_COUNT = (\d+)", src).group(1)) == 24
+    assert int(re.search(r"SPV_PATH_COUNT = (\d+)", src).group(1)) == 27
+    assert sorted(_native.PATH.values()) == list(range(27))

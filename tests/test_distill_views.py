@@ -107,7 +107,8 @@ def test_census_index_and_support(built):
     from spectre_vit import _native
     hdr = open(os.path.join(ROOT, "include", "spv.h")).read()
     enum = dict(re.findall(r"(SPV_PATH_[A-Z0-9_]+)\s*=\s*(\d+)", hdr))
-    assert int(enum["SPV_PATH_TEACHER_VIEW"]) == _native.PATH["teacher_view"] == 23 < int(enum["SPV_PATH_COUNT"]) == 24
+    assert int(enum["SPV_PATH_TEACHER_VIEW"]) == _native.PATH["teacher_view"] == 23 < int(enum["SPV_PATH_COUNT"]) == 27
+    assert sorted(_native.PATH.values()) == list(range(27))
     sup = lambda c, n, r, k: _native.call("spv_teacher_view_supported", c, n, r, k)
     assert sup(3, 32, 256, 224) == 1 and sup(1, 28, 256, 224) == 1 and sup(3, 28, 256, 224) == 1 and sup(3, 256, 256, 224) == 1
     assert sup(2, 32, 256, 224) == 0, "2 channels"

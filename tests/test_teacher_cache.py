@@ -32,8 +32,8 @@ def test_symbols_are_exported_and_bound_and_the_census_slot_is_8(built):
         assert re.search(r"\bint " + name + r"\(", hdr), name
     enum = dict(re.findall(r"(SPV_PATH_[A-Z0-9_]+)\s*=\s*(\d+)", hdr))
     assert int(enum["SPV_PATH_DISTILL_CACHED"]) == _native.PATH["distill_cached"] == 8
-    assert int(enum["SPV_PATH_COUNT"]) == 24
-    assert sorted(_native.PATH.values()) == list(range(24)), "every census slot has one name"
+    assert int(enum["SPV_PATH_COUNT"]) == 27
+    assert sorted(_native.PATH.values()) == list(range(27)), "every census slot has one name"
 
 
 def test_entry_points_reject_bad_arguments_before_any_launch(built):

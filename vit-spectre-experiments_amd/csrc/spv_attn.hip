@@ -472,6 +472,7 @@ int launch_attn2_fwd(const void* qkv, void* ctx, void* probs, int seqs, int len,
     dim3 grid(seqs * heads, cdiv(len, A2W * rpw));
     hipLaunchKernelGGL((attn2_fwd_kernel<T, HD>), grid, dim3(64 * A2W), lds, st, (const T*)qkv, (T*)ctx, (T*)probs, len, heads, rpw, p_drop, seed);
     SPV_LAUNCH_CHECK("spv_attention_fwd(v2)");
+    SPV_COUNT_PATH(SPV_PATH_ATTN_V2);
     return 0;
 }
 template <typename T, int HD>
@@ -488,10 +489,14 @@ int launch_attn2_bwd(const void* dctx, const void* qkv, const void* probs, void*
     hipLaunchKernelGGL((attn2_bwd_kv_kernel<T, HD>), dim3(seqs * heads, cdiv(len, 64)), dim3(256), lds_kv, st, (const T*)dctx,
                        (const T*)qkv, (const T*)probs, (const T*)ds, (T*)dqkv, len, heads, p_drop, seed);
     SPV_LAUNCH_CHECK("spv_attention_bwd(v2 kv)");
+    SPV_COUNT_PATH(SPV_PATH_ATTN_V2);
     return 0;
 }
 
-// v2 applies when head_dim is 16 / 32 / 64, rows are 8-byte aligned and the staged operands fit in LDS
+// v2 applies when head_dim is 16 / 32 / 64, rows are 8-byte aligned and the staged operands fit in LDS.  At A2_LDS_MAX = 150 KiB the
+// last length served is, at head dim 16 / 32 / 64: fp32 823 (lds_fwd) / 474 (lds_fwd) / 228 (lds_kv: 528 len + 33024 bytes), bf16 the
+// len cap 1024 / 820 (lds_fwd) / 443 (lds_kv).  bf16 at head dim 32 / 64 gets here only past v3's limits or when a pointer is 8- but not
+// 16-byte aligned.  tests/test_gpu_attention_edges.py runs both sides of every one of these by the dispatch census.
 template <typename T> inline bool attn2_ok(int len, int heads, int hd, const void* a, const void* b) {
     if (!(hd == 16 || hd == 32 || hd == 64)) return false;
     if (((uintptr_t)a & 7) || ((uintptr_t)b & 7) || ((size_t)heads * hd * sizeof(T)) % 8) return false;
@@ -866,6 +871,7 @@ int launch_attn3_fwd(const void* qkv, void* ctx, void* probs, int seqs, int len,
     hipLaunchKernelGGL((attn3_fwd_kernel<HD>), dim3(seqs * heads, cdiv(len, 128)), dim3(256), lds, st, (const bf16_t*)qkv, (bf16_t*)ctx,
                        (float*)probs, len, heads, p_drop, seed);
     SPV_LAUNCH_CHECK("spv_attention_fwd(v3)");
+    SPV_COUNT_PATH(SPV_PATH_ATTN_V3);
     return 0;
 }
 template <int HD>
@@ -882,9 +888,12 @@ int launch_attn3_bwd(const void* dctx, const void* qkv, const void* probs, void*
     hipLaunchKernelGGL((attn3_bwd_kv_kernel<HD>), grid, dim3(256), lds_kv, st, (const bf16_t*)dctx, (const bf16_t*)qkv,
                        (const float*)probs, (const float*)dscores, (bf16_t*)dqkv, len, heads, p_drop, seed);
     SPV_LAUNCH_CHECK("spv_attention_bwd(v3 kv)");
+    SPV_COUNT_PATH(SPV_PATH_ATTN_V3);
     return 0;
 }
 
+// v3 applies to bf16 at head dim 32 / 64, len >= 2, 16-byte aligned pointers, while backward-2's LDS (two transposed operands and three
+// fp32 / key rows) fits in 150 KiB: head dim 64 up to len 544 (545 rounds up to 576 rows: 155392 bytes), head dim 32 up to the len cap 1024
 inline bool attn3_ok(int len, int heads, int hd, int dtype, const void* a, const void* b, const void* c) {
     if (dtype != SPV_BF16 || !(hd == 32 || hd == 64) || len < 2 || (heads * hd) % 8) return false;
     if (((uintptr_t)a & 15) || ((uintptr_t)b & 15) || ((uintptr_t)c & 15)) return false;
@@ -918,6 +927,7 @@ extern "C" int spv_attention_fwd(const void* qkv, void* ctx, void* probs, int se
     hipLaunchKernelGGL(attn_fwd_kernel, grid, dim3(64 * AW), (size_t)AW * (len + MAXHD) * sizeof(float), static_cast<hipStream_t>(stream),
                        qkv, ctx, probs, len, heads, head_dim, dtype == SPV_BF16, p_drop, seed);
     SPV_LAUNCH_CHECK("spv_attention_fwd");
+    SPV_COUNT_PATH(SPV_PATH_ATTN_V1);
     return 0;
 }
 
@@ -939,6 +949,7 @@ extern "C" int spv_attention_bwd(const void* dctx, const void* qkv, const void* 
     hipLaunchKernelGGL(attn_bwd_kv_kernel, grid, dim3(64 * AW), (size_t)AW * 2 * len * sizeof(float), st, dctx, qkv, probs, dscores, dqkv,
                        len, heads, head_dim, dtype == SPV_BF16, p_drop, seed);
     SPV_LAUNCH_CHECK("spv_attention_bwd(kv)");
+    SPV_COUNT_PATH(SPV_PATH_ATTN_V1);
     return 0;
 }
 

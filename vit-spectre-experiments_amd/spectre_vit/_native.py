@@ -21,7 +21,8 @@ c_vp, c_i, c_i64, c_u64, c_f, c_d = ctypes.c_void_p, ctypes.c_int, ctypes.c_int6
 # indices of include/spv.h's SPV_PATH_* enum (dispatch census, test aid)
 PATH = dict(gemm_strip=0, gemm_strip_acc=1, gemm_tn=2, tail_lc=3, tail_up=4, tail_ln=5, fnet_mfma=6, gather_lds=7, distill_cached=8, gemm_tn_wide=9,
             gemm_tn_batch=10, gemm_strip_pool=11, permut_row0=12, gemm_rows=13,
-            spectrum=14, conv_fwd=15, conv_dgrad=16, conv_wgrad=17, token_pool=18, token_unpool=19, attn_row0_fwd=20, attn_row0_bwd=21, augment=22, teacher_view=23)
+            spectrum=14, conv_fwd=15, conv_dgrad=16, conv_wgrad=17, token_pool=18, token_unpool=19, attn_row0_fwd=20, attn_row0_bwd=21, augment=22, teacher_view=23,
+            attn_v1=24, attn_v2=25, attn_v3=26)
 
 # name -> argtypes (restype is int unless listed in _RESTYPES); mirrors include/spv.h one to one
 SIGNATURES = {
