@@ -686,6 +686,47 @@ int64_t spv_eval_head_stats_words(void);
 int spv_eval_head(const void* logits, const int64_t* labels, const int* n_valid, int64_t* pred, void* stats, int rows, int classes, int k,
                   int dtype, void* stream);
 
+/* ---- the training meter: the loss forwards that also keep the training loop's books (spectre_vit/repl/train.py:221-224, 243 and, in
+ * the distillation cell, :329-332, 355-361) -- hits counted on the row walk the loss already does, the step's scalars written into a
+ * device-resident log, so that a (graph-replayed) step records itself and an epoch costs ONE host read.  DESIGN.md section 4h.
+ *
+ * The meter is ONE contiguous block of spv_train_meter_words(capacity) 64-bit words, 8-byte aligned, laid out like spv_eval_head's
+ * stats block.  The caller zeroes it and writes `capacity` before the first call (and to start a new epoch):
+ *   word 0  cursor    steps logged so far = the log row the next step writes
+ *   word 1  capacity  log rows the block holds (written by the caller, only read by the kernels)
+ *   word 2  dropped   steps that found the log full (cursor == capacity): no row written, totals still accumulated
+ *   word 3-5  seen, top1, topk   int64: rows with a label in [0, classes), and the top-1 / top-k hits among them, over all steps
+ *   word 6-8  loss_sum, soft_sum, ce_sum   float64 bits: the sums of the steps' fp32 loss (soft term, CE term), one add per step
+ *   word 9-15 reserved, zero
+ *   then `capacity` log rows of SPV_TRAIN_METER_ROW words, one per step: the step's loss, soft and CE as fp32 bits in the low half of a
+ *   word each (soft and CE are 0 on the plain cross-entropy path), then the step's top1 and topk counts.
+ * pred, the top-1 hit and the top-k hit are spv_eval_head's, on the (student) logits: first maximum (a NaN entry never wins; a row
+ * without an ordered maximum predicts class 0), and #{j : z_j > z_y} + #{j < y : z_j == z_y} < k.  A row whose label is outside
+ * [0, classes) is not counted in seen / top1 / topk; it makes the step's loss NaN exactly as in the un-metered call, and that NaN goes
+ * into its log row and into loss_sum (what a host's `running += loss` does).
+ * loss, lse (out3, lse3) are, bit for bit, those of the un-metered entry point on the same inputs: the same grid, the same partial
+ * order, the same join.  The last workgroup to arrive also joins the workgroups' hit counts, writes log row `cursor`, adds to the
+ * totals, advances the cursor and re-arms the counter; a full log advances `dropped` instead of writing.  Nothing is written past the
+ * block.  The row index is read from the device, so a captured launch logs a new row at every replay.
+ * Arguments: those of the un-metered entry point, then meter, k (1..8), then the stream.  workspace: the *_meter_workspace_floats() of
+ * the entry point (the un-metered workspace, then the workgroups' hit counts), zeroed once by the caller.
+ * Refused on the host, before any launch: a null meter or one not 8-byte aligned, k outside 1..8, rows outside 1..2^24 or classes
+ * outside 1..2^24-1 (counts and class indices are joined as exact fp32 integers), and what the un-metered entry point refuses.
+ * spv_train_meter_words returns 0 (and sets spv_last_error) for a capacity outside 1..SPV_TRAIN_METER_MAX_CAPACITY. */
+#define SPV_TRAIN_METER_HEADER 16
+#define SPV_TRAIN_METER_ROW 5
+#define SPV_TRAIN_METER_MAX_CAPACITY (1 << 24)
+int64_t spv_train_meter_words(int64_t capacity);
+int64_t spv_cross_entropy_meter_workspace_floats(void);
+int spv_cross_entropy_meter_fwd(const float* logits, const int64_t* labels, float* lse, float* loss, float* workspace, int rows,
+                                int classes, void* meter, int k, void* stream);
+int64_t spv_distill_loss_meter_workspace_floats(void);
+int spv_distill_loss_meter_fwd(const float* student, const float* teacher, const int64_t* labels, float* lse3, float* out3, float* workspace,
+                               int rows, int classes, float T, float w_soft, float w_ce, void* meter, int k, void* stream);
+int spv_distill_loss_idx_meter_fwd(const float* student, const float* cache, const int64_t* index, const int64_t* labels, float* lse3,
+                                   float* out3, float* workspace, int rows, int n_cache, int classes, float T, float w_soft, float w_ce,
+                                   void* meter, int k, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

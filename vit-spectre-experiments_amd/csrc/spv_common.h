@@ -157,6 +157,37 @@ __device__ __forceinline__ void fold_partials_block(const FoldJob& j, int bid, i
     }
 }
 
+// ---------------------------------------------------------------- the training meter (include/spv.h)
+// host: the checks the three metered loss forwards share (spv_head.hip)
+int spv_train_meter_check(const char* name, const void* meter, int k, int rows, int classes);
+
+// the meter block's words
+constexpr int TM_CURSOR = 0, TM_CAPACITY = 1, TM_DROPPED = 2, TM_SEEN = 3, TM_TOP1 = 4, TM_TOPK = 5, TM_LOSS = 6, TM_SOFT = 7, TM_CE = 8;
+constexpr int TM_HEADER = SPV_TRAIN_METER_HEADER, TM_ROW = SPV_TRAIN_METER_ROW;
+
+// One thread, the last workgroup's: the step (loss, soft, ce; hits seen / top1 / topk) goes into log row `cursor` -- or, the log full,
+// into `dropped` -- and into the running totals, one float64 add per sum.  Nothing is written at or past row `capacity`.
+__device__ __forceinline__ void train_meter_log(long long* meter, float loss, float soft, float ce, int seen, int top1, int topk) {
+    const long long cur = meter[TM_CURSOR], cap = meter[TM_CAPACITY];
+    if (cur >= 0 && cur < cap) {
+        long long* row = meter + TM_HEADER + cur * TM_ROW;
+        row[0] = (long long)__float_as_uint(loss);
+        row[1] = (long long)__float_as_uint(soft);
+        row[2] = (long long)__float_as_uint(ce);
+        row[3] = top1;
+        row[4] = topk;
+        meter[TM_CURSOR] = cur + 1;
+    } else {
+        meter[TM_DROPPED] += 1;
+    }
+    meter[TM_SEEN] += seen;
+    meter[TM_TOP1] += top1;
+    meter[TM_TOPK] += topk;
+    meter[TM_LOSS] = __double_as_longlong(__longlong_as_double(meter[TM_LOSS]) + (double)loss);
+    meter[TM_SOFT] = __double_as_longlong(__longlong_as_double(meter[TM_SOFT]) + (double)soft);
+    meter[TM_CE] = __double_as_longlong(__longlong_as_double(meter[TM_CE]) + (double)ce);
+}
+
 // ---------------------------------------------------------------- math
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_erf_grad(float x) {

@@ -192,17 +192,25 @@ constexpr int DL_MAX_WG = 64;
 // difference, so the indexed launch returns the bits of the dense launch on cache[index].  A row whose index lies outside [0, n_cache)
 // forms no cache address: the wave runs the row body on the student row in the teacher's place (its CE and the student's two
 // log-sum-exps are the true ones) and then poisons what depends on the teacher: the row's soft term and lse3[2][r].
-template <bool INDEXED>
-__global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
-                                                                 const int64_t* __restrict__ index, const int64_t* __restrict__ labels,
-                                                                 float* __restrict__ lse3, float* __restrict__ out3,
-                                                                 float* __restrict__ partial, unsigned* __restrict__ counter, int rows,
-                                                                 int n_cache, int C, float T, float w_soft, float w_ce) {
+// METER (spv_distill_loss_meter_fwd / _idx_meter_fwd, the training meter of include/spv.h): the walk also finds the student row's first
+// maximum and counts the logits ranked in front of the label's (spv_eval_head's rules); the workgroups' hit counts ride behind their
+// partials and the joining workgroup logs the step into the meter block.  Every operation that forms lse3 and out3 is the un-metered
+// one, in the same order: the instantiations return the same bits.
+constexpr int DL_HITS = 2 * DL_MAX_WG + 2;   // first word of the metered workspace's hit partials [DL_MAX_WG][3] (int32)
+
+template <bool INDEXED, bool METER>
+__device__ __forceinline__ void distill_fwd_body(const float* __restrict__ z, const float* __restrict__ t,
+                                                 const int64_t* __restrict__ index, const int64_t* __restrict__ labels,
+                                                 float* __restrict__ lse3, float* __restrict__ out3, float* __restrict__ partial,
+                                                 unsigned* __restrict__ counter, int rows, int n_cache, int C, float T, float w_soft,
+                                                 float w_ce, long long* meter, int k) {
     __shared__ float ws[2][DL_WAVES];
+    __shared__ int hs[METER ? DL_WAVES : 1][3];
     __shared__ bool last;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const float invT = 1.0f / T;
     float acc_soft = 0.0f, acc_ce = 0.0f;
+    int seen = 0, top1 = 0, topk = 0;   // lane 0's
     for (int r = blockIdx.x * DL_WAVES + wave; r < rows; r += gridDim.x * DL_WAVES) {
         const float* zr = z + (size_t)r * C;
         const float* tr = t + (size_t)r * C;
@@ -213,19 +221,38 @@ __global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __
             tr = held ? t + (size_t)row * C : zr;
         }
         float mz = -INFINITY, mt = -INFINITY, dmax = 0.0f;
+        float bm = -INFINITY;   // METER: the lane's first largest student logit and its index (a NaN never wins)
+        int am = C;
+        int64_t ym = 0;
+        float zy = 0.0f;
+        if constexpr (METER) {   // the label and its logit first: the two dependent loads are in flight under the first walk of the row
+            ym = labels[r];
+            zy = zr[(ym >= 0 && ym < C) ? (int)ym : 0];   // clamped, unconditional (one address per wave)
+        }
         for (int c = lane; c < C; c += 64) {
             const float a = zr[c], b = tr[c];
             mz = fmaxf(mz, a);
             mt = fmaxf(mt, b);
             dmax = fmaxf(dmax, fabsf((b - a) * invT));
+            if constexpr (METER) {
+                if (a > bm) { bm = a; am = c; }
+            }
         }
         mz = wave_max(mz);
         mt = wave_max(mt);
         dmax = wave_max(dmax);
         const bool nearby = dmax < 0.5f;   // wave uniform
         float s1 = 0.0f, s2 = 0.0f, s3 = 0.0f, pu = 0.0f, qe = 0.0f;
+        int first = 0;
+        float cnt = 0.0f;
+        if constexpr (METER) {
+            // the smallest index among the lanes that hold the maximum (indices are below 2^24: exact as floats)
+            first = (int)(-wave_max(-(float)((bm == mz && am < C) ? am : C)));
+            if (first >= C) first = 0;   // a row without an ordered maximum (every entry NaN or -inf)
+        }
         for (int c = lane; c < C; c += 64) {
             const float a = zr[c], b = tr[c];
+            if constexpr (METER) cnt += (a > zy || (a == zy && c < ym)) ? 1.0f : 0.0f;
             const float az = (a - mz) * invT, bt = (b - mt) * invT;
             const float ez = expf(az), et = expf(bt);
             const float d = (b - a) * invT;
@@ -250,10 +277,23 @@ __global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __
             acc_soft += held ? pu / s3 - gap : __builtin_nanf("");
             acc_ce += (y >= 0 && y < C) ? lz - zr[y] : __builtin_nanf("");   // a label outside [0, C) poisons the loss instead of reading wild
         }
+        if constexpr (METER) {
+            const int above = (int)wave_sum(cnt);   // at most C < 2^24 ones: exact
+            if (lane == 0 && y >= 0 && y < C) {     // a row with a label outside the classes is not counted
+                seen += 1;
+                top1 += first == (int)y ? 1 : 0;
+                topk += above < k ? 1 : 0;
+            }
+        }
     }
     if (lane == 0) {
         ws[0][wave] = acc_soft;
         ws[1][wave] = acc_ce;
+        if constexpr (METER) {
+            hs[wave][0] = seen;
+            hs[wave][1] = top1;
+            hs[wave][2] = topk;
+        }
     }
     __syncthreads();
     if (tid == 0) {
@@ -264,6 +304,18 @@ __global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __
         }
         partial[blockIdx.x] = a;
         partial[DL_MAX_WG + blockIdx.x] = b;
+        if constexpr (METER) {
+            int* hits = reinterpret_cast<int*>(partial + DL_HITS) + 3 * blockIdx.x;
+            int a0 = 0, a1 = 0, a2 = 0;
+            for (int w = 0; w < DL_WAVES; ++w) {
+                a0 += hs[w][0];
+                a1 += hs[w][1];
+                a2 += hs[w][2];
+            }
+            hits[0] = a0;
+            hits[1] = a1;
+            hits[2] = a2;
+        }
         __threadfence();
         last = atomicAdd(counter, 1u) == gridDim.x - 1;
     }
@@ -274,15 +326,44 @@ __global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __
             const bool in = lane < (int)gridDim.x;
             const float a = wave_sum(in ? __builtin_nontemporal_load(partial + lane) : 0.0f);
             const float b = wave_sum(in ? __builtin_nontemporal_load(partial + DL_MAX_WG + lane) : 0.0f);
+            float h0 = 0.0f, h1 = 0.0f, h2 = 0.0f;
+            if constexpr (METER) {
+                // the hit counts: integers of at most rows <= 2^24 in all, so every float sum below is exact
+                const int* hits = reinterpret_cast<const int*>(partial + DL_HITS) + 3 * lane;
+                h0 = wave_sum(in ? (float)__builtin_nontemporal_load(hits) : 0.0f);
+                h1 = wave_sum(in ? (float)__builtin_nontemporal_load(hits + 1) : 0.0f);
+                h2 = wave_sum(in ? (float)__builtin_nontemporal_load(hits + 2) : 0.0f);
+            }
             if (lane == 0) {
                 const float soft = a * (T * T) / (float)rows, ce = b / (float)rows;
-                out3[0] = w_soft * soft + w_ce * ce;
+                const float total = w_soft * soft + w_ce * ce;
+                out3[0] = total;
                 out3[1] = soft;
                 out3[2] = ce;
+                if constexpr (METER) train_meter_log(meter, total, soft, ce, (int)h0, (int)h1, (int)h2);
                 *counter = 0u;
             }
         }
     }
+}
+
+template <bool INDEXED>
+__global__ __launch_bounds__(DL_THREADS) void distill_fwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
+                                                                 const int64_t* __restrict__ index, const int64_t* __restrict__ labels,
+                                                                 float* __restrict__ lse3, float* __restrict__ out3,
+                                                                 float* __restrict__ partial, unsigned* __restrict__ counter, int rows,
+                                                                 int n_cache, int C, float T, float w_soft, float w_ce) {
+    distill_fwd_body<INDEXED, false>(z, t, index, labels, lse3, out3, partial, counter, rows, n_cache, C, T, w_soft, w_ce, nullptr, 0);
+}
+
+template <bool INDEXED>
+__global__ __launch_bounds__(DL_THREADS) void distill_meter_fwd_kernel(const float* __restrict__ z, const float* __restrict__ t,
+                                                                       const int64_t* __restrict__ index, const int64_t* __restrict__ labels,
+                                                                       float* __restrict__ lse3, float* __restrict__ out3,
+                                                                       float* __restrict__ partial, unsigned* __restrict__ counter, int rows,
+                                                                       int n_cache, int C, float T, float w_soft, float w_ce,
+                                                                       long long* meter, int k) {
+    distill_fwd_body<INDEXED, true>(z, t, index, labels, lse3, out3, partial, counter, rows, n_cache, C, T, w_soft, w_ce, meter, k);
 }
 
 // dz = go / rows * (w_soft T (softmax(z / T) - softmax(t / T)) + w_ce (softmax(z) - onehot))
@@ -444,6 +525,37 @@ extern "C" int spv_distill_loss_idx_bwd(const float* student, const float* cache
                        dim3(DL_THREADS), 0, static_cast<hipStream_t>(stream), student, cache, index, labels, lse3, grad_out, dlogits, rows,
                        n_cache, classes, T, w_soft, w_ce);
     SPV_LAUNCH_CHECK("spv_distill_loss_idx_bwd");
+    return 0;
+}
+
+// ---- the training meter (include/spv.h): the same two forwards, counting hits and logging the step
+extern "C" int64_t spv_distill_loss_meter_workspace_floats() { return DL_HITS + 3 * DL_MAX_WG; }   // + one word of padding, the hit partials
+
+extern "C" int spv_distill_loss_meter_fwd(const float* student, const float* teacher, const int64_t* labels, float* lse3, float* out3,
+                                          float* workspace, int rows, int classes, float T, float w_soft, float w_ce, void* meter, int k,
+                                          void* stream) {
+    if (int rc = distill_check("spv_distill_loss_meter_fwd", student, teacher, labels, lse3, out3, workspace, rows, classes, T, w_soft, w_ce)) return rc;
+    if (int rc = spv_train_meter_check("spv_distill_loss_meter_fwd", meter, k, rows, classes)) return rc;
+    const int wgs = std::min(cdiv(rows, DL_WAVES), DL_MAX_WG);   // spv_distill_loss_fwd's grid: the same partial order
+    hipLaunchKernelGGL(distill_meter_fwd_kernel<false>, dim3(wgs), dim3(DL_THREADS), 0, static_cast<hipStream_t>(stream), student, teacher,
+                       (const int64_t*)nullptr, labels, lse3, out3, workspace, reinterpret_cast<unsigned*>(workspace + 2 * DL_MAX_WG), rows,
+                       0, classes, T, w_soft, w_ce, static_cast<long long*>(meter), k);
+    SPV_LAUNCH_CHECK("spv_distill_loss_meter_fwd");
+    return 0;
+}
+
+extern "C" int spv_distill_loss_idx_meter_fwd(const float* student, const float* cache, const int64_t* index, const int64_t* labels,
+                                              float* lse3, float* out3, float* workspace, int rows, int n_cache, int classes, float T,
+                                              float w_soft, float w_ce, void* meter, int k, void* stream) {
+    if (int rc = distill_check("spv_distill_loss_idx_meter_fwd", student, cache, labels, lse3, out3, workspace, rows, classes, T, w_soft, w_ce)) return rc;
+    if (int rc = distill_idx_check("spv_distill_loss_idx_meter_fwd", index, n_cache)) return rc;
+    if (int rc = spv_train_meter_check("spv_distill_loss_idx_meter_fwd", meter, k, rows, classes)) return rc;
+    const int wgs = std::min(cdiv(rows, DL_WAVES), DL_MAX_WG);
+    hipLaunchKernelGGL(distill_meter_fwd_kernel<true>, dim3(wgs), dim3(DL_THREADS), 0, static_cast<hipStream_t>(stream), student, cache, index,
+                       labels, lse3, out3, workspace, reinterpret_cast<unsigned*>(workspace + 2 * DL_MAX_WG), rows, n_cache, classes, T,
+                       w_soft, w_ce, static_cast<long long*>(meter), k);
+    SPV_LAUNCH_CHECK("spv_distill_loss_idx_meter_fwd");
+    SPV_COUNT_PATH(SPV_PATH_DISTILL_CACHED);
     return 0;
 }
 

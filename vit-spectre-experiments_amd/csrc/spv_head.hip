@@ -336,33 +336,95 @@ __global__ __launch_bounds__(WT) void small_sl_bwd_w_kernel(const float* __restr
 
 // ---- cross-entropy, mean over rows.  forward: wave per row; per-workgroup partial sums; the last workgroup to finish adds them in
 // index order (deterministic) and re-arms the counter.
-__global__ __launch_bounds__(HT) void ce_fwd_kernel(const float* __restrict__ z, const int64_t* __restrict__ labels, float* __restrict__ lse,
-                                                    float* __restrict__ loss, float* __restrict__ partial, unsigned* __restrict__ counter,
-                                                    int rows, int C) {
+// METER (spv_cross_entropy_meter_fwd, the training meter of include/spv.h): the same walk also finds the row's first maximum and
+// counts the logits ranked in front of the label's (spv_eval_head's rules), the workgroups' hit counts ride behind their loss partials,
+// and the joining workgroup logs the step into the meter block.  Every operation that forms lse and loss is the un-metered one, in the
+// same order: the two instantiations return the same bits.
+constexpr int CE_MAX_WG = 64;
+constexpr int CE_HITS = CE_MAX_WG + 2;   // first word of the metered workspace's hit partials [CE_MAX_WG][3] (int32), behind the counter
+
+template <bool METER>
+__device__ __forceinline__ void ce_fwd_body(const float* __restrict__ z, const int64_t* __restrict__ labels, float* __restrict__ lse,
+                                            float* __restrict__ loss, float* __restrict__ partial, unsigned* __restrict__ counter,
+                                            int rows, int C, long long* meter, int k) {
     __shared__ float ws[HT / 64];
+    __shared__ int hs[METER ? HT / 64 : 1][3];
     __shared__ bool last;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     float acc = 0.0f;
+    int seen = 0, top1 = 0, topk = 0;   // lane 0's
     for (int r = blockIdx.x * (HT / 64) + wave; r < rows; r += gridDim.x * (HT / 64)) {
         const float* zr = z + (size_t)r * C;
         float m = -INFINITY;
-        for (int c = lane; c < C; c += 64) m = fmaxf(m, zr[c]);
-        m = wave_max(m);
+        int first = 0, above = 0;
         float s = 0.0f;
-        for (int c = lane; c < C; c += 64) s += __expf(zr[c] - m);
+        if constexpr (METER) {
+            // the label and its logit first: the two dependent loads are in flight under the first walk of the row
+            const int64_t ym = labels[r];
+            const float zy = zr[(ym >= 0 && ym < C) ? (int)ym : 0];   // clamped, unconditional (one address per wave)
+            float bm = -INFINITY;   // the lane's first largest entry and its index (a NaN never wins)
+            int am = C;
+            for (int c = lane; c < C; c += 64) {
+                const float x = zr[c];
+                m = fmaxf(m, x);
+                if (x > bm) { bm = x; am = c; }
+            }
+            m = wave_max(m);
+            // the smallest index among the lanes that hold the maximum (indices are below 2^24: exact as floats)
+            first = (int)(-wave_max(-(float)((bm == m && am < C) ? am : C)));
+            if (first >= C) first = 0;   // a row without an ordered maximum (every entry NaN or -inf)
+            float cnt = 0.0f;
+            for (int c = lane; c < C; c += 64) {
+                const float x = zr[c];
+                s += __expf(x - m);
+                cnt += (x > zy || (x == zy && c < ym)) ? 1.0f : 0.0f;
+            }
+            above = (int)wave_sum(cnt);   // at most C < 2^24 ones: exact
+        } else {
+            for (int c = lane; c < C; c += 64) m = fmaxf(m, zr[c]);
+            m = wave_max(m);
+            for (int c = lane; c < C; c += 64) s += __expf(zr[c] - m);
+        }
         const float l = m + __logf(wave_sum(s));
         const int64_t y = labels[r];
+        const bool ok = y >= 0 && y < C;
         if (lane == 0) {
             lse[r] = l;
-            acc += (y >= 0 && y < C) ? l - zr[y] : __builtin_nanf("");   // a label outside [0, C) poisons the loss instead of reading wild
+            acc += ok ? l - zr[y] : __builtin_nanf("");   // a label outside [0, C) poisons the loss instead of reading wild
+            if constexpr (METER) {
+                if (ok) {   // such a row is not counted either
+                    seen += 1;
+                    top1 += first == (int)y ? 1 : 0;
+                    topk += above < k ? 1 : 0;
+                }
+            }
         }
     }
-    if (lane == 0) ws[wave] = acc;
+    if (lane == 0) {
+        ws[wave] = acc;
+        if constexpr (METER) {
+            hs[wave][0] = seen;
+            hs[wave][1] = top1;
+            hs[wave][2] = topk;
+        }
+    }
     __syncthreads();
     if (tid == 0) {
         float t = 0.0f;
         for (int w = 0; w < HT / 64; ++w) t += ws[w];
         partial[blockIdx.x] = t;
+        if constexpr (METER) {
+            int* hits = reinterpret_cast<int*>(partial + CE_HITS) + 3 * blockIdx.x;
+            int a0 = 0, a1 = 0, a2 = 0;
+            for (int w = 0; w < HT / 64; ++w) {
+                a0 += hs[w][0];
+                a1 += hs[w][1];
+                a2 += hs[w][2];
+            }
+            hits[0] = a0;
+            hits[1] = a1;
+            hits[2] = a2;
+        }
         __threadfence();
         last = atomicAdd(counter, 1u) == gridDim.x - 1;
     }
@@ -371,13 +433,36 @@ __global__ __launch_bounds__(HT) void ce_fwd_kernel(const float* __restrict__ z,
         __threadfence();
         // the partial sums, one per lane of wave 0 (gridDim.x <= 64), joined by the same tree every time
         if (wave == 0) {
-            const float t = wave_sum(lane < (int)gridDim.x ? __builtin_nontemporal_load(partial + lane) : 0.0f);
+            const bool in = lane < (int)gridDim.x;
+            const float t = wave_sum(in ? __builtin_nontemporal_load(partial + lane) : 0.0f);
+            float h0 = 0.0f, h1 = 0.0f, h2 = 0.0f;
+            if constexpr (METER) {
+                // the hit counts: integers of at most rows <= 2^24 in all, so every float sum below is exact
+                const int* hits = reinterpret_cast<const int*>(partial + CE_HITS) + 3 * lane;
+                h0 = wave_sum(in ? (float)__builtin_nontemporal_load(hits) : 0.0f);
+                h1 = wave_sum(in ? (float)__builtin_nontemporal_load(hits + 1) : 0.0f);
+                h2 = wave_sum(in ? (float)__builtin_nontemporal_load(hits + 2) : 0.0f);
+            }
             if (lane == 0) {
-                *loss = t / (float)rows;
+                const float mean = t / (float)rows;
+                *loss = mean;
+                if constexpr (METER) train_meter_log(meter, mean, 0.0f, 0.0f, (int)h0, (int)h1, (int)h2);
                 *counter = 0u;
             }
         }
     }
+}
+
+__global__ __launch_bounds__(HT) void ce_fwd_kernel(const float* __restrict__ z, const int64_t* __restrict__ labels, float* __restrict__ lse,
+                                                    float* __restrict__ loss, float* __restrict__ partial, unsigned* __restrict__ counter,
+                                                    int rows, int C) {
+    ce_fwd_body<false>(z, labels, lse, loss, partial, counter, rows, C, nullptr, 0);
+}
+
+__global__ __launch_bounds__(HT) void ce_meter_fwd_kernel(const float* __restrict__ z, const int64_t* __restrict__ labels,
+                                                          float* __restrict__ lse, float* __restrict__ loss, float* __restrict__ partial,
+                                                          unsigned* __restrict__ counter, int rows, int C, long long* meter, int k) {
+    ce_fwd_body<true>(z, labels, lse, loss, partial, counter, rows, C, meter, k);
 }
 
 // dz = (softmax(z) - onehot) * go / rows
@@ -441,7 +526,6 @@ extern "C" int spv_small_sl_bwd(const float* dout, const float* h, const float* 
     return 0;
 }
 
-constexpr int CE_MAX_WG = 64;
 extern "C" int64_t spv_cross_entropy_workspace_floats() { return CE_MAX_WG + 1; }  // partial sums + the arrival counter (zeroed once by the caller)
 
 extern "C" int spv_cross_entropy_fwd(const float* logits, const int64_t* labels, float* lse, float* loss, float* workspace, int rows, int classes,
@@ -452,6 +536,40 @@ extern "C" int spv_cross_entropy_fwd(const float* logits, const int64_t* labels,
     hipLaunchKernelGGL(ce_fwd_kernel, dim3(wgs), dim3(HT), 0, st, logits, labels, lse, loss, workspace, reinterpret_cast<unsigned*>(workspace + CE_MAX_WG),
                        rows, classes);
     SPV_LAUNCH_CHECK("spv_cross_entropy_fwd");
+    return 0;
+}
+
+// ---- the training meter (include/spv.h): the loss forward that also counts hits and logs the step
+extern "C" int64_t spv_train_meter_words(int64_t capacity) {
+    if (capacity < 1 || capacity > SPV_TRAIN_METER_MAX_CAPACITY) {
+        spv_set_error("spv_train_meter_words: capacity=%lld outside 1..%lld", (long long)capacity, (long long)SPV_TRAIN_METER_MAX_CAPACITY);
+        return 0;
+    }
+    return TM_HEADER + capacity * TM_ROW;
+}
+
+int spv_train_meter_check(const char* name, const void* meter, int k, int rows, int classes) {
+    SPV_CHECK(meter != nullptr, "%s: meter missing", name);
+    SPV_CHECK(((uintptr_t)meter & 7) == 0, "%s: the meter block must be 8-byte aligned", name);
+    SPV_CHECK(k >= 1 && k <= 8, "%s: k=%d outside 1..8", name, k);
+    SPV_CHECK(rows > 0 && rows <= (1 << 24) && classes > 0 && classes < (1 << 24), "%s: rows=%d classes=%d outside 1..2^24 rows, 1..2^24-1 classes",
+              name, rows, classes);
+    return 0;
+}
+
+// partial sums, the arrival counter, one word of padding, the hit partials [CE_MAX_WG][3] (zeroed once by the caller)
+extern "C" int64_t spv_cross_entropy_meter_workspace_floats() { return CE_HITS + 3 * CE_MAX_WG; }
+
+extern "C" int spv_cross_entropy_meter_fwd(const float* logits, const int64_t* labels, float* lse, float* loss, float* workspace, int rows,
+                                           int classes, void* meter, int k, void* stream) {
+    if (int rc = spv_train_meter_check("spv_cross_entropy_meter_fwd", meter, k, rows, classes)) return rc;
+    SPV_CHECK(logits != nullptr && labels != nullptr && lse != nullptr && loss != nullptr && workspace != nullptr,
+              "spv_cross_entropy_meter_fwd: null pointer");
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    const int wgs = std::min(cdiv(rows, HT / 64), CE_MAX_WG);   // spv_cross_entropy_fwd's grid: the same partial order
+    hipLaunchKernelGGL(ce_meter_fwd_kernel, dim3(wgs), dim3(HT), 0, st, logits, labels, lse, loss, workspace,
+                       reinterpret_cast<unsigned*>(workspace + CE_MAX_WG), rows, classes, static_cast<long long*>(meter), k);
+    SPV_LAUNCH_CHECK("spv_cross_entropy_meter_fwd");
     return 0;
 }
 

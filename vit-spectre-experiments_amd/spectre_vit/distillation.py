@@ -211,24 +211,32 @@ class DistillationLoss(nn.Module):
     weighted loss; ``.soft`` and ``.ce`` hold the unweighted soft-target and cross-entropy terms of the last call (device scalars,
     detached), the reference's "Batch Loss/Dist" and "Batch Loss/CE"."""
 
-    def __init__(self, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75):
+    def __init__(self, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75, meter=None):
         super().__init__()
         if not (T > 0 and math.isfinite(T)):
             raise ValueError(f"temperature T={T} must be positive and finite")
         self.T, self.soft_target_loss_weight, self.ce_loss_weight = float(T), float(soft_target_loss_weight), float(ce_loss_weight)
         self.soft = self.ce = None
+        if meter is not None:
+            from .meter import TrainMeter
+            if not isinstance(meter, TrainMeter):
+                raise TypeError(f"meter is a spectre_vit.meter.TrainMeter or None, got {type(meter).__name__}")
+        # a TrainMeter: the forward takes the metered launch -- the same bits, the student's hits counted and the step (loss, soft, ce)
+        # logged into the meter's device block; None: the un-metered launch, exactly
+        self.meter = meter
 
     def forward(self, student_logits, teacher_logits, labels, index=None):
         """index (int64 [rows], on the device): ``teacher_logits`` is then the resident cache -- a TeacherLogitCache or its [n, classes]
         matrix -- and row r's teacher logits are cache[index[r]], read inside the kernel (``hip_ops.distill_loss_cached``)."""
         from . import hip_ops
+        metered = {} if self.meter is None else {"meter": self.meter}
         if index is not None:
             cache = teacher_logits.logits if isinstance(teacher_logits, TeacherLogitCache) else teacher_logits
             loss, self.soft, self.ce = hip_ops.distill_loss_cached(student_logits, cache, index, labels, self.T,
-                                                                   self.soft_target_loss_weight, self.ce_loss_weight)
+                                                                   self.soft_target_loss_weight, self.ce_loss_weight, **metered)
             return loss
         loss, self.soft, self.ce = hip_ops.distill_loss(student_logits, teacher_logits, labels, self.T, self.soft_target_loss_weight,
-                                                        self.ce_loss_weight)
+                                                        self.ce_loss_weight, **metered)
         return loss
 
 

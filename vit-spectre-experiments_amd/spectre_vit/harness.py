@@ -129,6 +129,23 @@ def _ema_args(ema_decay, ema_warmup):
     return dict(ema_decay=float(ema_decay), ema_warmup=bool(ema_warmup))
 
 
+def _train_meter(device_meter, epoch_steps, device):
+    """the harness's device_meter argument -> the epoch's spectre_vit.meter.TrainMeter (one log row per step), or None when off"""
+    if not device_meter:
+        return None
+    from spectre_vit.meter import TrainMeter
+    return TrainMeter(max(epoch_steps, 1), topk=5, device=device)
+
+
+def _check_device_meter(device_meter, distill=False):
+    """raises before any device is touched"""
+    if not isinstance(device_meter, bool):
+        raise ValueError(f"device_meter={device_meter!r} must be True or False")
+    if device_meter and distill:
+        raise ValueError("device_meter=True meters the criterion's launch: the early distill=True form has no criterion on its training "
+                         "path (train_distill has)")
+
+
 def _eager_validate(model, batches, criterion, amp, batch_hook, world, device, float_logits=False):
     """one eager validation pass: every sample of the rank's shard, the loss sample-weighted (the tail batch is short), the sums kept on
     the device and read once.  -> (accuracy, loss, samples)"""
@@ -179,7 +196,7 @@ def _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, uint8):
 def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
           use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
           augment=False, batch_hook=None, graph_eval=False, lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None,
-          skip_nonfinite=False, ema_decay=None, ema_warmup=False):
+          skip_nonfinite=False, ema_decay=None, ema_warmup=False, device_meter=False):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
@@ -201,7 +218,13 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     (spectre_vit.optim.FusedAdamW(ema_decay=...), capturable=True on the eager path too).  After each epoch's validation a second pass
     runs on the averaged weights (inside optimizer.ema_weights(); through the same session with graph_eval=True) and the record gains
     "Accuracy/ValidationEMA" and "Loss/ValidationEMA"; model_ema_best.pt holds optimizer.ema_state_dict(model) of the best such epoch.
-    Every other entry of the record is what it is without averaging."""
+    Every other entry of the record is what it is without averaging.
+    device_meter=True (not with distill): the training criterion carries a spectre_vit.meter.TrainMeter of one log row per step of the
+    epoch, so its loss launch -- eager or replayed -- counts the batch's hits and logs the step on the device: the host issues no
+    argmax / == / sum / accumulate per step, reads the meter ONCE per epoch and resets it.  "Loss/Train" and "Accuracy/Train" (rank
+    local, as without it) come from the meter, the record gains "Accuracy/TrainTop5", and scalars.jsonl gains one
+    {"step", "Batch Loss/Train"} line per step (the reference's loss.item(), train.py:243).  Validation keeps a meter-less criterion."""
+    _check_device_meter(device_meter, distill)
     if augment and (uint8_input or distill):
         raise ValueError("augment=True yields normalised float batches for the plain training step: not with uint8_input or distill")
     ema = _ema_args(ema_decay, ema_warmup)
@@ -226,12 +249,16 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     train_set = SyntheticCifar(n_train, c, device, seed=seed)
     val_set = SyntheticCifar(n_val, c, device, seed=seed + 1)
     criterion = CrossEntropyLoss()  # nn.CrossEntropyLoss() of train.py:196 on the HIP path (spectre_vit/loss.py)
+    val_criterion = criterion
     if graph and distill:
         raise ValueError("graph=True replays the plain training step; the distillation step (teacher forward + KD loss) runs eagerly")
     gstep = session = None
     per_pass = (n_train // world) // batch_size
     control = _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite,
                                  (min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass) * epochs)
+    meter = _train_meter(device_meter, min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass, device)
+    if meter is not None:   # the training criterion logs every step it computes; validation must not
+        criterion = CrossEntropyLoss(meter=meter)
     if graph:
         from spectre_vit.optim import FusedAdamW
         optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
@@ -269,6 +296,7 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         running = torch.zeros((), device=device)
         correct = torch.zeros((), device=device, dtype=torch.int64)
         total, steps = 0, 0
+        first_step = global_step
         for img, label in train_batches():
             if batch_hook is not None:
                 batch_hook("train", global_step, img, label)
@@ -282,9 +310,10 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
                 else:
                     loss = gstep(img, label.long())
                     y_pred = gstep.out
-                correct += (label == torch.argmax(y_pred, dim=1)).sum()
-                total += label.size(0)
-                running += loss.detach()
+                if meter is None:
+                    correct += (label == torch.argmax(y_pred, dim=1)).sum()
+                    total += label.size(0)
+                    running += loss.detach()
                 steps += 1
                 if steps_per_epoch and steps >= steps_per_epoch:
                     break
@@ -298,20 +327,27 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
                     y_pred = student_logits
                 else:
                     y_pred = model(img)
-            correct += (label == torch.argmax(y_pred, dim=1)).sum()
-            total += label.size(0)
+            if meter is None:
+                correct += (label == torch.argmax(y_pred, dim=1)).sum()
+                total += label.size(0)
             if not distill:
                 loss = criterion(y_pred, label.long())
             reducer.zero_grad()
             loss.backward()
             reducer.finish()
             optimizer.step()
-            running += loss.detach()  # accumulated on device: no host sync per step (train.py:243 syncs every step)
+            if meter is None:
+                running += loss.detach()  # accumulated on device: no host sync per step (train.py:243 syncs every step)
             steps += 1
             if steps_per_epoch and steps >= steps_per_epoch:
                 break
-        train_loss = (running / max(steps, 1)).item()
-        train_acc = correct.item() / max(total, 1)
+        if meter is None:
+            train_loss = (running / max(steps, 1)).item()
+            train_acc = correct.item() / max(total, 1)
+        else:
+            metered = meter.read()   # the epoch's one read of the training scalars
+            meter.reset()
+            train_loss, train_acc = metered["loss_mean"], metered["accuracy"]
 
         model.eval()
         val_batch = min(getattr(c, "val_batch_size", batch_size), n_val)
@@ -321,13 +357,15 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
             batches = val_set.batches(val_batch, False, None, rank, world, raw_uint8=val_uint8, drop_last=False)
             if graph_eval:
                 return _graph_validate(session, batches, hook, world)
-            return _eager_validate(model, batches, criterion, use_amp and not distill, hook, world, device)
+            return _eager_validate(model, batches, val_criterion, use_amp and not distill, hook, world, device)
 
         if graph_eval and session is None:
             session = _eval_session(model, n_val, val_batch, rank, world, torch.bfloat16 if use_amp and not distill else None, val_uint8)
         val_acc, val_loss, val_samples = validate(batch_hook)
         rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
                "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
+        if meter is not None:
+            rec["Accuracy/TrainTop5"] = metered["accuracy_topk"]
         if control:
             rec.update(_step_control_record(optimizer))
         if ema:   # the same pass on the averaged weights (a session keeps its own copies: leaving the context does not disturb it)
@@ -335,6 +373,9 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
                 rec["Accuracy/ValidationEMA"], rec["Loss/ValidationEMA"], _ = validate(None)
         history.append(rec)
         if rank == 0:
+            if meter is not None:
+                for k, row in enumerate(metered["rows"]):
+                    log_f.write(json.dumps({"step": first_step + k, "Batch Loss/Train": row[0]}) + "\n")
             log_f.write(json.dumps(rec) + "\n")
             log_f.flush()
             log(rec)
@@ -378,7 +419,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                   use_amp=False, graph=False, augment=True, teacher=None, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75,
                   resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False,
                   lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False, ema_decay=None,
-                  ema_warmup=False, cache_teacher=False, teacher_cache_path=None):
+                  ema_warmup=False, device_meter=False, cache_teacher=False, teacher_cache_path=None):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -395,8 +436,12 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     they are computed once before epoch 0 into a resident spectre_vit.distillation.TeacherLogitCache (sharded over the ranks; loaded from
     teacher_cache_path when that file exists and matches, saved there by rank 0 otherwise), a {"TeacherCache": ...} line is logged, and
     the epochs call neither the view nor the teacher: the loss reads the cache through the batch's index (no "teacher" hook then; the
-    fill calls batch_hook("teacher_fill", block, img_teacher, index)).  Eager, as a data-parallel rank, and graph=True."""
+    fill calls batch_hook("teacher_fill", block, img_teacher, index)).  Eager, as a data-parallel rank, and graph=True.
+    device_meter=True: as in train() -- the DistillationLoss carries a TrainMeter, the host issues no per-step stack / argmax / == / sum
+    / accumulate, and the epoch's "Loss/Train", "Accuracy/Train", "Accuracy/TrainTop5" and the three per-batch loss lines come from
+    ONE read of the meter (its log rows hold each step's loss, soft and CE terms)."""
     from spectre_vit import _native
+    _check_device_meter(device_meter)
     ema = _ema_args(ema_decay, ema_warmup)
     c = parse_config(config_path)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -431,11 +476,12 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     if teacher is None:
         teacher = SyntheticTeacher(c.num_classes, 384, c.in_channels).to(device)
     teacher.eval()
-    criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight)
     val_criterion = CrossEntropyLoss()
     gstep = session = None
     per_pass = (n_train // world) // batch_size
     epoch_steps = min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass
+    meter = _train_meter(device_meter, epoch_steps, device)
+    criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight, **({} if meter is None else {"meter": meter}))
     control = _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite, epoch_steps * epochs)
     if graph:
         from spectre_vit.optim import FusedAdamW
@@ -511,15 +557,22 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                 loss.backward()
                 reducer.finish()
                 optimizer.step()
-            torch.stack((loss.detach(), soft, ce), out=batch_losses[steps])
-            correct += (label == torch.argmax(y_pred, dim=1)).sum()
-            total += label.size(0)
+            if meter is None:
+                torch.stack((loss.detach(), soft, ce), out=batch_losses[steps])
+                correct += (label == torch.argmax(y_pred, dim=1)).sum()
+                total += label.size(0)
             steps += 1
             if steps >= epoch_steps:
                 break
-        per_batch = batch_losses[:steps].tolist()   # the epoch's one read of the per-batch scalars
-        train_loss = sum(r[0] for r in per_batch) / max(steps, 1)
-        train_acc = correct.item() / max(total, 1)
+        if meter is None:
+            per_batch = batch_losses[:steps].tolist()   # the epoch's one read of the per-batch scalars
+            train_loss = sum(r[0] for r in per_batch) / max(steps, 1)
+            train_acc = correct.item() / max(total, 1)
+        else:
+            metered = meter.read()   # the epoch's one read: every step's (loss, soft, ce) row and the hit totals
+            meter.reset()
+            per_batch = [row[:3] for row in metered["rows"]]
+            train_loss, train_acc = metered["loss_mean"], metered["accuracy"]
 
         model.eval()
         val_batch = min(getattr(c, "val_batch_size", batch_size), n_val)
@@ -535,6 +588,8 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
         val_acc, val_loss, val_samples = validate(batch_hook)
         rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
                "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
+        if meter is not None:
+            rec["Accuracy/TrainTop5"] = metered["accuracy_topk"]
         if control:
             rec.update(_step_control_record(optimizer))
         if ema:
@@ -597,6 +652,9 @@ def build_parser():
                     help="keep an exponential moving average of the weights inside the optimizer launch, validate it after every epoch "
                          "and save model_ema_best.pt")
     ap.add_argument("--ema-warmup", action="store_true", help="--ema-decay: the decay warms up as min(decay, (1 + step) / (10 + step))")
+    ap.add_argument("--device-meter", action="store_true",
+                    help="keep the training loss / accuracy books on the device inside the loss launch (spectre_vit.meter.TrainMeter): "
+                         "no host-issued argmax / == / sum / accumulate per step, one read per epoch, per-step loss lines")
     ap.add_argument("--out", default="runs/spectre_vit")
     return ap
 
@@ -607,10 +665,11 @@ def main(argv=None):
                    skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup)
     if a.distill_paired:
         train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out,
-                      graph_eval=a.graph_eval, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache, **control)
+                      graph_eval=a.graph_eval, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache,
+                      device_meter=a.device_meter, **control)
         return
     train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph,
-          model=a.model, augment=a.augment, graph_eval=a.graph_eval, **control)
+          model=a.model, augment=a.augment, graph_eval=a.graph_eval, device_meter=a.device_meter, **control)
 
 
 if __name__ == "__main__":

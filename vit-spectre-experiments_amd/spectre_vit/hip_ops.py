@@ -1152,7 +1152,46 @@ class CrossEntropyFn(torch.autograd.Function):
         return dz, None
 
 
-def cross_entropy(logits, labels):
+def _meter_block(meter, dev, what):
+    """the block and k of a spectre_vit.meter.TrainMeter, checked against the device of the logits"""
+    block = meter.tensor()
+    if block.dtype != torch.int64 or not block.is_contiguous() or block.device != dev:
+        raise ValueError(f"{what}: the meter's block is a contiguous int64 tensor on the logits' device ({dev}), got {block.dtype} on {block.device}")
+    return block, int(meter.topk)
+
+
+_ce_meter_workspaces = {}
+
+
+class CrossEntropyMeterFn(torch.autograd.Function):
+    """CrossEntropyFn with the training meter (spectre_vit.meter.TrainMeter): the forward launch also counts the batch's top-1 / top-k
+    hits and logs the step into the meter's block; loss and lse keep CrossEntropyFn's bits, the backward is CrossEntropyFn's."""
+
+    @staticmethod
+    def forward(ctx, logits, labels, meter):
+        _require_gpu(logits, labels)
+        if logits.dim() != 2 or logits.dtype != torch.float32 or labels.dtype != torch.int64 or labels.shape != logits.shape[:1]:
+            raise ValueError("cross_entropy: fp32 logits [rows, classes] and int64 labels [rows] expected")
+        block, k = _meter_block(meter, logits.device, "cross_entropy")
+        z = logits.contiguous()
+        y = labels.contiguous()
+        rows, C = z.shape
+        lse = torch.empty((rows,), dtype=torch.float32, device=z.device)
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
+        _native.call("spv_cross_entropy_meter_fwd", _p(z), _p(y), _p(lse), _p(loss),
+                     _p(_zero_workspace(_ce_meter_workspaces, z.device, "spv_cross_entropy_meter_workspace_floats")), rows, C, _p(block), k, _stream())
+        ctx.save_for_backward(z, y, lse)
+        return loss
+
+    @staticmethod
+    def backward(ctx, go):
+        return CrossEntropyFn.backward(ctx, go) + (None,)
+
+
+def cross_entropy(logits, labels, meter=None):
+    """meter (a spectre_vit.meter.TrainMeter): the metered launch -- the same loss bits, and the step logs itself"""
+    if meter is not None:
+        return CrossEntropyMeterFn.apply(logits, labels, meter)
     return CrossEntropyFn.apply(logits, labels)
 
 
@@ -1215,8 +1254,44 @@ class DistillLossFn(torch.autograd.Function):
         return dz, None, None, None, None, None
 
 
-def distill_loss(student_logits, teacher_logits, labels, T=2.0, w_soft=0.25, w_ce=0.75):
-    """(loss, soft, ce): the weighted loss (differentiable in the student logits) and the two unweighted terms, detached"""
+_distill_meter_workspaces = {}
+
+
+class DistillLossMeterFn(torch.autograd.Function):
+    """DistillLossFn with the training meter: the forward launch also counts the student's top-1 / top-k hits and logs the step (loss,
+    soft, ce) into the meter's block; every output keeps DistillLossFn's bits, the backward is DistillLossFn's."""
+
+    @staticmethod
+    def forward(ctx, student_logits, teacher_logits, labels, T, w_soft, w_ce, meter):
+        _require_gpu(student_logits, teacher_logits, labels)
+        z, t = student_logits, teacher_logits
+        if (z.dim() != 2 or z.dtype != torch.float32 or t.dtype != torch.float32 or t.shape != z.shape or labels.dtype != torch.int64
+                or labels.shape != z.shape[:1]):
+            raise ValueError("distill_loss: fp32 student and teacher logits [rows, classes] and int64 labels [rows] expected")
+        block, k = _meter_block(meter, z.device, "distill_loss")
+        z, t, y = z.contiguous(), t.detach().contiguous(), labels.contiguous()
+        rows, C = z.shape
+        lse = torch.empty((3, rows), dtype=torch.float32, device=z.device)
+        out = torch.empty((3,), dtype=torch.float32, device=z.device)
+        _native.call("spv_distill_loss_meter_fwd", _p(z), _p(t), _p(y), _p(lse), _p(out),
+                     _p(_zero_workspace(_distill_meter_workspaces, z.device, "spv_distill_loss_meter_workspace_floats")), rows, C, float(T),
+                     float(w_soft), float(w_ce), _p(block), k, _stream())
+        ctx.save_for_backward(z, t, y, lse)
+        ctx.consts = (float(T), float(w_soft), float(w_ce))
+        loss, soft, ce = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(soft, ce)
+        return loss, soft, ce
+
+    @staticmethod
+    def backward(ctx, go, _gsoft, _gce):
+        return DistillLossFn.backward(ctx, go, _gsoft, _gce) + (None,)
+
+
+def distill_loss(student_logits, teacher_logits, labels, T=2.0, w_soft=0.25, w_ce=0.75, meter=None):
+    """(loss, soft, ce): the weighted loss (differentiable in the student logits) and the two unweighted terms, detached.
+    meter (a spectre_vit.meter.TrainMeter): the metered launch -- the same bits, and the step logs itself."""
+    if meter is not None:
+        return DistillLossMeterFn.apply(student_logits, teacher_logits, labels, T, w_soft, w_ce, meter)
     return DistillLossFn.apply(student_logits, teacher_logits, labels, T, w_soft, w_ce)
 
 
@@ -1261,8 +1336,42 @@ class DistillLossIdxFn(torch.autograd.Function):
         return dz, None, None, None, None, None, None
 
 
-def distill_loss_cached(student_logits, cache, index, labels, T=2.0, w_soft=0.25, w_ce=0.75):
+class DistillLossIdxMeterFn(torch.autograd.Function):
+    """DistillLossIdxFn with the training meter (see DistillLossMeterFn): the bits and the backward of DistillLossIdxFn."""
+
+    @staticmethod
+    def forward(ctx, student_logits, cache, index, labels, T, w_soft, w_ce, meter):
+        _require_gpu(student_logits, cache, index, labels)
+        z = student_logits
+        if (z.dim() != 2 or z.dtype != torch.float32 or cache.dim() != 2 or cache.dtype != torch.float32 or cache.shape[1] != z.shape[1]
+                or cache.shape[0] < 1 or not cache.is_contiguous() or labels.dtype != torch.int64 or labels.shape != z.shape[:1]
+                or index.dtype != torch.int64 or index.shape != z.shape[:1]):
+            raise ValueError("distill_loss_cached: fp32 student logits [rows, classes], a contiguous fp32 cache [n, classes], int64 index "
+                             "[rows] and int64 labels [rows] expected")
+        block, k = _meter_block(meter, z.device, "distill_loss_cached")
+        z, t, idx, y = z.contiguous(), cache.detach(), index.contiguous(), labels.contiguous()
+        rows, C = z.shape
+        lse = torch.empty((3, rows), dtype=torch.float32, device=z.device)
+        out = torch.empty((3,), dtype=torch.float32, device=z.device)
+        _native.call("spv_distill_loss_idx_meter_fwd", _p(z), _p(t), _p(idx), _p(y), _p(lse), _p(out),
+                     _p(_zero_workspace(_distill_meter_workspaces, z.device, "spv_distill_loss_meter_workspace_floats")), rows, t.shape[0], C,
+                     float(T), float(w_soft), float(w_ce), _p(block), k, _stream())
+        ctx.save_for_backward(z, y, lse)
+        ctx.resident = (t, idx)
+        ctx.consts = (float(T), float(w_soft), float(w_ce))
+        loss, soft, ce = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(soft, ce)
+        return loss, soft, ce
+
+    @staticmethod
+    def backward(ctx, go, _gsoft, _gce):
+        return DistillLossIdxFn.backward(ctx, go, _gsoft, _gce) + (None,)
+
+
+def distill_loss_cached(student_logits, cache, index, labels, T=2.0, w_soft=0.25, w_ce=0.75, meter=None):
     """distill_loss(student_logits, cache[index], labels, ...) without materialising cache[index]: (loss, soft, ce)"""
+    if meter is not None:
+        return DistillLossIdxMeterFn.apply(student_logits, cache, index, labels, T, w_soft, w_ce, meter)
     return DistillLossIdxFn.apply(student_logits, cache, index, labels, T, w_soft, w_ce)
 
 

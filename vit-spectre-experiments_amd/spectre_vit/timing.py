@@ -29,6 +29,10 @@ _WORK_MODELS = {
     # (rows, n_cache, classes): the same traffic with the teacher's rows gathered from the cache, + the index; the store copies rows once
     "spv_distill_loss_idx_fwd": lambda i: ("distill_loss_idx_fwd", (i[0], i[2]), F32, "hbm", i[0] * (i[2] * 8.0 + 8.0)),
     "spv_distill_loss_idx_bwd": lambda i: ("distill_loss_idx_bwd", (i[0], i[2]), F32, "hbm", i[0] * (i[2] * 12.0 + 8.0)),
+    # the metered forwards (rows, classes[, n_cache], k): the un-metered traffic; the meter's row and header are a few words
+    "spv_cross_entropy_meter_fwd": lambda i: ("cross_entropy_meter_fwd", i[0:2], F32, "hbm", i[0] * i[1] * 4.0),
+    "spv_distill_loss_meter_fwd": lambda i: ("distill_loss_meter_fwd", i[0:2], F32, "hbm", i[0] * i[1] * 8.0),
+    "spv_distill_loss_idx_meter_fwd": lambda i: ("distill_loss_idx_meter_fwd", (i[0], i[2]), F32, "hbm", i[0] * (i[2] * 8.0 + 8.0)),
     "spv_logit_cache_store": lambda i: ("logit_cache_store", (i[0], i[2]), F32, "hbm", i[0] * (i[2] * 8.0 + 8.0)),
     # (batch, n_src, chans, n, resize, crop, dtype): the uint8 images read, the cropped view written once
     "spv_teacher_view_u8": lambda i: ("teacher_view", (i[0], i[2], i[3], i[5]), i[6], "hbm",
