@@ -318,6 +318,36 @@ int spv_haar_dwt(const void* x, void* y, int batch, int tokens, int dim, int axi
 int spv_set_seed_device_ptr(const void* seed_word);
 int spv_seed_advance(void* seed_word, void* stream);
 
+/* ---- the step prologue: the small launches that open a graph-replayed training step, as one ----------------------------------------
+ * spv_seed_advance, spv_weight_shadows_multi, spv_spectral_fold_bf16 (or spv_spectral_fold: fold_out_bf16 NULL), spv_patchify with
+ * transposed = 2 and spv_embed_posbias depend on nothing but the parameters and the image, and on each other not at all: one
+ * 256-thread launch whose workgroup ranges are dealt to these roles.  Every role is optional -- a NULL leading pointer or a zero count
+ * leaves it out -- and a role's workgroup computes what the same workgroup of the separate launch computes: the same bits.
+ * Pointers as in the separate entry points (all device memory); the struct itself is read on the host. */
+typedef struct spv_prologue_jobs {
+    void* seed_word;                                   /* the dropout seed word (spv_seed_advance); NULL: not stepped */
+    const void* shadow_table;                          /* spv_weight_shadows_multi's table and tile lists */
+    const int* tile_tensor;
+    const int* tile_x;
+    const int* tile_y;
+    int ntiles, shadow_dtype;
+    const float* fold_w;                               /* spv_spectral_fold_bf16: proj_w, freq_h, freq_w -> w_full (+ bf16 copy) */
+    const float* fold_fh;
+    const float* fold_fw;
+    float* fold_out;
+    void* fold_out_bf16;
+    int fold_embed, fold_chans, fold_patch, pad0;
+    const float* patch_img;                            /* spv_patchify(img, out, ..., ld, transposed = 2, dtype) */
+    void* patch_out;
+    int patch_batch, patch_chans, patch_height, patch_width, patch_size, patch_ld, patch_dtype, pad1;
+    const float* pos_pos;                              /* spv_embed_posbias(pos, bias, cls, out, patches, embed) */
+    const float* pos_bias;
+    const float* pos_cls;
+    float* pos_out;
+    int pos_patches, pos_embed;
+} spv_prologue_jobs;
+int spv_step_prologue(const spv_prologue_jobs* jobs, void* stream);
+
 /* ---- AdamW over many tensors in one launch ------------------------------------------------------------
  * The optimizer step the script drives: torch.optim.AdamW(lr, betas, weight_decay), spectre_vit/repl/train.py:199-201,237
  * (decoupled weight decay, bias correction; amsgrad / maximize off).  `table`: device array of {float* p; const float* g;
@@ -504,6 +534,14 @@ int spv_small_sl_bwd(const float* dout, const float* h, const float* xs, const f
                      const float* W, const float* gamma, const float* beta, float* dh, void* dx, float* dW,
                      float* dgamma, float* dbeta, float* dbias, float* partials, int rows, int n, int k, int dx_dtype,
                      void* stream);
+/* The two launches of spv_small_sl_bwd on their own (it calls both, in this order).  Nothing inside a backward pass reads dW, dgamma,
+ * dbeta or dbias, so a caller may issue the weights launch later, beside other work: it reads dh and partials (written by the rows
+ * launch) and xs, in 256-thread workgroups with 4 KB of LDS.  Same bits either way. */
+int spv_small_sl_bwd_rows(const float* dout, const float* h, const float* mean, const float* rstd, const float* W,
+                          const float* gamma, const float* beta, float* dh, void* dx, float* partials, int rows, int n, int k,
+                          int dx_dtype, void* stream);
+int spv_small_sl_bwd_w(const float* dh, const float* xs, const float* partials, float* dW, float* dgamma, float* dbeta,
+                       float* dbias, int rows, int n, int k, void* stream);
 /* loss = mean_r(logsumexp(logits[r]) - logits[r][labels[r]]) (fp32 logits [rows, classes], int64 labels; a label outside
  * [0, classes) makes the loss NaN).  lse [rows] is kept for the backward: dlogits = (softmax - onehot) * grad_out[0] / rows.
  * workspace: spv_cross_entropy_workspace_floats() floats, ZEROED ONCE by the caller (it holds an arrival counter that

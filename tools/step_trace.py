@@ -16,8 +16,9 @@ def main():
             rows.append(r)
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     names = [r["_name"] for r in rows]
-    # a step starts at the patchify kernel
-    starts = [i for i, n in enumerate(names) if "patchify" in n]
+    # a step starts at its prologue launch (the patch rows are one of its roles) -- in a trace from before it, at the patchify kernel
+    marks = ("step_prologue",) if any("step_prologue" in n for n in names) else ("patchify",)
+    starts = [i for i, n in enumerate(names) if any(m in n for m in marks)]
     k = int(sys.argv[2]) if len(sys.argv) > 2 else 2
     a, b = starts[-k - 1], starts[-k]
     t0 = int(rows[a]["Start_Timestamp"])

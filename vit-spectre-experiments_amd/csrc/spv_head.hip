@@ -256,42 +256,51 @@ __global__ __launch_bounds__(HT) void small_sl_bwd_rows_kernel(const float* __re
     }
 }
 
-// ---- backward, weights: workgroup (output pair, 128-column block): 4 row groups x 128 columns, dW[o][c] = sum_r dh[r][o] x[r][c] with the
-// row groups' sums joined through LDS in a fixed order; the last workgroup folds dgamma / dbeta / dbias from the partials
-constexpr int WT = 1024, WCOLS = 128, WGRP = WT / WCOLS, WOUT = 2;
+// ---- backward, weights: workgroup (output pair, 32-column block): 8 row groups x 32 columns, dW[o][c] = sum_r dh[r][o] x[r][c] -- group g
+// takes rows g, g + 8, ... in that order, one fmaf each -- with the row groups' sums joined through LDS in index order; the last
+// workgroup folds dgamma / dbeta / dbias from the partials (16 slices per column, slice q = partials q, q + 16, ... in that order,
+// joined in index order).  Nothing inside the backward pass reads these four gradients, so the launch runs beside the batched layer
+// weight gradients (hip_ops: held): 4 waves and 4 KB of LDS per workgroup, so that it fits on a CU next to that kernel's workgroups.
+// The 1024-thread form this replaces had the same 8 row groups (1024 / 128 columns) walking rows g, g + 8, ... and joined them in the
+// same order, 32 rows in flight where there are now 16: only the batching of the loads differs, so every output bit is the same.
+// A wave now spans two row groups, so the dh reads are per-lane loads where they were wave-uniform.
+constexpr int WT = 256, WCOLS = 32, WGRP = WT / WCOLS, WOUT = 2;
 __global__ __launch_bounds__(WT) void small_sl_bwd_w_kernel(const float* __restrict__ dh, const float* __restrict__ xs,
                                                             const float* __restrict__ partials, float* __restrict__ dW,
                                                             float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ dbias,
                                                             int rows, int n, int k, int nparts, int cblocks) {
-    __shared__ float red[WGRP][WOUT][WCOLS];
+    constexpr int SL = 16;   // slices of the fold
+    __shared__ float smem[SL * 64];   // the fold's [SL][64]; the join's [WGRP][WOUT][WCOLS] (512 floats)
     const int tid = threadIdx.x;
     const int njobs = ((n + WOUT - 1) / WOUT) * cblocks;
     if ((int)blockIdx.x == njobs) {
-        // fold: thread (column e, part slice q) -- 16 slices of the partials per column, joined in a fixed order
-        constexpr int SL = 16;
-        float* fold = &red[0][0][0];   // [SL][64] floats per pass
+        // fold: thread (column e, part slices q, q + 4, q + 8, q + 12) -- 16 slices of the partials per column, joined in a fixed order
         for (int e0 = 0; e0 < 3 * n; e0 += 64) {
-            const int e = e0 + (tid & 63), q = tid >> 6;
-            float a = 0.0f;
-            if (e < 3 * n) {
-                const int w = e / n, c = e - w * n;
-                for (int p0 = q; p0 < nparts; p0 += SL * 8) {   // eight independent loads in flight
-                    float v[8];
+            const int e = e0 + (tid & 63);
 #pragma unroll
-                    for (int j = 0; j < 8; ++j) {
-                        const int pp = p0 + j * SL;
-                        v[j] = partials[((size_t)min(pp, nparts - 1) * 3 + w) * n + c] * (pp < nparts ? 1.0f : 0.0f);
+            for (int u = 0; u < SL / (WT / 64); ++u) {
+                const int q = (tid >> 6) + u * (WT / 64);
+                float a = 0.0f;
+                if (e < 3 * n) {
+                    const int w = e / n, c = e - w * n;
+                    for (int p0 = q; p0 < nparts; p0 += SL * 8) {   // eight independent loads in flight
+                        float v[8];
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) {
+                            const int pp = p0 + j * SL;
+                            v[j] = partials[((size_t)min(pp, nparts - 1) * 3 + w) * n + c] * (pp < nparts ? 1.0f : 0.0f);
+                        }
+#pragma unroll
+                        for (int j = 0; j < 8; ++j) a += v[j];
                     }
-#pragma unroll
-                    for (int j = 0; j < 8; ++j) a += v[j];
                 }
+                smem[q * 64 + (tid & 63)] = a;
             }
-            fold[q * 64 + (tid & 63)] = a;
             __syncthreads();
             if (tid < 64 && e < 3 * n) {
                 float t = 0.0f;
 #pragma unroll
-                for (int j = 0; j < SL; ++j) t += fold[j * 64 + tid];
+                for (int j = 0; j < SL; ++j) t += smem[j * 64 + tid];
                 const int w = e / n, c = e - w * n;
                 (w == 0 ? dgamma : (w == 1 ? dbeta : dbias))[c] = t;
             }
@@ -299,12 +308,13 @@ __global__ __launch_bounds__(WT) void small_sl_bwd_w_kernel(const float* __restr
         }
         return;
     }
+    float (*red)[WOUT][WCOLS] = reinterpret_cast<float (*)[WOUT][WCOLS]>(smem);
     const int o0 = ((int)blockIdx.x / cblocks) * WOUT, c = ((int)blockIdx.x % cblocks) * WCOLS + (tid & (WCOLS - 1));
-    const int g = __builtin_amdgcn_readfirstlane(tid / WCOLS);   // wave-uniform: the dh reads below are scalar loads
+    const int g = tid / WCOLS;
     const int o1 = min(o0 + 1, n - 1);
     const int cc = min(c, k - 1);
     float a0 = 0.0f, a1 = 0.0f;
-    constexpr int RB = 32;   // rows in flight
+    constexpr int RB = 16;   // rows in flight
     for (int rb = g; rb < rows; rb += WGRP * RB) {
         float x[RB], d0[RB], d1[RB];
 #pragma unroll
@@ -507,23 +517,36 @@ extern "C" int spv_small_sl_fwd(const void* xa, int64_t lda, const void* xb, int
     return 0;
 }
 
-extern "C" int spv_small_sl_bwd(const float* dout, const float* h, const float* xs, const float* mean, const float* rstd, const float* W,
-                                const float* gamma, const float* beta, float* dh, void* dx, float* dW, float* dgamma, float* dbeta,
-                                float* dbias, float* partials, int rows, int n, int k, int dx_dtype, void* stream) {
-    SPV_CHECK(spv_small_sl_supported(rows, n, k), "spv_small_sl_bwd: rows=%d n=%d k=%d outside the small-rows kernel", rows, n, k);
-    SPV_CHECK(dx_dtype == SPV_F32 || dx_dtype == SPV_BF16, "spv_small_sl_bwd: bad dtype %d", dx_dtype);
+extern "C" int spv_small_sl_bwd_rows(const float* dout, const float* h, const float* mean, const float* rstd, const float* W, const float* gamma,
+                                     const float* beta, float* dh, void* dx, float* partials, int rows, int n, int k, int dx_dtype, void* stream) {
+    SPV_CHECK(spv_small_sl_supported(rows, n, k), "spv_small_sl_bwd_rows: rows=%d n=%d k=%d outside the small-rows kernel", rows, n, k);
+    SPV_CHECK(dx_dtype == SPV_F32 || dx_dtype == SPV_BF16, "spv_small_sl_bwd_rows: bad dtype %d", dx_dtype);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int nparts = cdiv(rows, HR);
     if (dx_dtype == SPV_BF16)
         hipLaunchKernelGGL((small_sl_bwd_rows_kernel<bf16_t>), dim3(nparts), dim3(HT), 0, st, dout, h, mean, rstd, gamma, beta, W, dh, dx, partials, rows, n, k);
     else
         hipLaunchKernelGGL((small_sl_bwd_rows_kernel<float>), dim3(nparts), dim3(HT), 0, st, dout, h, mean, rstd, gamma, beta, W, dh, dx, partials, rows, n, k);
-    SPV_LAUNCH_CHECK("spv_small_sl_bwd(rows)");
-    const int cblocks = cdiv(k, WCOLS);
-    hipLaunchKernelGGL(small_sl_bwd_w_kernel, dim3(cdiv(n, WOUT) * cblocks + 1), dim3(WT), 0, st, dh, xs, partials, dW, dgamma, dbeta, dbias, rows,
-                       n, k, nparts, cblocks);
-    SPV_LAUNCH_CHECK("spv_small_sl_bwd(weights)");
+    SPV_LAUNCH_CHECK("spv_small_sl_bwd_rows");
     return 0;
+}
+
+extern "C" int spv_small_sl_bwd_w(const float* dh, const float* xs, const float* partials, float* dW, float* dgamma, float* dbeta, float* dbias,
+                                  int rows, int n, int k, void* stream) {
+    SPV_CHECK(spv_small_sl_supported(rows, n, k), "spv_small_sl_bwd_w: rows=%d n=%d k=%d outside the small-rows kernel", rows, n, k);
+    SPV_CHECK(dh && xs && partials && dW && dgamma && dbeta && dbias, "spv_small_sl_bwd_w: null pointer");
+    const int cblocks = cdiv(k, WCOLS);
+    hipLaunchKernelGGL(small_sl_bwd_w_kernel, dim3(cdiv(n, WOUT) * cblocks + 1), dim3(WT), 0, static_cast<hipStream_t>(stream), dh, xs, partials,
+                       dW, dgamma, dbeta, dbias, rows, n, k, cdiv(rows, HR), cblocks);
+    SPV_LAUNCH_CHECK("spv_small_sl_bwd_w");
+    return 0;
+}
+
+extern "C" int spv_small_sl_bwd(const float* dout, const float* h, const float* xs, const float* mean, const float* rstd, const float* W,
+                                const float* gamma, const float* beta, float* dh, void* dx, float* dW, float* dgamma, float* dbeta,
+                                float* dbias, float* partials, int rows, int n, int k, int dx_dtype, void* stream) {
+    if (int rc = spv_small_sl_bwd_rows(dout, h, mean, rstd, W, gamma, beta, dh, dx, partials, rows, n, k, dx_dtype, stream)) return rc;
+    return spv_small_sl_bwd_w(dh, xs, partials, dW, dgamma, dbeta, dbias, rows, n, k, stream);
 }
 
 extern "C" int64_t spv_cross_entropy_workspace_floats() { return CE_MAX_WG + 1; }  // partial sums + the arrival counter (zeroed once by the caller)

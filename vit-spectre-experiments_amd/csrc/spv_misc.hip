@@ -1,6 +1,7 @@
 // spv_misc.hip -- error plumbing + small bandwidth kernels (casts, transposes, GELU, column sums).
 #include "spv_common.h"
 #include "spv_adamw_core.h"
+#include "spv_prologue_core.h"
 
 #include <string.h>
 
@@ -64,55 +65,7 @@ __global__ __launch_bounds__(256) void cast_transpose_kernel(const TI* __restric
     }
 }
 
-// One pass over an fp32 weight [rows, cols]: the plain copy in the compute dtype (skipped when plain == nullptr) and the
-// transposed copy [cols, ld] (zero beyond rows) -- the two operand layouts the NT GEMMs read.  Run once per weight per
-// training step (the copies cannot be cached: see hip_ops._ShadowCache).
-template <typename TO>
-__device__ __forceinline__ void weight_shadow_tile(const float* __restrict__ src, TO* __restrict__ plain, TO* __restrict__ tr, int rows,
-                                                   int cols, int ld, int bx, int by, float (*tile)[65]) {
-    // 32 (rows) x 64 (cols) tile: 16-byte loads along the columns, the transposed copy leaves as 8 consecutive rows per thread
-    const int r0 = by * 32, c0 = bx * 64;
-    const int t = threadIdx.x;
-    const bool vec = (cols & 3) == 0;
-#pragma unroll
-    for (int pass = 0; pass < 2; ++pass) {
-        const int rl = pass * 16 + (t >> 4), c4 = (t & 15) * 4;
-        const int r = r0 + rl, c = c0 + c4;
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (r < rows) {
-            if (vec && c + 3 < cols) {
-                const float4 f = *reinterpret_cast<const float4*>(src + (size_t)r * cols + c);
-                v[0] = f.x; v[1] = f.y; v[2] = f.z; v[3] = f.w;
-                if (plain != nullptr) io<TO>::st4(plain + (size_t)r * cols + c, v);
-            } else {
-                for (int u = 0; u < 4; ++u)
-                    if (c + u < cols) {
-                        v[u] = src[(size_t)r * cols + c + u];
-                        if (plain != nullptr) io<TO>::st(plain + (size_t)r * cols + c + u, v[u]);
-                    }
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < 4; ++u) tile[rl][c4 + u] = v[u];
-    }
-    __syncthreads();
-    const int cl = t >> 2, r8 = (t & 3) * 8;  // column cl of the tile, rows r8 .. r8 + 7
-    const int c = c0 + cl;
-    if (c < cols) {
-        TO* o = tr + (size_t)c * ld + r0 + r8;
-        if (r0 + r8 + 7 < ld && (ld & 7) == 0) {
-            float a[4], b[4];
-#pragma unroll
-            for (int u = 0; u < 4; ++u) { a[u] = tile[r8 + u][cl]; b[u] = tile[r8 + 4 + u][cl]; }
-            io<TO>::st4(o, a);
-            io<TO>::st4(o + 4, b);
-        } else {
-            for (int u = 0; u < 8; ++u)
-                if (r0 + r8 + u < ld) io<TO>::st(o + u, tile[r8 + u][cl]);
-        }
-    }
-}
-
+// (weight_shadow_tile, the body of the three kernels that cast weights: spv_prologue_core.h)
 template <typename TO>
 __global__ __launch_bounds__(256) void weight_shadow_kernel(const float* __restrict__ src, TO* __restrict__ plain, TO* __restrict__ tr,
                                                             int rows, int cols, int ld) {
@@ -122,7 +75,6 @@ __global__ __launch_bounds__(256) void weight_shadow_kernel(const float* __restr
 
 // every weight of the model in ONE launch (8 launches of 4.9 us each per training step otherwise): workgroup b serves tile
 // (tile_x[b], tile_y[b]) of tensor tile_tensor[b]
-struct ShadowTensor { const float* src; void* plain; void* tr; int rows, cols, ld, pad; };
 template <typename TO>
 __global__ __launch_bounds__(256) void weight_shadow_multi_kernel(const ShadowTensor* __restrict__ tab, const int* __restrict__ tile_tensor,
                                                                   const int* __restrict__ tile_x, const int* __restrict__ tile_y) {
@@ -373,6 +325,7 @@ __global__ __launch_bounds__(256) void adamw_multi_ema_kernel(const AdamTensor* 
     adamw_chunk<false, true>(a, n, off, lr, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2, step_dev, 1.0f, ema_tab[t], ema_w, ema_warmup,
                              ema_step);
 }
+
 }  // namespace
 
 extern "C" int spv_adamw_multi(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr,
@@ -415,7 +368,60 @@ int spv_seed_ptr_set_patch(const unsigned long long* p);
 int spv_seed_ptr_set_attn(const unsigned long long* p);
 int spv_seed_ptr_set_gemm(const unsigned long long* p);
 namespace {
-__global__ void seed_advance_kernel(unsigned long long* p) { *p += 0x9e3779b97f4a7c15ull; }
+__global__ void seed_advance_kernel(unsigned long long* p) { *p += SEED_STEP; }
+
+// ---- the step prologue: the five launches that open a graph-replayed training step as ONE.  They are mutually independent -- each
+// reads only the post-optimizer parameters or the image buffer, and all are needed only in front of the token GEMM -- but as five
+// dependent graph nodes of 1 .. 1536 workgroups each paid its own launch and drain.  Workgroup ranges are dealt to the roles in the
+// order seed, shadows, fold, patch rows, position rows; a role's workgroup runs the body of its stand-alone kernel with that kernel's
+// grid, so every output bit is the stand-alone launch's.
+struct PrologueArgs {
+    spv_prologue_jobs j;
+    int n_seed, n_shadow, n_fold, n_patch, n_pos;   // workgroups per role (0: the role is absent)
+    int patch_vec4;
+};
+
+__global__ __launch_bounds__(256) void step_prologue_kernel(const PrologueArgs a) {
+    __shared__ float tile[32][65];   // the shadows' transpose tile; the other roles use no LDS
+    int bid = blockIdx.x;
+    if (bid < a.n_seed) {
+        if (threadIdx.x == 0) *static_cast<unsigned long long*>(a.j.seed_word) += SEED_STEP;
+        return;
+    }
+    bid -= a.n_seed;
+    if (bid < a.n_shadow) {
+        const ShadowTensor t = static_cast<const ShadowTensor*>(a.j.shadow_table)[a.j.tile_tensor[bid]];
+        if (a.j.shadow_dtype == SPV_BF16)
+            weight_shadow_tile<bf16_t>(t.src, static_cast<bf16_t*>(t.plain), static_cast<bf16_t*>(t.tr), t.rows, t.cols, t.ld, a.j.tile_x[bid],
+                                       a.j.tile_y[bid], tile);
+        else
+            weight_shadow_tile<float>(t.src, static_cast<float*>(t.plain), static_cast<float*>(t.tr), t.rows, t.cols, t.ld, a.j.tile_x[bid],
+                                      a.j.tile_y[bid], tile);
+        return;
+    }
+    bid -= a.n_shadow;
+    if (bid < a.n_fold) {
+        spectral_fold_body(a.j.fold_w, a.j.fold_fh, a.j.fold_fw, a.j.fold_out, a.j.fold_embed, a.j.fold_chans, a.j.fold_patch,
+                           static_cast<bf16_t*>(a.j.fold_out_bf16), bid, a.n_fold);
+        return;
+    }
+    bid -= a.n_fold;
+    if (bid < a.n_patch) {
+        const bool bf = a.j.patch_dtype == SPV_BF16;
+        if (!a.patch_vec4)
+            patchify_body(a.j.patch_img, a.j.patch_out, a.j.patch_batch, a.j.patch_chans, a.j.patch_height, a.j.patch_width, a.j.patch_size,
+                          a.j.patch_ld, 2, bf, bid, a.n_patch);
+        else if (bf)
+            patchify_vec4_body<bf16_t>(a.j.patch_img, static_cast<bf16_t*>(a.j.patch_out), a.j.patch_batch, a.j.patch_chans, a.j.patch_height,
+                                       a.j.patch_width, a.j.patch_size, a.j.patch_ld, 1, bid, a.n_patch);
+        else
+            patchify_vec4_body<float>(a.j.patch_img, static_cast<float*>(a.j.patch_out), a.j.patch_batch, a.j.patch_chans, a.j.patch_height,
+                                      a.j.patch_width, a.j.patch_size, a.j.patch_ld, 1, bid, a.n_patch);
+        return;
+    }
+    bid -= a.n_patch;
+    if (bid < a.n_pos) posbias_body(a.j.pos_pos, a.j.pos_bias, a.j.pos_cls, a.j.pos_out, a.j.pos_patches, a.j.pos_embed, bid, a.n_pos);
+}
 }
 extern "C" int spv_set_seed_device_ptr(const void* seed_word) {
     const unsigned long long* p = static_cast<const unsigned long long*>(seed_word);
@@ -427,5 +433,54 @@ extern "C" int spv_seed_advance(void* seed_word, void* stream) {
     SPV_CHECK(seed_word != nullptr, "spv_seed_advance: null pointer");
     hipLaunchKernelGGL(seed_advance_kernel, dim3(1), dim3(1), 0, static_cast<hipStream_t>(stream), static_cast<unsigned long long*>(seed_word));
     SPV_LAUNCH_CHECK("spv_seed_advance");
+    return 0;
+}
+
+extern "C" int spv_step_prologue(const spv_prologue_jobs* jobs, void* stream) {
+    SPV_CHECK(jobs != nullptr, "spv_step_prologue: null jobs");
+    PrologueArgs a;
+    a.j = *jobs;
+    const spv_prologue_jobs& j = a.j;
+    a.n_seed = j.seed_word != nullptr ? 1 : 0;
+    // shadows: the arrays of spv_weight_shadows_multi, one workgroup per tile
+    SPV_CHECK(j.ntiles >= 0, "spv_step_prologue: ntiles = %d", j.ntiles);
+    a.n_shadow = (j.shadow_table != nullptr && j.ntiles > 0) ? j.ntiles : 0;
+    if (a.n_shadow) {
+        SPV_CHECK(j.tile_tensor && j.tile_x && j.tile_y, "spv_step_prologue: null tile lists");
+        SPV_CHECK(j.shadow_dtype == SPV_BF16 || j.shadow_dtype == SPV_F32, "spv_step_prologue: bad shadow dtype %d", j.shadow_dtype);
+    }
+    // spectral fold: spv_spectral_fold[_bf16]'s grid
+    a.n_fold = 0;
+    if (j.fold_w != nullptr && j.fold_embed > 0) {
+        SPV_CHECK(j.fold_fh && j.fold_fw && j.fold_out && j.fold_chans > 0 && j.fold_patch > 0, "spv_step_prologue: bad spectral-fold arguments");
+        a.n_fold = patch_ew_blocks((int64_t)j.fold_embed * j.fold_chans * j.fold_patch * j.fold_patch);
+    }
+    // patch rows in token layout (spv_patchify, transposed = 2): its shape checks, its choice of kernel, its grid
+    a.n_patch = a.patch_vec4 = 0;
+    if (j.patch_img != nullptr && j.patch_batch > 0) {
+        SPV_CHECK(j.patch_out && j.patch_chans > 0 && j.patch_size > 0 && j.patch_height >= j.patch_size && j.patch_width >= j.patch_size,
+                  "spv_step_prologue: bad patch shape");
+        SPV_CHECK(j.patch_dtype == SPV_F32 || j.patch_dtype == SPV_BF16, "spv_step_prologue: bad patch dtype");
+        const int Np = (j.patch_height / j.patch_size) * (j.patch_width / j.patch_size), K = j.patch_chans * j.patch_size * j.patch_size;
+        SPV_CHECK(j.patch_ld >= K, "spv_step_prologue: patch ld=%d too small", j.patch_ld);
+        if (j.patch_size % 4 == 0 && j.patch_width % 4 == 0 && j.patch_ld % 4 == 0 && ((uintptr_t)j.patch_img & 15) == 0 &&
+            ((uintptr_t)j.patch_out & 15) == 0) {
+            a.patch_vec4 = 1;
+            a.n_patch = patch_ew_blocks((int64_t)j.patch_batch * (Np + 1) * (j.patch_ld / 4));
+        } else {
+            a.n_patch = patch_ew_blocks((int64_t)j.patch_batch * (Np + 1) * j.patch_ld);
+        }
+    }
+    // position + bias rows (spv_embed_posbias)
+    a.n_pos = 0;
+    if (j.pos_pos != nullptr && j.pos_patches > 0) {
+        SPV_CHECK(j.pos_bias && j.pos_out && j.pos_embed > 0, "spv_step_prologue: bad position-row arguments");
+        a.n_pos = patch_ew_blocks((int64_t)(j.pos_patches + 1) * j.pos_embed);
+    }
+    const int64_t total = (int64_t)a.n_seed + a.n_shadow + a.n_fold + a.n_patch + a.n_pos;
+    if (total == 0) return 0;
+    SPV_CHECK(total < (1ll << 31), "spv_step_prologue: too many workgroups");
+    hipLaunchKernelGGL(step_prologue_kernel, dim3((unsigned)total), dim3(256), 0, static_cast<hipStream_t>(stream), a);
+    SPV_LAUNCH_CHECK("spv_step_prologue");
     return 0;
 }

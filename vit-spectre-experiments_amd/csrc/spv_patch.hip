@@ -3,72 +3,24 @@
 // projection matrix), dropout as a stand-alone counter-based mask.
 #define SPV_USES_SEED
 #include "spv_common.h"
+#include "spv_prologue_core.h"
 
 namespace {
 
-__device__ __forceinline__ void st_any(void* base, size_t off, int bf, float v) {
-    if (bf) static_cast<bf16_t*>(base)[off] = f2bf(v);
-    else static_cast<float*>(base)[off] = v;
-}
 __device__ __forceinline__ float ld_any(const void* base, size_t off, int bf) {
     return bf ? bf2f(static_cast<const bf16_t*>(base)[off]) : static_cast<const float*>(base)[off];
 }
 
-// out[row][k] (transposed = 0, leading dim ld >= K) or out[k][row] (transposed = 1, ld >= rows);
-// row = b * Np + ih * nW + iw,  k = c * P * P + p * P + q  (spectre.py:130-133 / Conv2d weight order)
+// the float-image patch rows: bodies in spv_prologue_core.h (shared with the step prologue)
 __global__ __launch_bounds__(256) void patchify_kernel(const float* __restrict__ img, void* __restrict__ out, int B, int C, int H,
                                                        int W, int P, int ld, int transposed, int bf) {
-    const int nH = H / P, nW = W / P, Np = nH * nW, K = C * P * P;
-    const int64_t rows = (int64_t)B * Np;
-    // transposed == 2: token rows [B][Np + 1][ld], row 0 of every image (the CLS slot) zero -- the layout the token GEMM and the TN
-    // weight-gradient GEMM both read as it lies
-    const int64_t total = transposed == 1 ? (int64_t)K * ld : (transposed == 2 ? (int64_t)B * (Np + 1) * ld : rows * ld);
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        int64_t row;
-        int k;
-        if (transposed == 1) { k = (int)(e / ld); row = e % ld; }
-        else { row = e / ld; k = (int)(e % ld); }
-        if (transposed == 2) {
-            const int64_t b2 = row / (Np + 1);
-            const int t2 = (int)(row % (Np + 1));
-            row = t2 == 0 ? rows : b2 * Np + t2 - 1;   // rows = "no such row": zero
-        }
-        float v = 0.0f;
-        if (row < rows && k < K) {
-            const int b = (int)(row / Np), n = (int)(row % Np);
-            const int ih = n / nW, iw = n % nW;
-            const int c = k / (P * P), p = (k / P) % P, q = k % P;
-            v = img[(((size_t)b * C + c) * H + ih * P + p) * W + iw * P + q];
-        }
-        st_any(out, (size_t)e, bf, v);
-    }
+    patchify_body(img, out, B, C, H, W, P, ld, transposed, bf, blockIdx.x, gridDim.x);
 }
 
-// float NCHW, patch and width multiples of 4, row-major outputs (modes 0 and 2), ld % 4 == 0: one thread per FOUR consecutive k (one
-// 16-byte pixel load, one 8/16-byte store).  The element-per-thread kernel above spends ~10 integer divisions per element: 14.4 us for
-// the 3 MB of the CIFAR batch; this form ~3 us.
 template <typename T>
 __global__ __launch_bounds__(256) void patchify_vec4_kernel(const float* __restrict__ img, T* __restrict__ out, int B, int C, int H, int W,
                                                             int P, int ld, int token_rows) {
-    const int nH = H / P, nW = W / P, Np = nH * nW, K = C * P * P;
-    const int T1 = token_rows ? Np + 1 : Np;
-    const int ld4 = ld >> 2, P4 = P >> 2;
-    const int64_t total = (int64_t)B * T1 * ld4;
-    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < total; e += (int64_t)gridDim.x * blockDim.x) {
-        const int64_t row = e / ld4;
-        const int k = (int)(e - row * ld4) * 4;
-        const int b = (int)(row / T1), t = (int)(row - (int64_t)b * T1);
-        const int n = token_rows ? t - 1 : t;
-        float v[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-        if (n >= 0 && k < K) {
-            const int ih = n / nW, iw = n - ih * nW;
-            const int c = k / (P * P), r = k - c * P * P, pr = r / P, q = r - pr * P;   // q is a multiple of 4
-            const float4 px = *reinterpret_cast<const float4*>(img + (((size_t)b * C + c) * H + ih * P + pr) * W + iw * P + q);
-            v[0] = px.x; v[1] = px.y; v[2] = px.z; v[3] = px.w;
-        }
-        (void)P4;
-        io<T>::st4(out + (size_t)row * ld + k, v);
-    }
+    patchify_vec4_body<T>(img, out, B, C, H, W, P, ld, token_rows, blockIdx.x, gridDim.x);
 }
 
 // The same patch rows straight from the loader's uint8 HWC image (spectre_vit/repl/train.py:102-112: ToTensor = /255,
@@ -104,14 +56,9 @@ __global__ __launch_bounds__(256) void patchify_u8_kernel(const unsigned char* _
     }
 }
 
-// posbias[t][e] = pos[1 + t][e] + bias[e]
-// with cls: one more row in front, out[0][e] = cls[e] + pos[0][e] -- the token GEMM over the zero CLS patch row then writes the CLS token
 __global__ __launch_bounds__(256) void posbias_kernel(const float* __restrict__ pos, const float* __restrict__ bias,
                                                       const float* __restrict__ cls, float* __restrict__ out, int Np, int E) {
-    const int lead = cls != nullptr ? E : 0;
-    const int total = Np * E + lead;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x)
-        out[i] = i < lead ? cls[i] + pos[i] : pos[E + i - lead] + bias[(i - lead) % E];
+    posbias_body(pos, bias, cls, out, Np, E, blockIdx.x, gridDim.x);
 }
 
 // tokens[b][0][e] = cls[e] + pos[0][e]
@@ -158,26 +105,10 @@ __global__ __launch_bounds__(256) void dropout_kernel(const void* __restrict__ x
                                      dropout_scale(dropout_row_key(live_seed(seed), (uint64_t)i >> 12), (unsigned)(i & 4095), p, inv_keep));
 }
 
-__device__ __forceinline__ float rcoef(int u, int v, int p, int q, int P) {
-    // Re(rfft2(norm="ortho")) kernel: cos(2 pi (u p + v q) / P) / P      (spectre.py:136)
-    return cospif(2.0f * (float)((u * p + v * q) % P) / (float)P) / (float)P;
-}
-
-// W_full[e][c,p,q] = sum_{u,v} W[e][c,u,v] fh[u] fw[v] R[(u,v),(p,q)]
 __global__ __launch_bounds__(256) void spectral_fold_kernel(const float* __restrict__ w, const float* __restrict__ fh,
                                                             const float* __restrict__ fw, float* __restrict__ wf, int E, int C, int P,
                                                             bf16_t* __restrict__ wf_bf = nullptr) {
-    const int Pv = P / 2 + 1;
-    const int total = E * C * P * P;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int q = i % P, p = (i / P) % P, c = (i / (P * P)) % C, e = i / (P * P * C);
-        const float* wr = w + ((size_t)e * C + c) * P * Pv;
-        float a = 0.0f;
-        for (int u = 0; u < P; ++u)
-            for (int v = 0; v < Pv; ++v) a = fmaf(wr[u * Pv + v] * fh[u] * fw[v], rcoef(u, v, p, q, P), a);
-        wf[i] = a;
-        if (wf_bf != nullptr) wf_bf[i] = f2bf(a);   // the GEMM operand of a bf16 step: saves the cast launch that followed
-    }
+    spectral_fold_body(w, fh, fw, wf, E, C, P, wf_bf, blockIdx.x, gridDim.x);
 }
 
 // G[e][c,u,v] = sum_{p,q} dWf[e][c,p,q] R[(u,v),(p,q)];  dW = G fh fw;  gw = G * W (for the frequency-weight sums)
@@ -229,7 +160,7 @@ __global__ __launch_bounds__(1024) void freq_weight_grad_kernel(const float* __r
     }
 }
 
-inline int ew_blocks(int64_t n) { return (int)std::min<int64_t>((n + 255) / 256, 4096); }
+inline int ew_blocks(int64_t n) { return patch_ew_blocks(n); }
 
 }  // namespace
 

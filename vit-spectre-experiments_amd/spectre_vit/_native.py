@@ -69,6 +69,8 @@ SIGNATURES = {
     "spv_small_sl_partial_floats": [c_i, c_i],
     "spv_small_sl_fwd": [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp],
     "spv_small_sl_bwd": [c_vp] * 15 + [c_i, c_i, c_i, c_i, c_vp],
+    "spv_small_sl_bwd_rows": [c_vp] * 10 + [c_i, c_i, c_i, c_i, c_vp],
+    "spv_small_sl_bwd_w": [c_vp] * 7 + [c_i, c_i, c_i, c_vp],
     "spv_cross_entropy_workspace_floats": [],
     "spv_cross_entropy_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_vp],
     "spv_cross_entropy_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_vp],
@@ -104,6 +106,7 @@ SIGNATURES = {
     "spv_colsum": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp],
     "spv_set_seed_device_ptr": [c_vp],
     "spv_seed_advance": [c_vp, c_vp],
+    "spv_step_prologue": [c_vp, c_vp],
     "spv_adamw_multi": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp],
     "spv_adamw_multi_ema": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_f, c_i, c_f, c_vp],
     "spv_grad_sumsq": [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_vp],
@@ -159,6 +162,16 @@ class AugmentCfg(ctypes.Structure):
     _fields_ = [(n, c_f) for n in ("flip_p", "bright_lo", "bright_hi", "contrast_lo", "contrast_hi", "sat_lo", "sat_hi", "hue_lo", "hue_hi",
                                    "gray_p", "degrees", "blur_p", "sigma_lo", "sigma_hi", "erase_p", "scale_lo", "scale_hi", "ratio_lo",
                                    "ratio_hi")]
+
+
+class PrologueJobs(ctypes.Structure):
+    """spv_prologue_jobs (include/spv.h): the roles of one spv_step_prologue launch; a zeroed field leaves its role out"""
+    _fields_ = ([("seed_word", c_vp), ("shadow_table", c_vp), ("tile_tensor", c_vp), ("tile_x", c_vp), ("tile_y", c_vp), ("ntiles", c_i),
+                 ("shadow_dtype", c_i), ("fold_w", c_vp), ("fold_fh", c_vp), ("fold_fw", c_vp), ("fold_out", c_vp), ("fold_out_bf16", c_vp)]
+                + [(n, c_i) for n in ("fold_embed", "fold_chans", "fold_patch", "pad0")]
+                + [("patch_img", c_vp), ("patch_out", c_vp)]
+                + [(n, c_i) for n in ("patch_batch", "patch_chans", "patch_height", "patch_width", "patch_size", "patch_ld", "patch_dtype", "pad1")]
+                + [("pos_pos", c_vp), ("pos_bias", c_vp), ("pos_cls", c_vp), ("pos_out", c_vp), ("pos_patches", c_i), ("pos_embed", c_i)])
 
 
 class TnProblem(ctypes.Structure):

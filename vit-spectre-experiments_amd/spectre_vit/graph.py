@@ -13,7 +13,7 @@ spectre_vit/repl/train.py:216-238 minus the host-side bookkeeping.  Requirements
     three on the device inside ``optimizer.step()``, which is what every step class here captures (``GraphedDPStep``: in graph B,
     behind the all-reduce, so every rank decides alike);
   * dropout: seeds are by-value kernel arguments frozen at capture, so every dropout kernel adds a 64-bit device word that this
-    class advances once per replay (``spv_seed_advance`` is the first node of the graph) -- fresh masks every step;
+    class advances once per replay (a role of ``spv_step_prologue``, the first node of the graph) -- fresh masks every step;
   * fixed shapes (one graph per batch shape).
 
 ``GraphedTrainStep`` is the single-process form: ONE graph.  ``GraphedDPStep`` is a data-parallel rank (the reference is single
@@ -98,7 +98,9 @@ class GraphedTrainStep:
 
     # -- the two halves of a step -----------------------------------------------------------------------------------------------
     def _forward_backward(self):
-        _native.call("spv_seed_advance", self.seed_word.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        # ONE launch: the seed word's advance and whatever else of the forward's opening depends on nothing but the parameters and
+        # the image buffer (hip_ops.step_prologue); the nodes concerned pick their results up instead of launching
+        hip_ops.step_prologue(self.model, self.img, self.seed_word, self.autocast_dtype)
         self.reducer.zero_grad()
         with torch.autocast("cuda", dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None):
             out = self.model(self.img)

@@ -21,7 +21,7 @@ from typing import NamedTuple
 
 import torch
 
-from . import _native, shadows
+from . import _native, prologue, shadows
 from ._launch import _DT, BF16, F32, _dt, _p, _require_gpu, _stream  # noqa: F401  (tools/ and tests read them here)
 from .shadows import invalidate_weight_shadows  # noqa: F401  (the documented name: INTEGRATION.md)
 from .timing import KernelTimer, _timing, set_kernel_timer  # noqa: F401  (bench.py reads the timer here)
@@ -135,6 +135,12 @@ _held_wgrads = []  # _HeldWgrad records
 WGRAD_BATCH = 8    # problems per launch (csrc/spv_gemm.hip TNB_MAX)
 BATCH_FOLDS = 16   # fold jobs the batch's reduce launch carries (FJ_MAX)
 _WGRAD_HOLD = True   # layer weight gradients are held for the batch launch
+# The class head's parameter gradients (dW, dgamma, dbeta, dbias: spv_small_sl_bwd_w) are read by nothing inside the backward pass
+# either, and alone their launch leaves nine tenths of the chip idle between the loss and the last layer's backward: held under the
+# same conditions, they are issued on the main stream at the end of the patch embedding's backward, where the batched layer weight
+# gradients run on the side stream (start_held_wgrads .. join_side_stream) -- or by the end-of-pass callback.
+HEAD_WGRAD_HOLD = True
+_held_head = []    # _HeldHead records
 FOLD_RIDE = True     # tail folds ride in their layer's weight-gradient reduce
 
 
@@ -175,6 +181,10 @@ _Fold = NamedTuple("_Fold", [("partials", _T), ("outs", tuple), ("parts", int), 
 # A layer weight gradient dw[n, k] = dh[rows, n]^T . x[rows, k] held for the batch launch at the end of the backward pass: dw is the
 # address of its sink slot, fold the _Fold that rides in its reduce (or None)
 _HeldWgrad = NamedTuple("_HeldWgrad", [("dh", _T), ("x", _T), ("dw", int), ("rows", int), ("n", int), ("k", int), ("fold", object)])
+
+
+# dh, xs, partials: what the launch reads (held until it is issued); outs: the addresses of the four sink slots (dW, dgamma, dbeta, dbias)
+_HeldHead = NamedTuple("_HeldHead", [("dh", _T), ("xs", _T), ("partials", _T), ("outs", tuple), ("rows", int), ("n", int), ("k", int)])
 
 
 def _addrs(tensors):
@@ -278,6 +288,7 @@ def _begin_pass(task):
     if _held_task != task:
         _held_folds.clear()   # leftovers of a backward pass that never finished (an exception): their launch must not ride along
         _held_wgrads.clear()
+        _held_head.clear()
         _engine.queue_callback(flush_held_folds)
         _held_task = task
 
@@ -294,6 +305,32 @@ def _hold_wgrad(dh, x, dw, sink, rows, n, k, fold, fold_sunk):
     return True
 
 
+def _hold_head_wgrad(dh, xs, partials, outs, sinks, rows, n, k):
+    """hold the class head's weights launch for the end of the embedding's backward (see HEAD_WGRAD_HOLD).  False: not held."""
+    if not (HEAD_WGRAD_HOLD and _hold_ok() and _sunk(outs, sinks)):
+        return False
+    task = _graph_task_id()
+    if task < 0:
+        return False
+    _begin_pass(task)
+    _held_head.append(_HeldHead(dh, xs, partials, _addrs(outs), rows, n, k))
+    return True
+
+
+def flush_held_head(end_of_pass=False):
+    """issue the held class-head weights launches of this backward pass on the current stream.  The record kept the tensors they read
+    alive until here; they were allocated on this stream and are read on it, so the allocator's stream order covers them from here on
+    (no entry in _side_keep: that list is for what a SIDE-stream kernel touches).  (Records of another pass -- one that never
+    finished -- are dropped; the end-of-pass callback only ever sees its own pass's.)"""
+    if not _held_head:
+        return
+    if end_of_pass or _held_task == _graph_task_id():
+        for h in _held_head:
+            _native.call("spv_small_sl_bwd_w", _p(h.dh), _p(h.xs), _p(h.partials), *h.outs, h.rows, h.n, h.k, _stream())
+            PATH_COUNTS["head_wgrad_held"] += 1
+    _held_head.clear()
+
+
 def _in_sink(dw, sink):
     """dw is the parameter's sink slot or a row range of it (memory that outlives the node: it may be written at the end of the pass)"""
     if sink is None:
@@ -306,6 +343,7 @@ def flush_held_folds():
     """run the weight gradients and folds still held (called by the autograd engine when the backward pass is over)"""
     global _held_task
     _flush_held_wgrads()
+    flush_held_head(True)   # (no embedding node in this pass, or one that issued nothing)
     if _held_folds:
         arr = _fold_array(_held_folds)
         _native.call("spv_fold_multi", ctypes.addressof(arr), len(_held_folds), _stream())
@@ -741,6 +779,13 @@ class SpectralFoldFn(torch.autograd.Function):
     def forward(ctx, proj_w, fh, fw, chans, patch):
         _require_gpu(proj_w)
         E = proj_w.shape[0]
+        ready = prologue.take("fold", (proj_w, fh, fw), (chans, patch)) if torch.is_autocast_enabled("cuda") else None
+        if ready is not None:   # the step prologue's launch has folded these very tensors already
+            wf, wf._spv_bf16 = ready
+            ctx.save_for_backward(proj_w, fh, fw)
+            ctx.sinks = (_sink(proj_w), _sink(fh), _sink(fw))
+            ctx.meta = (E, chans, patch)
+            return wf
         wf = torch.empty((E, chans * patch * patch), dtype=torch.float32, device=proj_w.device)
         if torch.is_autocast_enabled("cuda"):   # a bf16 step: the token GEMM's operand comes out of the same launch (PatchEmbedFn picks it up)
             wb = torch.empty(wf.shape, dtype=torch.bfloat16, device=proj_w.device)
@@ -801,16 +846,22 @@ class PatchEmbedFn(torch.autograd.Function):
         st = _stream()
         # token rows [B][T][K], the CLS slot of every image zero: the GEMM below then writes cls + pos[0] there by itself (its row bias
         # holds that sum in row 0), and the backward's TN weight-gradient GEMM reads the same matrix against dtok as both lie in memory
-        patches = torch.empty((B * T, K), dtype=dtype, device=dev)
-        if u8:
+        patches = None if u8 else prologue.take("patchify", (img,), (patch, dtype))   # made by the step prologue's launch?
+        if patches is not None:
+            pass
+        elif u8:
+            patches = torch.empty((B * T, K), dtype=dtype, device=dev)
             _native.call("spv_patchify_u8", _p(img), _p(norm[0]), _p(norm[1]), _p(patches), B, C, H, W, patch, K, 2, _DT[dtype], st)
         else:
+            patches = torch.empty((B * T, K), dtype=dtype, device=dev)
             _native.call("spv_patchify", _p(img), _p(patches), B, C, H, W, patch, K, 2, _DT[dtype], st)
         wc = w_full if dtype == torch.float32 else (getattr(w_full, "_spv_bf16", None) if dtype == torch.bfloat16 else None)
         if wc is None:
             wc = _raw_cast(w_full, dtype)
-        posbias = torch.empty((T, E), dtype=torch.float32, device=dev)
-        _native.call("spv_embed_posbias", _p(pos), _p(bias), _p(cls), _p(posbias), Np, E, st)
+        posbias = prologue.take("posbias", (pos, bias, cls), (Np, E))
+        if posbias is None:
+            posbias = torch.empty((T, E), dtype=torch.float32, device=dev)
+            _native.call("spv_embed_posbias", _p(pos), _p(bias), _p(cls), _p(posbias), Np, E, st)
         tokens = torch.empty((B, T, E), dtype=dtype, device=dev)
         seed = _new_seed() if p_drop > 0.0 else 0
         # the dropout rides in the GEMM's epilogue (the mask spv_dropout would draw from the same seed; the backward re-derives it)
@@ -850,6 +901,7 @@ class PatchEmbedFn(torch.autograd.Function):
             # dW = dtok^T . P over all B*T token rows, with P the patch matrix widened by a zero row per image (the CLS
             # row): the TN kernel then takes dtok as it lies in memory -- no transposed copies of a 34 MB tensor
             dwf = _weight_grad(dtok.view(B * T, E), patches, B * T, E, K)
+            flush_held_head()   # the class head's parameter gradients: beside the batch, at the end of this node's chain
             if not early:   # (with a batch in flight the end-of-pass callback joins: the spectral fold's backward overlaps it too)
                 join_side_stream()
             return None, dwf, dbias, dcls, dpos_full, None, None, None, None
@@ -1061,6 +1113,76 @@ class ClsAddFn(torch.autograd.Function):
 
 
 # ------------------------------------------------------------------------------------------------
+# the step prologue: the small launches that open a graph-replayed training step, as one (csrc/spv_misc.hip: step_prologue_kernel)
+# ------------------------------------------------------------------------------------------------
+# The seed word's advance, the layer weights' bf16 copies, the spectral embedding's folded projection, the patch rows and the
+# position/bias rows are mutually independent and all needed only in front of the token GEMM, yet as five dependent graph nodes each
+# paid its own launch and drain.  False: the step issues spv_seed_advance and every node launches for itself, as an eager forward does.
+STEP_PROLOGUE = True
+
+
+def step_prologue(model, img, seed_word, autocast_dtype):
+    """ONE launch in front of a graph-replayed step's forward (spectre_vit.graph): the seed word, plus every role whose inputs `model`
+    has.  The outputs wait in spectre_vit.prologue for the nodes that would have launched them; a node that finds none launches as
+    always, so a role left out here (baseline ViT, SpectreBranch, uint8 images, fp32 steps, a model without the spectral embedding)
+    costs nothing but its old launch.  The registry is emptied first: nothing of an earlier step can be served."""
+    prologue.clear()
+    if not STEP_PROLOGUE:
+        _native.call("spv_seed_advance", _p(seed_word), _stream())
+        return
+    jobs = _native.PrologueJobs()
+    jobs.seed_word = _p(seed_word)
+    work = 16.0
+    deposits = []
+    emb = getattr(model, "embeddings_block", None)
+    if autocast_dtype == torch.bfloat16 and torch.is_grad_enabled() and img.is_cuda:
+        weights_fn = getattr(model, "_shadow_weights", None)
+        weights = weights_fn() if callable(weights_fn) else None
+        ss = shadows.shadow_set(model, weights) if weights else None
+        if ss is not None and ss.dtype == torch.bfloat16:
+            table, tt, tx, ty, ntiles = ss._tables
+            jobs.shadow_table, jobs.tile_tensor, jobs.tile_x, jobs.tile_y = _p(table), _p(tt), _p(tx), _p(ty)
+            jobs.ntiles, jobs.shadow_dtype = ntiles, BF16
+            work += 2048.0 * ntiles * 8
+            deposits.append(("shadows", weights, (ss.dtype,), ss))
+        # the embedding module itself names what its forward will hand SpectralFoldFn and PatchEmbedFn (SpectralPatchEmbed
+        # ._prologue_sources); a module without that method launches for itself
+        sources_fn = getattr(emb, "_prologue_sources", None)
+        sources = sources_fn(img) if callable(sources_fn) and img.dtype == torch.float32 and img.is_contiguous() else None
+        if sources is not None:
+            (w, fh, fw, C, P), (bias, cls, pos) = sources
+            B, _, H, W = img.shape
+            dev = img.device
+            E, K = w.shape[0], C * P * P
+            Np = (H // P) * (W // P)
+            fp32 = all(t.dtype == torch.float32 and t.is_contiguous() and t.is_cuda for t in (w, fh, fw, pos, bias, cls))
+            if fp32 and P > 0 and H >= P and W >= P and w.dim() == 2 and w.shape[1] == C * P * (P // 2 + 1) and pos.numel() == (Np + 1) * E:
+                wf = torch.empty((E, K), dtype=torch.float32, device=dev)
+                wb = torch.empty((E, K), dtype=torch.bfloat16, device=dev)
+                jobs.fold_w, jobs.fold_fh, jobs.fold_fw, jobs.fold_out, jobs.fold_out_bf16 = _p(w), _p(fh), _p(fw), _p(wf), _p(wb)
+                jobs.fold_embed, jobs.fold_chans, jobs.fold_patch = E, C, P
+                work += 4.0 * w.numel() + 6.0 * E * K
+                deposits.append(("fold", (w, fh, fw), (C, P), (wf, wb)))
+                patches = torch.empty((B * (Np + 1), K), dtype=torch.bfloat16, device=dev)
+                jobs.patch_img, jobs.patch_out = _p(img), _p(patches)
+                jobs.patch_batch, jobs.patch_chans, jobs.patch_height, jobs.patch_width = B, C, H, W
+                jobs.patch_size, jobs.patch_ld, jobs.patch_dtype = P, K, BF16
+                work += 4.0 * img.numel() + 2.0 * patches.numel()
+                deposits.append(("patchify", (img,), (P, torch.bfloat16), patches))
+                posbias = torch.empty((Np + 1, E), dtype=torch.float32, device=dev)
+                jobs.pos_pos, jobs.pos_bias, jobs.pos_cls, jobs.pos_out = _p(pos), _p(bias), _p(cls), _p(posbias)
+                jobs.pos_patches, jobs.pos_embed = Np, E
+                work += 8.0 * (Np + 1) * E
+                deposits.append(("posbias", (pos, bias, cls), (Np, E), posbias))
+    if _timing():
+        _native.hint = int(work)
+    _native.call("spv_step_prologue", ctypes.addressof(jobs), _stream())
+    PATH_COUNTS["step_prologue"] += 1
+    for role, sources, extra, value in deposits:
+        prologue.deposit(role, sources, extra, value)
+
+
+# ------------------------------------------------------------------------------------------------
 # the classifier end of the step: class head over the CLS rows + mean cross-entropy (csrc/spv_head.hip)
 # ------------------------------------------------------------------------------------------------
 def small_head_ok(rows: int, n: int, k: int) -> bool:
@@ -1115,8 +1237,10 @@ class ClsHeadFn(torch.autograd.Function):
         dgamma = _grad_buf(s_g, (n,), dev)
         dbeta = _grad_buf(s_be, (n,), dev)
         partials = torch.empty((_native.call("spv_small_sl_partial_floats", B, n),), dtype=torch.float32, device=dev)
-        _native.call("spv_small_sl_bwd", _p(dlogits), _p(h), _p(xs), _p(mean), _p(rstd), _p(weight), _p(gamma), _p(beta), _p(dh), _p(dx),
-                     _p(dw), _p(dgamma), _p(dbeta), _p(dbias), _p(partials), B, n, E, _DT[dtype], _stream())
+        _native.call("spv_small_sl_bwd_rows", _p(dlogits), _p(h), _p(mean), _p(rstd), _p(weight), _p(gamma), _p(beta), _p(dh), _p(dx),
+                     _p(partials), B, n, E, _DT[dtype], _stream())
+        if not _hold_head_wgrad(dh, xs, partials, (dw, dgamma, dbeta, dbias), (s_w, s_g, s_be, s_b), B, n, E):
+            _native.call("spv_small_sl_bwd_w", _p(dh), _p(xs), _p(partials), _p(dw), _p(dgamma), _p(dbeta), _p(dbias), B, n, E, _stream())
         if dfeats is not None:
             dx = dx + dfeats.to(dx.dtype)
         return _cls_row_gradient(shape, dtype, dev, dx), dx, dw, dbias, dgamma, dbeta  # the stack's gradient is dense: zero off the CLS row

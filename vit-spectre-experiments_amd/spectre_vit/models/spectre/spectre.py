@@ -193,6 +193,14 @@ class SpectralPatchEmbed(nn.Module):
         return hip_ops.patch_embed(x, w_full, self.proj.bias, self.cls_token, self.position_embeddings, self.P, self.pixel_norm,
                                    self.dropout.p if self.training else 0.0)   # the nn.Dropout of spectre.py:156, inside the same node
 
+    def _prologue_sources(self, x):
+        """what forward(x) hands SpectralFoldFn and patch_embed, for hip_ops.step_prologue (which launches their small kernels ahead
+        of the forward): (proj_w, fh, fw, chans, patch) and (bias, cls, pos).  None: a batch the prologue does not serve (uint8)."""
+        if x.dtype == torch.uint8 or x.dim() != 4:
+            return None
+        return ((self.proj.weight, self.freq_weight_h, self.freq_weight_w, x.shape[1], self.P),
+                (self.proj.bias, self.cls_token, self.position_embeddings))
+
 
 class SpectreViT(nn.Module):
     """reference spectre.py:159-202."""

@@ -10,7 +10,7 @@ import weakref
 
 import torch
 
-from . import _native
+from . import _native, prologue
 from ._launch import _DT, _p, _stream
 
 
@@ -112,6 +112,10 @@ class ShadowSet:
 
     def refresh(self):
         _refresh_multi(self._tables, self.dtype)
+        self.mark_fresh()
+
+    def mark_fresh(self):
+        """the copies were just rebuilt (by refresh, or by the step prologue's launch): hand them to this forward's layers"""
         for wr, (wc, wt) in zip(self.weights, self.bufs):
             w = wr()
             if w is not None:
@@ -163,19 +167,31 @@ def pinned_shadows(p):
         _pinned = prev
 
 
-def refresh_weight_shadows(module, weights_fn):
-    """called at the top of a model's bf16 training forward: module._spv_shadow_set is (re)built when a weight moved or changed shape"""
-    weights = weights_fn()
-    if not weights:
-        return
+def shadow_set(module, weights):
+    """module._spv_shadow_set, (re)built when a weight moved or changed shape; None where it cannot be built (inside a capture)"""
     ss = getattr(module, "_spv_shadow_set", None)
     key = tuple((w.data_ptr(), tuple(w.shape)) for w in weights)
     if ss is None or ss.key != key:
         if torch.cuda.is_current_stream_capturing():
-            return  # (tables cannot be uploaded inside a capture: the per-weight path serves this forward)
+            return None  # (tables cannot be uploaded inside a capture: the per-weight path serves this forward)
         ss = ShadowSet(weights)
         object.__setattr__(module, "_spv_shadow_set", ss)
-    ss.refresh()
+    return ss
+
+
+def refresh_weight_shadows(module, weights_fn):
+    """called at the top of a model's bf16 training forward: one launch rebuilds every copy of module._spv_shadow_set -- unless the
+    step prologue has just done so for exactly these weights (spectre_vit.prologue), in which case nothing is launched"""
+    weights = weights_fn()
+    if not weights:
+        return
+    ss = shadow_set(module, weights)
+    if ss is None:
+        return
+    if prologue.take("shadows", weights, (ss.dtype,)) is ss:
+        ss.mark_fresh()
+    else:
+        ss.refresh()
 
 
 def invalidate_weight_shadows(*_args, **_kwargs):

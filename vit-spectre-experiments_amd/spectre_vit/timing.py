@@ -21,6 +21,9 @@ def _es(dt):
 _WORK_MODELS = {
     "spv_small_sl_fwd": lambda i: ("head_fwd", i[2:5], i[5], "mfma", 2.0 * i[2] * i[3] * i[4]),
     "spv_small_sl_bwd": lambda i: ("head_bwd", i[0:3], i[3], "mfma", 4.0 * i[0] * i[1] * i[2]),
+    # the two halves of head_bwd on their own: dx = dh W (rows); dW = dh^T x (weights)
+    "spv_small_sl_bwd_rows": lambda i: ("head_bwd_rows", i[0:3], i[3], "mfma", 2.0 * i[0] * i[1] * i[2]),
+    "spv_small_sl_bwd_w": lambda i: ("head_bwd_w", i[0:3], F32, "mfma", 2.0 * i[0] * i[1] * i[2]),
     "spv_cross_entropy_fwd": lambda i: ("cross_entropy_fwd", i[0:2], F32, "hbm", i[0] * i[1] * 4.0),
     "spv_cross_entropy_bwd": lambda i: ("cross_entropy_bwd", i[0:2], F32, "hbm", i[0] * i[1] * 8.0),
     # student + teacher logits read (forward), read + the gradient written (backward)
@@ -93,6 +96,8 @@ _WORK_MODELS = {
     "spv_grad_sumsq": lambda i: ("grad_sumsq", i[0:1], F32, "hbm", 4.0 * 2048 * i[0]),
     "spv_step_control": lambda i: ("step_control", i[0:2], F32, "hbm", 8.0 * i[0] + 64),
     "spv_adamw_multi_ctl": lambda i: ("adamw_multi_ctl", i[0:1], F32, "hbm", 7.0 * 4 * 2048 * i[0]),
+    # one launch for the step's small opening jobs: the sum of its roles' compulsory bytes, handed over as the caller's hint
+    "spv_step_prologue": lambda i: ("step_prologue", (), BF16, "hbm", float(i[-1])),
     "spv_weight_shadows": lambda i: ("weight_shadows", i[0:2], i[3], "hbm", i[0] * i[1] * (4.0 + 2 * _es(i[3]))),
     "spv_dropout": lambda i: ("dropout", i[0:1], i[1], "hbm", 2.0 * i[0] * _es(i[1])),
     "spv_axpby": lambda i: ("axpby", i[0:1], i[1], "hbm", 3.0 * i[0] * _es(i[1])),
