@@ -171,7 +171,12 @@ int spv_spectre_tail_fwd(const void* h, const void* x, const float* gamma, const
  * transposed pooling of the masked dout, to which the caller accumulates dh.W), and the fp32
  * column sums dgamma/dbeta/dbias [n].  `partials` is fp32 scratch of spv_rowop_partial_floats(n)
  * floats.  `dx_add` (nullable, [rows,k_in], dtype): a residual-stream gradient folded into dx_pool
- * (x1 feeds both norm2's residual and linear1, spectre.py:67,70-73), instead of a separate add pass. */
+ * (x1 feeds both norm2's residual and linear1, spectre.py:67,70-73), instead of a separate add pass.
+ * dx_pool == NULL (the skip gradient is not formed; dx_add is then ignored) is accepted where a kernel honours it: n = 512 (any
+ * k_in), n = 3072 from k_in = 768 with h, dout, dh, gamma, beta and partials 16-byte aligned, and k_in a proper multiple of n
+ * (exact windows); spv_spectre_tail_bwd_up and spv_spectre_tail_ln_bwd accept it as well.  Every other shape is refused on the host.
+ * Rows with n % 4 != 0 (n <= 1024) are served by scalar kernels; their forward stages x in LDS 16 bytes at a time only when both
+ * k_in and 2 n are multiples of 4 (the stage starts 2 n floats into LDS), one float at a time otherwise. */
 int spv_spectre_tail_bwd(const void* dout, const void* h, const float* mean, const float* rstd,
                          const float* gamma, const float* beta, void* dh, void* dx_pool, float* dgamma,
                          float* dbeta, float* dbias, float* partials, int rows, int n, int k_in, int dtype,

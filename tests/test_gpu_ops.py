@@ -396,7 +396,9 @@ def test_spectre_linear_small_p_dropout_statistics(ops, n, k):
 # ------------------------------------------------------------------------------------------------ add + LayerNorm
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
 @pytest.mark.parametrize("mode", [0, 1])
-@pytest.mark.parametrize("rows,n", [(130, 512), (7, 48), (33, 768), (5, 100), (9, 3072), (6, 1000)])
+@pytest.mark.parametrize("rows,n", [(130, 512), (7, 48), (33, 768), (5, 100), (9, 3072), (6, 1000),
+                                    (9, 1024),        # the backward's fast kernel <4>
+                                    (4101, 512)])     # above the backward's grid cap (1024 workgroups x 4 rows): a second sweep, ragged
 def test_add_layernorm(ops, dtype, mode, rows, n):
     rng = np.random.default_rng(rows + n + mode)
     a, b = q(rng.standard_normal((rows, n)), dtype), q(rng.standard_normal((rows, n)), dtype)

@@ -158,7 +158,8 @@ __global__ __launch_bounds__(RT, (MAXI <= 4 ? 4 : (MAXI <= 12 ? 2 : 1))) void ta
         }
         if (pool_mode == POOL_TABLE) {
             lds_fence();  // previous row's pooled reads are done before the stage is overwritten
-            if ((k_in & 3) == 0) {
+            // 16-byte LDS stores only where xs = lds + 2n + wave * k_in is 16-byte aligned (VEC = 1 rows of odd length put it at 8)
+            if ((k_in & 3) == 0 && ((2 * n) & 3) == 0) {
                 for (int j = lane * 4; j < k_in; j += 256) {
                     float t4[4];
                     ldv<4>(x, (size_t)row * k_in + j, bf, t4);
@@ -1488,6 +1489,9 @@ static int tail_bwd_impl(const void* dout, const void* h, const float* mean, con
         return 0;
     }
     const int pm = pool_mode_of(n, k_in);
+    // only the exact-window branch of the generic kernel skips the skip gradient; the others store through dx_pool
+    SPV_CHECK(dx_pool != nullptr || pm == POOL_EXACT,
+              "spv_spectre_tail_bwd: dx_pool == NULL is not served for n=%d k_in=%d (accepted: n = 512, 768 -> 3072 on 16-byte aligned pointers, k_in a multiple of n)", n, k_in);
     const int wgs = std::min(cdiv(rows, RW), BWD_MAX_WG);
     const size_t lds = (size_t)3 * n * sizeof(float) + (pm == POOL_TABLE ? (size_t)(2 * k_in + n + RW * n) * sizeof(int) : 0);
     SPV_CHECK(lds <= 64 * 1024, "spv_spectre_tail_bwd: n=%d k_in=%d needs %zu bytes of LDS", n, k_in, lds);
