@@ -271,9 +271,14 @@ int spv_permut_row0_bwd(const void* dg0, const void* dx0, const uint32_t* idx, v
  * spectre.py:31).  The operator is symmetric, so the same call is its own backward.
  * `twiddle`: token-axis cos/sin table of spv_fnet_twiddle_floats(tokens) floats filled once by
  * spv_fnet_make_twiddle (the caller caches it).  `workspace`: fp32 scratch of
- * spv_fnet_workspace_floats(batch,tokens,dim) floats (0 on the LDS fast path: dim a power of two,
+ * spv_fnet_workspace_floats(batch,tokens,dim) floats (0 on the LDS fast path: dim a power of two in 8..4096,
  * tokens <= 79 and (tokens+3)*dim*4 <= 160 KiB).  `add_in` (nullable, same shape/dtype as y) is added to the
- * output: in the backward, the residual-stream gradient that bypasses the mixer (spectre.py:66). */
+ * output: in the backward, the residual-stream gradient that bypasses the mixer (spectre.py:66).
+ * Alignment: the LDS fast path and the bf16 dim-512 MFMA path (2 <= tokens <= 65) move 16 bytes per access, so x, y and add_in
+ * must be 16-byte aligned there; a misaligned pointer is refused on the host.  The two-stage generic path (every shape with a
+ * non-zero spv_fnet_workspace_floats) takes any alignment of the element type.  The same holds for x / prenorm / out and
+ * dout / prenorm / dx of spv_fnet_ln_*, and for x / out of spv_fnet_cls_fwd and dx of spv_fnet_cls_bwd (16-byte row accesses);
+ * gamma and beta are read four floats at a time and must come from 16-byte aligned allocations as well. */
 int spv_fnet_mix(const void* x, void* y, const void* add_in, const float* twiddle, int batch, int tokens, int dim,
                  int dtype, float* workspace, void* stream);
 int64_t spv_fnet_workspace_floats(int batch, int tokens, int dim);

@@ -933,6 +933,11 @@ extern "C" int spv_fnet_make_twiddle(float* tw, int tokens, void* stream) {
     return 0;
 }
 
+// the LDS, MFMA and row-0 kernels move 16 bytes per access: their tensors must sit on 16-byte boundaries (the generic path takes any)
+static bool aligned16(const void* a, const void* b = nullptr, const void* c = nullptr, const void* d = nullptr) {
+    return (((uintptr_t)a | (uintptr_t)b | (uintptr_t)c | (uintptr_t)d) & 15) == 0;
+}
+
 static bool fnet_fast_ok(int tokens, int dim) {
     if (dim < 8 || (dim & (dim - 1)) || dim > 4096) return false;
     if (tokens / 2 + 1 > 2 * FNET_MH) return false;
@@ -953,6 +958,7 @@ extern "C" int spv_fnet_mix(const void* x, void* y, const void* add_in, const fl
     const int bf = dtype == SPV_BF16;
     if (bf && dim == V2D && tokens >= 2 && tokens <= 65) {
         SPV_CHECK(twiddle != nullptr, "spv_fnet_mix: twiddle table required");
+        SPV_CHECK(aligned16(x, y, add_in), "spv_fnet_mix: x, y and add_in must be 16-byte aligned for tokens=%d dim=%d", tokens, dim);
         const int v2_stagger = batch >= 512 ? 1 : 0;  // x 8128 cycles (~3.5 us)
         const int rows = std::max(2 * ((tokens + 1) / 2), 2 * (tokens / 2 + 1));
         const size_t lds = (size_t)rows * V2RS;
@@ -966,6 +972,7 @@ extern "C" int spv_fnet_mix(const void* x, void* y, const void* add_in, const fl
     }
     if (fnet_fast_ok(tokens, dim)) {
         SPV_CHECK(twiddle != nullptr, "spv_fnet_mix: twiddle table required");
+        SPV_CHECK(aligned16(x, y, add_in), "spv_fnet_mix: x, y and add_in must be 16-byte aligned for tokens=%d dim=%d", tokens, dim);
         const size_t lds = ((size_t)(tokens + 1) * dim + 2 * (size_t)dim) * 4;
         FftPlan plan = make_fft_plan(dim);
         int log2tpf = 0;
@@ -1057,7 +1064,8 @@ extern "C" int spv_fnet_ln_fwd(const void* x, void* prenorm, void* out, const fl
                                const float* twiddle, int batch, int tokens, int dim, int dtype, void* stream) {
     SPV_CHECK(batch > 0 && spv_fnet_ln_supported(tokens, dim, dtype), "spv_fnet_ln_fwd: unsupported shape %d x %d x %d / dtype %d", batch,
               tokens, dim, dtype);
-    SPV_CHECK(twiddle && gamma && beta && mean && rstd && prenorm, "spv_fnet_ln_fwd: null pointer");
+    SPV_CHECK(x && out && twiddle && gamma && beta && mean && rstd && prenorm, "spv_fnet_ln_fwd: null pointer");
+    SPV_CHECK(aligned16(x, prenorm, out), "spv_fnet_ln_fwd: x, prenorm and out must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     FnetLn ln{gamma, beta, mean, rstd, static_cast<const bf16_t*>(x), static_cast<bf16_t*>(prenorm), nullptr, nullptr};
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fnet_mfma_kernel<1>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1074,7 +1082,8 @@ extern "C" int spv_fnet_ln_bwd(const void* dout, const void* prenorm, const floa
                                int dtype, void* stream) {
     SPV_CHECK(batch > 0 && spv_fnet_ln_supported(tokens, dim, dtype), "spv_fnet_ln_bwd: unsupported shape %d x %d x %d / dtype %d", batch,
               tokens, dim, dtype);
-    SPV_CHECK(twiddle && gamma && mean && rstd && prenorm && partials && ((dgamma != nullptr) == (dbeta != nullptr)), "spv_fnet_ln_bwd: null pointer");
+    SPV_CHECK(dout && dx && twiddle && gamma && mean && rstd && prenorm && partials && ((dgamma != nullptr) == (dbeta != nullptr)), "spv_fnet_ln_bwd: null pointer");
+    SPV_CHECK(aligned16(dout, prenorm, dx), "spv_fnet_ln_bwd: dout, prenorm and dx must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
     FnetLn ln{gamma, nullptr, const_cast<float*>(mean), const_cast<float*>(rstd), nullptr, nullptr, static_cast<const bf16_t*>(prenorm), partials};
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&fnet_mfma_kernel<2>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
@@ -1260,6 +1269,8 @@ extern "C" int spv_fnet_cls_fwd(const void* x, const float* gamma, const float* 
                                 int tokens, int dim, int dtype, void* stream) {
     SPV_CHECK(spv_fnet_cls_supported(tokens, dim, dtype), "spv_fnet_cls_fwd: unsupported tokens=%d dim=%d dtype=%d", tokens, dim, dtype);
     SPV_CHECK(batch > 0, "spv_fnet_cls_fwd: empty batch");
+    SPV_CHECK(x && gamma && beta && out && m0 && mean && rstd, "spv_fnet_cls_fwd: null pointer");
+    SPV_CHECK(aligned16(x, out), "spv_fnet_cls_fwd: x and out must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define SPV_CLS_F(TT, DD) hipLaunchKernelGGL((fnet_cls_fwd_kernel<TT, DD>), dim3(batch), dim3(DD / 2), 0, st, (const TT*)x, gamma, beta, (TT*)out, m0, mean, rstd, tokens)
     if (dtype == SPV_BF16) { if (dim == 256) SPV_CLS_F(bf16_t, 256); else if (dim == 512) SPV_CLS_F(bf16_t, 512); else SPV_CLS_F(bf16_t, 1024); }
@@ -1273,6 +1284,8 @@ extern "C" int spv_fnet_cls_bwd(const void* g1, const float* m0, const float* me
                                 float* partials, int batch, int tokens, int dim, int dtype, void* stream) {
     SPV_CHECK(spv_fnet_cls_supported(tokens, dim, dtype), "spv_fnet_cls_bwd: unsupported tokens=%d dim=%d dtype=%d", tokens, dim, dtype);
     SPV_CHECK(batch > 0, "spv_fnet_cls_bwd: empty batch");
+    SPV_CHECK(g1 && m0 && mean && rstd && gamma && dx && partials, "spv_fnet_cls_bwd: null pointer");
+    SPV_CHECK(aligned16(dx), "spv_fnet_cls_bwd: dx must be 16-byte aligned");
     hipStream_t st = static_cast<hipStream_t>(stream);
 #define SPV_CLS_B(TT, DD) hipLaunchKernelGGL((fnet_cls_bwd_kernel<TT, DD>), dim3(batch), dim3(DD / 2), 0, st, (const TT*)g1, m0, mean, rstd, gamma, (TT*)dx, partials, tokens)
     if (dtype == SPV_BF16) { if (dim == 256) SPV_CLS_B(bf16_t, 256); else if (dim == 512) SPV_CLS_B(bf16_t, 512); else SPV_CLS_B(bf16_t, 1024); }
