@@ -775,6 +775,55 @@ int spv_distill_loss_idx_meter_fwd(const float* student, const float* cache, con
                                    float* out3, float* workspace, int rows, int n_cache, int classes, float T, float w_soft, float w_ce,
                                    void* meter, int k, void* stream);
 
+/* ---- the resident loader: DataLoader(shuffle=True) of spectre_vit/repl/train.py:147-155, 216-218 on the device -- ONE launch reads
+ * the step from a device cursor, writes that step's shuffled batch to fixed addresses and advances the cursor, so a captured launch
+ * fetches a new batch at every replay and the host feeds a graph-replayed step nothing.  DESIGN.md section 4i.
+ *
+ * The order (csrc/spv_loader_core.h, host/device; restated in tests/loader_ref.py).  All arithmetic below is on unsigned words.
+ *   mix64(x): x ^= x >> 33; x *= 0xff51afd7ed558ccd; x ^= x >> 33; x *= 0xc4ceb9fe1a85ec53; x ^= x >> 33   (64-bit, murmur3's finaliser)
+ *   mix32(x): x ^= x >> 16; x *= 0x7feb352d; x ^= x >> 15; x *= 0x846ca68b; x ^= x >> 16                    (32-bit, the dropout masks')
+ *   key(seed, epoch) = mix64(mix64(seed + G) + epoch),  G = 0x9e3779b97f4a7c15
+ *   perm_epoch, a bijection of [0, n), 1 <= n < 2^31: a balanced Feistel network on 2 h bits, h the smallest integer >= 1 with
+ *   2^(2h) >= n, of SPV_LOADER_ROUNDS = 6 rounds with round keys k_r = the low 32 bits of mix64(key + (r + 1) G), r = 0..5:
+ *       (L, R) = (x >> h, x & (2^h - 1));  six times (L, R) := (R, L ^ (mix32(R + k_r) & (2^h - 1)));  x := (L << h) | R
+ *   re-applied while x >= n (cycle-walking; 2^(2h) < 4 n, fewer than four passes on average).  shuffle == 0: the identity.
+ *   The position rule -- idx[rank::world] cut into batches of `batch`, the tail dropped, the harness's own sharding -- with the step t
+ *   taken as the cursor's 64 bits UNSIGNED:  sample r of step t is row  perm_epoch[((t mod S) * batch + r) * world + rank],
+ *   epoch = t div S, S = steps_per_epoch with S * batch * world <= n (so S <= (n div world) div batch).  Whatever 64 bits the cursor
+ *   holds, every position is < S * batch * world <= n and every row is < n: no source address is formed outside the set.
+ *
+ * cursor: a block of SPV_LOADER_CURSOR_BYTES (64) bytes, 8-byte aligned, zeroed by the caller: word 0 (64-bit) = the step t, the low
+ * half of word 1 = the launch's arrival counter, the rest reserved.  Every workgroup reads t and then adds one to the counter; the
+ * last to arrive -- every workgroup holds its copy of t by then -- stores t + 1 and re-arms the counter (the scheme of
+ * spv_cross_entropy_fwd's join).  A host that writes the cursor (resume) writes t and zeroes the counter, never under capture.
+ *
+ * One call writes index[r] = the row (int64 [batch]), labels[r] = labels_src[row] (int64 [batch]; labels_src uint8 or int64 [n], by
+ * label_dtype) and the images, from the resident set src_nhwc (uint8 [n][height][width][chans], the layout spv_augment_u8 reads):
+ *   SPV_LOADER_FLOAT  img fp32 [batch][chans][height][width] = (x / 255 - mean[c]) * inv_std[c], three fp32 operations, inv_std as the
+ *                     caller rounded it (spectre_vit.augment.TrainAugment.norm: 1 / std in float64, rounded once);
+ *   SPV_LOADER_UINT8  img uint8 [batch][height][width][chans], the rows copied unchanged (spv_patchify_u8 normalises);
+ *   SPV_LOADER_NONE   index and labels only (src_nhwc, img, mean, inv_std unused): the caller hands `index` to spv_augment_u8 or
+ *                     spv_distill_loss_idx_fwd.
+ * chans 1 or 3, height and width 1..512, any batch: the grid is (image, span of 1024 pixels -- uint8: of 4096 bytes), no whole image
+ * in LDS, so 224 x 224 runs like 32 x 32.  Float mode stages a span's bytes in LDS and writes planar rows.  Access width: 16-byte
+ * global loads and stores when height * width * chans % 16 == 0, src_nhwc and img are 16-byte aligned and (float mode) height * width
+ * % 4 == 0 -- every image, span and plane then starts on a 16-byte boundary; single bytes in and single floats / bytes out otherwise
+ * (3 x 5 x 7; a view of the set that starts 4 bytes into its allocation).
+ * Refused on the host, before any launch: a null labels_src / cursor / index / labels, a null src_nhwc / img in an image mode, mode
+ * float without mean / inv_std, a cursor not 8-byte aligned, n < 1, batch < 1, world < 1 or rank outside [0, world), S < 1 or
+ * S * batch * world > n, chans / height / width outside the above, an unknown mode or label dtype, batch * spans >= 2^31. */
+#define SPV_LOADER_ROUNDS 6
+#define SPV_LOADER_CURSOR_BYTES 64
+#define SPV_LOADER_NONE 0
+#define SPV_LOADER_FLOAT 1
+#define SPV_LOADER_UINT8 2
+#define SPV_LOADER_LABEL_U8 0
+#define SPV_LOADER_LABEL_I64 1
+int64_t spv_loader_cursor_bytes(void);
+int spv_loader_fetch(const unsigned char* src_nhwc, const void* labels_src, void* cursor, int64_t* index, int64_t* labels, void* img,
+                     const float* mean, const float* inv_std, int n, int batch, int chans, int height, int width, int world, int rank,
+                     int steps_per_epoch, uint64_t seed, int shuffle, int mode, int label_dtype, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

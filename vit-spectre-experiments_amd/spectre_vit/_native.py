@@ -144,12 +144,15 @@ SIGNATURES = {
     "spv_distill_loss_meter_workspace_floats": [],
     "spv_distill_loss_meter_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_f, c_f, c_f, c_vp, c_i, c_vp],
     "spv_distill_loss_idx_meter_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_f, c_f, c_f, c_vp, c_i, c_vp],
+    "spv_loader_cursor_bytes": [],
+    "spv_loader_fetch": [c_vp] * 8 + [c_i] * 8 + [c_u64, c_i, c_i, c_i, c_vp],
 }
 _RESTYPES = {"spv_last_error": ctypes.c_char_p, "spv_path_count": ctypes.c_longlong, "spv_rowop_partial_floats": c_i64, "spv_fnet_workspace_floats": c_i64,
              "spv_fnet_twiddle_floats": c_i64, "spv_tail_ln_partial_floats": c_i64, "spv_permut_table_words": c_i64, "spv_small_sl_partial_floats": c_i64,
              "spv_cross_entropy_workspace_floats": c_i64, "spv_distill_loss_workspace_floats": c_i64,
              "spv_eval_head_stats_words": c_i64, "spv_augment_tiled_ws_bytes": ctypes.c_size_t, "spv_train_meter_words": c_i64,
-             "spv_cross_entropy_meter_workspace_floats": c_i64, "spv_distill_loss_meter_workspace_floats": c_i64}
+             "spv_cross_entropy_meter_workspace_floats": c_i64, "spv_distill_loss_meter_workspace_floats": c_i64,
+             "spv_loader_cursor_bytes": c_i64}
 _NO_STATUS = set(_RESTYPES) | {"spv_version", "spv_fnet_ln_supported", "spv_fnet_cls_supported", "spv_tail_ln_supported", "spv_tail_up_supported", "spv_small_sl_supported", "spv_tail_bwd_parts", "spv_embed_bwd_groups", "spv_haar_ln_supported", "spv_permut_pool_supported", "spv_spectrum_floats", "spv_augment_supported", "spv_augment_plan", "spv_teacher_view_supported"}
 
 class FoldJob(ctypes.Structure):

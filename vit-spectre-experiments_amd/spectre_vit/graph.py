@@ -16,6 +16,15 @@ spectre_vit/repl/train.py:216-238 minus the host-side bookkeeping.  Requirements
     class advances once per replay (a role of ``spv_step_prologue``, the first node of the graph) -- fresh masks every step;
   * fixed shapes (one graph per batch shape).
 
+``loader=`` (a ``spectre_vit.data.ResidentLoader`` with an image output) puts the batch inside the graph as well: the step's image and
+label buffers ARE the loader's, ``loader.fetch()`` is the graph's first node -- in front of ``hip_ops.step_prologue``, whose patch-row
+role reads the image buffer -- and a step is one replay with no host-issued work in front of it:
+
+    step = GraphedTrainStep(model, optimizer, criterion, None, None, loader=loader)
+    loss = step()                   # step.img / step.labels: the batch that replay trained on
+
+The warm-up steps are real steps and each consumes one loader step; the capture consumes none (a recorded launch does not run).
+
 ``GraphedTrainStep`` is the single-process form: ONE graph.  ``GraphedDPStep`` is a data-parallel rank (the reference is single
 device, train.py:41; SURVEY 8e makes the gradient exchange new work):
 
@@ -67,8 +76,14 @@ class GraphedTrainStep:
     _dp = False
 
     def __init__(self, model, optimizer, criterion, example_img, example_labels, autocast_dtype=torch.bfloat16, warmup=3,
-                 return_features=False, process_group=None, force_collective=False):
-        if not example_img.is_cuda:
+                 return_features=False, process_group=None, force_collective=False, loader=None):
+        if loader is not None:
+            if loader.img is None:
+                raise ValueError(f"{type(self).__name__}(loader=...): the loader has no image output (output='none'); fetch eagerly, "
+                                 "build the images from loader.index and feed the step instead")
+            if example_img is not None or example_labels is not None:
+                raise ValueError(f"{type(self).__name__}(loader=...): the batch comes from the loader, pass example_img = example_labels = None")
+        elif not example_img.is_cuda:
             raise RuntimeError(f"{type(self).__name__} needs the example batch on the GPU")
         for g in optimizer.param_groups:
             if not g.get("capturable", False):
@@ -76,8 +91,12 @@ class GraphedTrainStep:
         self._closed = True   # until the seed word is claimed
         self.model, self.optimizer, self.criterion = model, optimizer, criterion
         self.autocast_dtype = autocast_dtype
-        self.img = example_img.clone()
-        self.labels = example_labels.clone()
+        self.loader = loader
+        if loader is None:
+            self.img = example_img.clone()
+            self.labels = example_labels.clone()
+        else:   # the loader's fixed-address buffers are the step's
+            self.img, self.labels = loader.img, loader.labels
         dev = self.img.device
         self.force_collective = bool(force_collective)
         # fixed gradient addresses (the graphs replay into them; the optimizer's pointer table is built once, before the capture).
@@ -98,6 +117,8 @@ class GraphedTrainStep:
 
     # -- the two halves of a step -----------------------------------------------------------------------------------------------
     def _forward_backward(self):
+        if self.loader is not None:
+            self.loader.fetch()   # the first node: this step's batch into self.img / self.labels, the device cursor moved on
         # ONE launch: the seed word's advance and whatever else of the forward's opening depends on nothing but the parameters and
         # the image buffer (hip_ops.step_prologue); the nodes concerned pick their results up instead of launching
         hip_ops.step_prologue(self.model, self.img, self.seed_word, self.autocast_dtype)
@@ -150,12 +171,16 @@ class GraphedTrainStep:
     def __call__(self, img=None, labels=None):
         if self._closed:
             raise RuntimeError("this graph-replayed step was closed")
+        if self.loader is not None and (img is not None or labels is not None):
+            raise ValueError("this step fetches its own batch (loader=...): call it without arguments")
         if img is not None:
             self.img.copy_(img, non_blocking=True)
         if labels is not None:
             self.labels.copy_(labels, non_blocking=True)
         self._replay()
         self.replays += 1
+        if self.loader is not None:
+            self.loader.count_replay()
         # the replay updated the weights through raw pointers: neither the parameters' version counters nor the optimizer's post-step
         # hook saw it, so the inference-time cache of bf16 weight copies (shadows._ShadowCache) must be told
         shadows.invalidate_weight_shadows()

@@ -51,6 +51,12 @@ def augment_seed(seed: int, rank: int = 0) -> int:
     return (int(seed) & 0xFFFFFFFF) | ((int(rank) & 0xFFFFFFFF) << 32)
 
 
+def loader_seed(seed: int) -> int:
+    """the resident loader's 64-bit seed: the config seed's low word, as augment_seed(seed, 0).  NOT a function of the rank: the ranks
+    take disjoint parts (idx[rank::world]) of ONE permutation, so they must draw the same one; the rank enters through the position"""
+    return augment_seed(seed, 0)
+
+
 def build_model(c, mixer="permut", device="cuda", model="spectre"):
     """train.py:48-59; model="spectre_branch" builds reference spectre_branch.py's SpectreBranch from the same config fields"""
     if model == "spectre_branch":
@@ -146,6 +152,15 @@ def _check_device_meter(device_meter, distill=False):
                          "path (train_distill has)")
 
 
+def _check_device_loader(device_loader, distill=False):
+    """raises before any device is touched"""
+    if not isinstance(device_loader, bool):
+        raise ValueError(f"device_loader={device_loader!r} must be True or False")
+    if device_loader and distill:
+        raise ValueError("device_loader=True fetches the batches of the plain training step: the early distill=True form is not built "
+                         "for it")
+
+
 def _eager_validate(model, batches, criterion, amp, batch_hook, world, device, float_logits=False):
     """one eager validation pass: every sample of the rank's shard, the loss sample-weighted (the tail batch is short), the sums kept on
     the device and read once.  -> (accuracy, loss, samples)"""
@@ -196,7 +211,7 @@ def _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, uint8):
 def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
           use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
           augment=False, batch_hook=None, graph_eval=False, lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None,
-          skip_nonfinite=False, ema_decay=None, ema_warmup=False, device_meter=False):
+          skip_nonfinite=False, ema_decay=None, ema_warmup=False, device_meter=False, device_loader=False):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
@@ -223,8 +238,18 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     epoch, so its loss launch -- eager or replayed -- counts the batch's hits and logs the step on the device: the host issues no
     argmax / == / sum / accumulate per step, reads the meter ONCE per epoch and resets it.  "Loss/Train" and "Accuracy/Train" (rank
     local, as without it) come from the meter, the record gains "Accuracy/TrainTop5", and scalars.jsonl gains one
-    {"step", "Batch Loss/Train"} line per step (the reference's loss.item(), train.py:243).  Validation keeps a meter-less criterion."""
+    {"step", "Batch Loss/Train"} line per step (the reference's loss.item(), train.py:243).  Validation keeps a meter-less criterion.
+    device_loader=True (not with distill): the training batches come from a spectre_vit.data.ResidentLoader over the resident uint8 set
+    -- the epoch's permutation is computed on the device, one launch fetches a step's batch into fixed buffers -- instead of the host's
+    randperm, slices, gathers and normalisation; with or without uint8_input.  Its steps per epoch are this loop's (min(per_pass,
+    steps_per_epoch)), its seed loader_seed(config seed), its shard this rank's.  With graph=True the fetch is the first node of the
+    step's graph, so a step is one replay and nothing else; with augment=True the loader fetches index and labels only and
+    TrainAugment takes loader.index (draw and apply stay host-issued in front of the step: their step number is a by-value argument).
+    The host then no longer knows a batch beforehand: batch_hook("train", step, img, label) is called AFTER the step, with the step's
+    buffers (the loader's, or the augmented batch) -- valid until the next step overwrites them.  Validation is untouched.  The sample
+    ORDER differs from the host randperm's (same distribution, another stream): hence a flag and not the default."""
     _check_device_meter(device_meter, distill)
+    _check_device_loader(device_loader, distill)
     if augment and (uint8_input or distill):
         raise ValueError("augment=True yields normalised float batches for the plain training step: not with uint8_input or distill")
     ema = _ema_args(ema_decay, ema_warmup)
@@ -278,12 +303,27 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     gen = torch.Generator().manual_seed(seed)
     best_acc, best_ema_acc, history = 0.0, 0.0, []
     global_step = 0
-    aug = train_nhwc = None
+    aug = train_nhwc = loader = None
+    if augment or device_loader:
+        train_nhwc = train_set.images.permute(0, 2, 3, 1).contiguous()
     if augment:
         aug = TrainAugment(CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels], seed=augment_seed(seed, rank))
-        train_nhwc = train_set.images.permute(0, 2, 3, 1).contiguous()
+    if device_loader:
+        from spectre_vit.data import ResidentLoader
+        loader = ResidentLoader(train_nhwc, train_set.labels, batch_size, CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels],
+                                seed=loader_seed(seed), rank=rank, world=world, steps_per_epoch=min(per_pass, steps_per_epoch or per_pass),
+                                output="none" if augment else ("uint8" if uint8_input else "float"))
+    loader_in_graph = loader is not None and graph and aug is None   # the step fetches its own batch
 
     def train_batches():
+        if loader is not None:
+            for _ in range(loader.steps_per_epoch):
+                if loader_in_graph:
+                    yield None, None
+                    continue
+                loader.fetch()
+                yield loader.img if aug is None else aug(train_nhwc, loader.index, step=global_step), loader.labels
+            return
         if aug is None:
             yield from train_set.batches(batch_size, True, gen, rank, world, raw_uint8=uint8_input and not distill)
             return
@@ -298,22 +338,31 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         total, steps = 0, 0
         first_step = global_step
         for img, label in train_batches():
-            if batch_hook is not None:
+            if batch_hook is not None and loader is None:
                 batch_hook("train", global_step, img, label)
             global_step += 1
             if graph:
                 if gstep is None:   # built on the first batch (its shape is the captured one); warm-up steps are real training steps
                     from spectre_vit.graph import GraphedDPStep, GraphedTrainStep
                     cls = GraphedDPStep if world > 1 else GraphedTrainStep
-                    gstep = cls(model, optimizer, criterion, img, label.long(), autocast_dtype=torch.bfloat16 if use_amp else None, warmup=1)
+                    fed = dict(loader=loader) if loader_in_graph else {}
+                    gstep = cls(model, optimizer, criterion, img, None if loader_in_graph else label.long(),
+                                autocast_dtype=torch.bfloat16 if use_amp else None, warmup=1, **fed)
                     loss, y_pred = gstep.warm_loss, gstep.warm_out   # the warm-up step WAS this batch's training step
+                elif loader_in_graph:
+                    loss = gstep()   # ONE replay: fetch, forward, loss, backward, optimizer
+                    y_pred = gstep.out
                 else:
                     loss = gstep(img, label.long())
                     y_pred = gstep.out
+                if loader_in_graph:
+                    img, label = loader.img, loader.labels   # what the step just trained on
                 if meter is None:
                     correct += (label == torch.argmax(y_pred, dim=1)).sum()
                     total += label.size(0)
                     running += loss.detach()
+                if batch_hook is not None and loader is not None:
+                    batch_hook("train", global_step - 1, img, label)
                 steps += 1
                 if steps_per_epoch and steps >= steps_per_epoch:
                     break
@@ -338,6 +387,8 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
             optimizer.step()
             if meter is None:
                 running += loss.detach()  # accumulated on device: no host sync per step (train.py:243 syncs every step)
+            if batch_hook is not None and loader is not None:
+                batch_hook("train", global_step - 1, img, label)
             steps += 1
             if steps_per_epoch and steps >= steps_per_epoch:
                 break
@@ -655,6 +706,9 @@ def build_parser():
     ap.add_argument("--device-meter", action="store_true",
                     help="keep the training loss / accuracy books on the device inside the loss launch (spectre_vit.meter.TrainMeter): "
                          "no host-issued argmax / == / sum / accumulate per step, one read per epoch, per-step loss lines")
+    ap.add_argument("--device-loader", action="store_true",
+                    help="fetch the shuffled training batches on the GPU (spectre_vit.data.ResidentLoader): with --graph a step is one "
+                         "replay with no host-issued work in front of it; the sample order differs from the host randperm's")
     ap.add_argument("--out", default="runs/spectre_vit")
     return ap
 
@@ -669,7 +723,8 @@ def main(argv=None):
                       device_meter=a.device_meter, **control)
         return
     train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph,
-          model=a.model, augment=a.augment, graph_eval=a.graph_eval, device_meter=a.device_meter, **control)
+          model=a.model, augment=a.augment, graph_eval=a.graph_eval, device_meter=a.device_meter, device_loader=a.device_loader,
+          **control)
 
 
 if __name__ == "__main__":

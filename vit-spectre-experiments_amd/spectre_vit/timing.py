@@ -102,6 +102,10 @@ _WORK_MODELS = {
     "spv_dropout": lambda i: ("dropout", i[0:1], i[1], "hbm", 2.0 * i[0] * _es(i[1])),
     "spv_axpby": lambda i: ("axpby", i[0:1], i[1], "hbm", 3.0 * i[0] * _es(i[1])),
     "spv_colsum": lambda i: ("colsum", i[0:2], i[2], "hbm", 1.0 * i[0] * i[1] * _es(i[2])),
+    # (n, batch, chans, height, width, world, rank, steps, shuffle, mode, label dtype): index and labels written, the labels read, and
+    # the image read as uint8 and written as fp32 (mode 1) or uint8 (mode 2)
+    "spv_loader_fetch": lambda i: ("loader_fetch", i[1:5], F32, "hbm",
+                                   i[1] * (16.0 + (8 if i[10] else 1) + i[2] * i[3] * i[4] * {0: 0, 1: 5, 2: 2}.get(i[9], 0))),
     "spv_cast": lambda i: ("cast", i[2:3], i[1], "hbm", 1.0 * i[2] * (_es(i[0]) + _es(i[1]))),
 }
 
