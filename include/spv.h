@@ -247,19 +247,34 @@ int spv_add_layernorm_bwd(const void* dout, const void* a, const void* b, const 
  * of scatter lists (backward and forward): per (head, quarter of the output row) the sources whose target lies in that quarter, in
  * ascending order. */
 int64_t spv_permut_table_words(int heads, int d);
-/* 1 when spv_permut_gather_fwd emits `pooled` for this window on rows longer than the LDS (any window that divides d and a quarter of it) */
+/* 1 when spv_permut_gather_fwd emits `pooled` for this window on rows longer than the LDS: bf16, d % 8 == 0, heads <= 65 535, and a
+ * window that divides d and a quarter of it.  A SHAPE-ONLY answer: the forward refuses what it cannot tell (x or g off 16-byte
+ * alignment, batch > 65 535) rather than return with `pooled` unwritten.  Rows that fit the LDS pool by the rule below. */
 int spv_permut_pool_supported(int heads, int d, int pool_window, int dtype);
 int spv_permut_pack(const int64_t* perms, const float* signs, uint32_t* idx, int heads, int d, void* stream);
 /* pooled (nullable, [batch, heads*d / pool_window]): the average of every pool_window consecutive gathered elements
- * (what the SpectreLinear skip needs), produced on the fly so the tail kernel does not re-read g. */
+ * (what the SpectreLinear skip needs), produced on the fly so the tail kernel does not re-read g.  A call that is given `pooled`
+ * writes all of it or fails:
+ *   - a row that fits the LDS (d * elsize <= 150 KiB) in whole 16-byte pieces: window 4, 8, 16 or 32 that divides heads * d, with
+ *     (heads * d / 4) % 1024 == 0; anything else is refused ("needs the LDS path" / "unsupported pool window");
+ *   - a longer bf16 row: what spv_permut_pool_supported answers;
+ *   - x, g and idx 16-byte aligned, else refused.
+ * Without `pooled` every shape and every alignment of the element type is served: the kernels that move 16-byte pieces (csrc/
+ * spv_permut_core.h names the kernel of every call) need x, g and idx 16-byte aligned; a call that does not meet that runs the
+ * element-wide global kernel, which is several times slower. */
 int spv_permut_gather_fwd(const void* x, const uint32_t* idx, void* g, void* pooled, int pool_window, int batch,
                           int heads, int d, int dtype, void* stream);
+/* Every shape and every alignment of the element type is served; the fast kernels need dg, dx and idx 16-byte aligned (the long-row
+ * scatter reads dg one element at a time and needs only dx), otherwise the element-wide global kernel runs. */
 int spv_permut_gather_bwd(const void* dg, const uint32_t* idx, void* dx, int batch, int heads, int d,
                           int dtype, void* stream);
 /* Token row 0 of the gathered matrix only (the last layer of a stack whose consumer reads the CLS row): g0[b][c] = +-x[b][idx[c]]
  * for the first n = heads * embed entries of the forward table (reference layers.py:71-72: row t of the raw view is the chunk
  * [t n, (t + 1) n) of the flattened (heads, d) gather), x0[b] = the sample's own row 0.  Backward: dx[b] = dx0[b] in row 0, zero
- * elsewhere, + the n scattered values.  idx: the table of spv_permut_pack (its forward part comes first). */
+ * elsewhere, + the n scattered values.  idx: the table of spv_permut_pack (its forward part comes first).
+ * 0 < n <= d and 0 < embed <= d, else refused (n < embed is fine: all of x0 is written); the backward also refuses d or embed that
+ * is not a multiple of 8.  The LDS kernels need x and x0 (dx and dx0) 16-byte aligned, a row of at most 150 KiB and, forward, d and
+ * embed multiples of the 16-byte vector; otherwise element-wide kernels in global memory serve the call. */
 int spv_permut_row0_fwd(const void* x, const uint32_t* idx, void* g0, void* x0, int batch, int d, int n, int embed, int dtype,
                         void* stream);
 int spv_permut_row0_bwd(const void* dg0, const void* dx0, const uint32_t* idx, void* dx, int batch, int d, int n, int embed,

@@ -16,14 +16,13 @@
 // the forward kernel additionally serves TWO samples per workgroup from one pass over the table (their rows interleaved in LDS
 // as bf16 pairs, so one 4-byte LDS read fetches both), which halves the table traffic again.
 #include "spv_common.h"
+#include "spv_permut_core.h"   // the table geometry and the dispatch rules (host only)
 
 namespace {
 
-constexpr int PT = 1024;         // threads per workgroup
-constexpr int LDS_LIMIT = 150 * 1024;
+constexpr int PT = PERMUT_PT;    // threads per workgroup
+constexpr int LDS_LIMIT = PERMUT_LDS_LIMIT;
 
-// compact tables exist iff every index fits 16 bits and head slices start on a sign-byte boundary
-inline bool compact_ok(int d) { return d <= 65536 && d % 8 == 0; }
 struct Compact {
     const uint16_t *fwd16, *inv16;
     const uint8_t *fwd_sg, *inv_sg;
@@ -112,7 +111,9 @@ __global__ __launch_bounds__(PT) void gather_fwd_lds_kernel(const T* __restrict_
             const int gl = pw >> 2;  // lanes per window: 1, 2, 4 or 8 (host checks)
             if (gl >= 2) sm += dpp_mov<0xB1>(sm);   // quad_perm [1,0,3,2]
             if (gl >= 4) sm += dpp_mov<0x4E>(sm);   // quad_perm [2,3,0,1]
-            if (gl >= 8) sm += dpp_mov<0x124>(sm);  // row_ror:4 -> lanes 0-3 also hold lanes 4-7's sum
+            // row_ror:12: lane i reads lane (i + 4) mod 16, so lanes 0-3 add lanes 4-7's sum and lanes 8-11 lanes 12-15's
+            // (row_ror:4 reads lane (i - 4) mod 16: the window's writer would add the NEIGHBOUR window's upper half)
+            if (gl >= 8) sm += dpp_mov<0x12C>(sm);
             if ((q & (gl - 1)) == 0) io<T>::st(pooled + (size_t)b * (total / pw) + q / gl, sm * (1.0f / (float)pw));
         }
     }
@@ -137,63 +138,16 @@ __global__ __launch_bounds__(256) void gather_fwd_global_kernel(const T* __restr
     }
 }
 
-// Rows that do not fit the LDS (Spectre-ViT-Base at 224 / 16: d = 197 x 768 = 151 296 bf16 = 296 KB) in PARTS that do: a workgroup owns
-// PARTS_CH gathered elements, keeps their table entries in registers, and for each part of the sample's row -- staged in LDS
-// by coalesced 16-byte loads -- picks up the elements whose source lies in it.  The row is read from L2 once per workgroup instead of
-// being hit by one random two-byte global load per element (gather_fwd_global_kernel: 592 us per Base layer at bs 64, 12 of the
-// student step's 30 ms together with the backward below).  grid = (chunks of PARTS_CH elements, batch).
+// A bf16 row too long for the compact backward (40 960 < d <= 76 800) still fits the LDS whole: a workgroup owns PARTS_CH inputs,
+// keeps their table entries in registers, and for each head stages that head's gradient row in LDS by coalesced 16-byte loads.
 constexpr int PARTS_T = 512;     // threads: 2 waves per SIMD, so that 64 table entries + values per thread stay in registers
 constexpr int PARTS_G = 8;       // groups of 8 CONSECUTIVE elements per thread (two 16-byte table loads, one 16-byte store per group)
 constexpr int PARTS_CH = PARTS_T * PARTS_G * 8;   // elements per workgroup: 32 768
 typedef unsigned gp_u32x4 __attribute__((ext_vector_type(4)));
-constexpr int PARTS_GF = 8;      // the forward: 8 groups per thread too (12 and 16 spill: 48 / 168 VGPRs)
-constexpr int PARTS_CHF = PARTS_T * PARTS_GF * 8;
-__global__ __launch_bounds__(PARTS_T) void gather_fwd_parts_kernel(const uint16_t* __restrict__ x, const uint32_t* __restrict__ idx,
-                                                                   uint16_t* __restrict__ g, int heads, int d, int part) {
-    extern __shared__ __attribute__((aligned(16))) unsigned char gp_smem[];
-    const uint16_t* row = reinterpret_cast<const uint16_t*>(gp_smem);
-    const int b = blockIdx.y;
-    const int total = heads * d;   // < 2^31 (host), a multiple of 8
-    const int f0 = blockIdx.x * PARTS_CHF + threadIdx.x * 8;   // group gi starts at f0 + gi * PARTS_T * 8
-    const uint16_t* xr = x + (size_t)b * d;
-    gp_u32x4 id[PARTS_GF][2], out[PARTS_GF];
-#pragma unroll
-    for (int gi = 0; gi < PARTS_GF; ++gi) {
-        const int f = f0 + gi * PARTS_T * 8;
-        const bool in = f < total;
-        id[gi][0] = in ? *reinterpret_cast<const gp_u32x4*>(idx + f) : gp_u32x4{~0u, ~0u, ~0u, ~0u};   // (an index that lies in no part)
-        id[gi][1] = in ? *reinterpret_cast<const gp_u32x4*>(idx + f + 4) : gp_u32x4{~0u, ~0u, ~0u, ~0u};
-        out[gi] = gp_u32x4{0u, 0u, 0u, 0u};
-    }
-    for (int base = 0; base < d; base += part) {
-        const int len = min(part, d - base);   // multiples of 8 (host)
-        for (int p = threadIdx.x * 8; p < len; p += PARTS_T * 8)
-            *reinterpret_cast<gp_u32x4*>(gp_smem + (size_t)p * 2) = *reinterpret_cast<const gp_u32x4*>(xr + base + p);
-        __syncthreads();
-#pragma unroll
-        for (int gi = 0; gi < PARTS_GF; ++gi)
-#pragma unroll
-            for (int e = 0; e < 8; ++e) {
-                const uint32_t w = id[gi][e >> 2][e & 3];
-                const uint32_t pos = (w & 0x7fffffffu) - (uint32_t)base;
-                if (pos < (uint32_t)len) {
-                    const uint32_t v = (uint32_t)row[pos] ^ ((w >> 31) << 15);
-                    out[gi][e >> 1] |= v << (16 * (e & 1));
-                }
-            }
-        __syncthreads();
-    }
-    uint16_t* go = g + (size_t)b * total;
-#pragma unroll
-    for (int gi = 0; gi < PARTS_GF; ++gi) {
-        const int f = f0 + gi * PARTS_T * 8;
-        if (f < total) *reinterpret_cast<gp_u32x4*>(go + f) = out[gi];
-    }
-}
 // backward: dx[b][i] = sum_h +-dg[b][h][inv_h(i)], heads in ascending order in fp32 (the order of gather_bwd_global_kernel): a workgroup
-// owns PARTS_CH inputs and walks (head, part of that head's gradient row).  grid = (chunks of inputs, batch).
+// owns PARTS_CH inputs and walks the heads.  grid = (chunks of inputs, batch), LDS = d bf16.
 __global__ __launch_bounds__(PARTS_T) void gather_bwd_parts_kernel(const bf16_t* __restrict__ dg, const uint32_t* __restrict__ inv,
-                                                                   bf16_t* __restrict__ dx, int heads, int d, int part) {
+                                                                   bf16_t* __restrict__ dx, int heads, int d) {
     extern __shared__ __attribute__((aligned(16))) unsigned char gpb_smem[];
     const bf16_t* row = reinterpret_cast<const bf16_t*>(gpb_smem);
     const int b = blockIdx.y;
@@ -213,24 +167,21 @@ __global__ __launch_bounds__(PARTS_T) void gather_bwd_parts_kernel(const bf16_t*
             id[gi][1] = in ? *reinterpret_cast<const gp_u32x4*>(inv + (size_t)h * d + i + 4) : gp_u32x4{~0u, ~0u, ~0u, ~0u};
         }
         const bf16_t* src = dg + ((size_t)b * heads + h) * d;
-        for (int base = 0; base < d; base += part) {
-            const int len = min(part, d - base);
-            for (int p = threadIdx.x * 8; p < len; p += PARTS_T * 8)
-                *reinterpret_cast<gp_u32x4*>(gpb_smem + (size_t)p * 2) = *reinterpret_cast<const gp_u32x4*>(src + base + p);
-            __syncthreads();
+        for (int p = threadIdx.x * 8; p < d; p += PARTS_T * 8)   // d is a multiple of 8 (host)
+            *reinterpret_cast<gp_u32x4*>(gpb_smem + (size_t)p * 2) = *reinterpret_cast<const gp_u32x4*>(src + p);
+        __syncthreads();
 #pragma unroll
-            for (int gi = 0; gi < PARTS_G; ++gi)
+        for (int gi = 0; gi < PARTS_G; ++gi)
 #pragma unroll
-                for (int e = 0; e < 8; ++e) {
-                    const uint32_t w = id[gi][e >> 2][e & 3];
-                    const uint32_t pos = (w & 0x7fffffffu) - (uint32_t)base;
-                    if (pos < (uint32_t)len) {
-                        const float v = bf2f(row[pos]);
-                        acc[gi][e] += (w >> 31) ? -v : v;
-                    }
+            for (int e = 0; e < 8; ++e) {
+                const uint32_t w = id[gi][e >> 2][e & 3];
+                const uint32_t pos = w & 0x7fffffffu;
+                if (pos < (uint32_t)d) {   // (an index that lies in no row: the lanes past d)
+                    const float v = bf2f(row[pos]);
+                    acc[gi][e] += (w >> 31) ? -v : v;
                 }
-            __syncthreads();
-        }
+            }
+        __syncthreads();
     }
 #pragma unroll
     for (int gi = 0; gi < PARTS_G; ++gi) {
@@ -251,14 +202,7 @@ __global__ __launch_bounds__(PARTS_T) void gather_bwd_parts_kernel(const bf16_t*
 // Table tail (uint32 words behind the wide + compact tables), two sets -- [0] from the forward table for this backward, [1] from the
 // inverse table for the forward below --, each: off [heads][nparts + 1], cur [heads][nparts] (pack-time cursors),
 // ej [heads][d] = source | sign << 31, et [heads][d] uint16 = target - part * L.
-inline bool long_row(int d) { return (size_t)d * 2 > (size_t)LDS_LIMIT; }
-inline int scat_parts(int d) { return (int)(((size_t)d * 4 + LDS_LIMIT - 1) / LDS_LIMIT); }
-inline int scat_len(int d) { const int n = scat_parts(d); return (((d + n - 1) / n) + 7) / 8 * 8; }
-inline int64_t scat_set_words(int heads, int d) {   // one list set
-    const int64_t total = (int64_t)heads * d;
-    return (int64_t)heads * (scat_parts(d) + 1) + (int64_t)heads * scat_parts(d) + total + (total + 1) / 2;
-}
-inline int64_t scat_words(int heads, int d) { return 2 * scat_set_words(heads, d); }   // [0] the backward's (from the forward table), [1] the forward's
+// (long_row, scat_parts, scat_len, scat_set_words, scat_words: spv_permut_core.h)
 struct ScatTail {
     int* off;
     int* cur;
@@ -412,15 +356,9 @@ __global__ __launch_bounds__(1024) void gather_fwd_scatter_kernel(const uint16_t
     }
 }
 
-// part length for a row of d elements: the fewest equal parts that fit the LDS, a multiple of 8 elements
-inline int parts_len(int d) {
-    const int cap = LDS_LIMIT / 2;
-    const int n = (d + cap - 1) / cap;
-    return (((d + n - 1) / n) + 7) / 8 * 8;
-}
-
-// backward, LDS path: grid = batch; thread owns elements i = (it*PT + tid)*4 .. +3, it < MAX_IT
-constexpr int MAX_IT = 10;  // d <= 4 * PT * MAX_IT = 40 960
+// backward, LDS path (fp32: every bf16 row this shape rule admits has compact tables): grid = batch; thread owns elements
+// i = (it*PT + tid)*4 .. +3, it < MAX_IT
+constexpr int MAX_IT = PERMUT_MAX_IT;  // d <= 4 * PT * MAX_IT = 40 960
 template <typename T>
 __global__ __launch_bounds__(PT) void gather_bwd_lds_kernel(const T* __restrict__ dg, const uint32_t* __restrict__ inv,
                                                             T* __restrict__ dx, int heads, int d) {
@@ -583,7 +521,7 @@ __global__ __launch_bounds__(PT) void gather_fwd_pair_kernel(const uint16_t* __r
 }
 
 // backward, compact table (bf16): grid = batch; thread owns elements i = (it*PT + tid)*8 .. +7, it < C_IT
-constexpr int C_IT = 5;  // d <= 8 * PT * C_IT = 40 960
+constexpr int C_IT = PERMUT_C_IT;  // d <= 8 * PT * C_IT = 40 960
 __global__ __launch_bounds__(PT) void gather_bwd_c16_kernel(const bf16_t* __restrict__ dg, const uint16_t* __restrict__ inv16,
                                                             const uint8_t* __restrict__ sg8, bf16_t* __restrict__ dx, int heads, int d) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -759,42 +697,35 @@ extern "C" int spv_permut_pack(const int64_t* perms, const float* signs, uint32_
     return 0;
 }
 
-/* 1 when spv_permut_gather_fwd can emit the pooled skip for this window on the long-row (scatter) path */
-extern "C" int spv_permut_pool_supported(int heads, int d, int pool_window, int dtype) {
-    (void)heads;
-    return (dtype == SPV_BF16 && long_row(d) && d % 8 == 0 && pool_window > 0 && d % pool_window == 0 && scat_len(d) % pool_window == 0) ? 1 : 0;
-}
+/* 1 when spv_permut_gather_fwd can emit the pooled skip for this window on the long-row (scatter) path: a shape-only answer */
+extern "C" int spv_permut_pool_supported(int heads, int d, int pool_window, int dtype) { return permut_pool_supported(heads, d, pool_window, dtype); }
 
-extern "C" int64_t spv_permut_table_words(int heads, int d) {
-    const int64_t total = (int64_t)heads * d;
-    return 2 * total + (compact_ok(d) ? total + (total / 4 + 3) / 4 : 0) + (long_row(d) ? scat_words(heads, d) : 0);
-}
+extern "C" int64_t spv_permut_table_words(int heads, int d) { return permut_table_words(heads, d); }
+
+static inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 extern "C" int spv_permut_gather_fwd(const void* x, const uint32_t* idx, void* g, void* pooled, int pool_window, int batch,
                                      int heads, int d, int dtype, void* stream) {
-    SPV_CHECK(batch > 0 && heads > 0 && d > 0, "spv_permut_gather_fwd: empty");
-    SPV_CHECK(dtype == SPV_F32 || dtype == SPV_BF16, "spv_permut_gather_fwd: bad dtype %d", dtype);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    const size_t es = dtype == SPV_BF16 ? 2 : 4;
-    const bool aligned = ((size_t)d * es) % 16 == 0 && ((int64_t)heads * d) % 4 == 0;
-    const bool scat_pool = pooled != nullptr && dtype == SPV_BF16 && long_row(d) && pool_window > 0 && d % pool_window == 0 &&
-                           scat_len(d) % pool_window == 0;   // the scatter path emits any window that divides its quarters
-    if (pooled != nullptr && !scat_pool) {
-        const int64_t total = (int64_t)heads * d;
-        SPV_CHECK(aligned && (size_t)d * es <= (size_t)LDS_LIMIT, "spv_permut_gather_fwd: pooled output needs the LDS path");
-        SPV_CHECK((pool_window == 4 || pool_window == 8 || pool_window == 16 || pool_window == 32) && total % pool_window == 0 &&
-                      (total / 4) % PT == 0,
-                  "spv_permut_gather_fwd: unsupported pool window %d", pool_window);
-    }
     const int64_t total_e = (int64_t)heads * d;
-    if (dtype == SPV_BF16 && compact_ok(d) && (size_t)d * 4 <= (size_t)LDS_LIMIT &&
-        (pooled == nullptr || ((pool_window == 8 || pool_window == 16 || pool_window == 32) && (total_e / 8) % PT == 0))) {
+    const size_t es = dtype == SPV_BF16 ? 2 : 4;
+    switch (permut_fwd_path(dtype, heads, d, batch, pooled != nullptr, pool_window, al16(x), al16(g), al16(idx))) {
+    case PERMUT_REFUSE_EMPTY: return spv_set_error("spv_permut_gather_fwd: empty");
+    case PERMUT_REFUSE_DTYPE: return spv_set_error("spv_permut_gather_fwd: bad dtype %d", dtype);
+    case PERMUT_REFUSE_POOL_LDS: return spv_set_error("spv_permut_gather_fwd: pooled output needs the LDS path");
+    case PERMUT_REFUSE_POOL_WINDOW: return spv_set_error("spv_permut_gather_fwd: unsupported pool window %d", pool_window);
+    case PERMUT_REFUSE_POOL_UNSERVED:
+        return spv_set_error("spv_permut_gather_fwd: pooled output needs x, g and the table 16-byte aligned (x %p, g %p, idx %p) and, on a long row, d %% 8 == 0 "
+                             "and heads, batch <= 65535 (d=%d heads=%d batch=%d)", x, g, (const void*)idx, d, heads, batch);
+    case PERMUT_FWD_PAIR: {
         const Compact c = compact_of(idx, total_e);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_fwd_pair_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         SPV_COUNT_PATH(SPV_PATH_GATHER_LDS);
         hipLaunchKernelGGL(gather_fwd_pair_kernel, dim3((batch + 1) / 2), dim3(PT), (size_t)d * 4, st, (const uint16_t*)x, c.fwd16, c.fwd_sg,
                            (uint16_t*)g, heads, d, (bf16_t*)pooled, pool_window, batch);
-    } else if (aligned && (size_t)d * es <= (size_t)LDS_LIMIT) {
+        break;
+    }
+    case PERMUT_FWD_LDS: {
         const size_t lds = (size_t)d * es;
         if (dtype == SPV_BF16) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_fwd_lds_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
@@ -804,26 +735,26 @@ extern "C" int spv_permut_gather_fwd(const void* x, const uint32_t* idx, void* g
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_fwd_lds_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
             hipLaunchKernelGGL((gather_fwd_lds_kernel<float>), dim3(batch), dim3(PT), lds, st, (const float*)x, idx, (float*)g, heads, d, (float*)pooled, pool_window);
         }
-    } else if (dtype == SPV_BF16 && long_row(d) && d % 8 == 0 && (pooled == nullptr || scat_pool) &&
-               (((uintptr_t)x | (uintptr_t)g) & 15) == 0 && heads <= 65535 && batch <= 65535) {
+        break;
+    }
+    case PERMUT_FWD_SCATTER: {
         // output quarters in LDS, filled from the inverse table's lists (spv_permut_pack)
-        const ScatTail t = scat_of(const_cast<uint32_t*>(idx) + (spv_permut_table_words(heads, d) - scat_words(heads, d)) + scat_set_words(heads, d), heads, d);
+        const ScatTail t = scat_of(const_cast<uint32_t*>(idx) + (permut_table_words(heads, d) - scat_words(heads, d)) + scat_set_words(heads, d), heads, d);
         const int np = scat_parts(d), L = scat_len(d);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_fwd_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         hipLaunchKernelGGL(gather_fwd_scatter_kernel, dim3(np, heads, batch), dim3(1024), (size_t)L * 2, st, (const uint16_t*)x, t.off, t.ej, t.et, (uint16_t*)g, heads,
                            d, L, np, (bf16_t*)pooled, pool_window);
-    } else if (dtype == SPV_BF16 && d % 8 == 0 && (((uintptr_t)x | (uintptr_t)g | (uintptr_t)idx) & 15) == 0 && (int64_t)heads * d < (1ll << 31) - PARTS_CHF) {
-        // rows longer than the LDS: staged part by part (Base / 224)
-        const int part = parts_len(d);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_fwd_parts_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
-        const dim3 grid((unsigned)(((int64_t)heads * d + PARTS_CHF - 1) / PARTS_CHF), batch);
-        hipLaunchKernelGGL(gather_fwd_parts_kernel, grid, dim3(PARTS_T), (size_t)part * 2, st, (const uint16_t*)x, idx, (uint16_t*)g, heads, d, part);
-    } else {
-        dim3 grid((unsigned)std::min<int64_t>(((int64_t)heads * d + 255) / 256, 1024), batch);
+        break;
+    }
+    case PERMUT_FWD_GLOBAL: {   // element-wide accesses: any shape, any alignment of the element type; never with `pooled`
+        dim3 grid((unsigned)std::min<int64_t>((total_e + 255) / 256, 1024), batch);
         if (dtype == SPV_BF16)
             hipLaunchKernelGGL((gather_fwd_global_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)x, idx, (bf16_t*)g, heads, d);
         else
             hipLaunchKernelGGL((gather_fwd_global_kernel<float>), grid, dim3(256), 0, st, (const float*)x, idx, (float*)g, heads, d);
+        break;
+    }
+    default: return spv_set_error("spv_permut_gather_fwd: no path");
     }
     SPV_LAUNCH_CHECK("spv_permut_gather_fwd");
     return 0;
@@ -831,53 +762,54 @@ extern "C" int spv_permut_gather_fwd(const void* x, const uint32_t* idx, void* g
 
 extern "C" int spv_permut_gather_bwd(const void* dg, const uint32_t* idx, void* dx, int batch, int heads, int d, int dtype,
                                      void* stream) {
-    SPV_CHECK(batch > 0 && heads > 0 && d > 0, "spv_permut_gather_bwd: empty");
-    SPV_CHECK(dtype == SPV_F32 || dtype == SPV_BF16, "spv_permut_gather_bwd: bad dtype %d", dtype);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const uint32_t* inv = idx + (size_t)heads * d;
-    const size_t es = dtype == SPV_BF16 ? 2 : 4;
-    const bool aligned = ((size_t)d * es) % 16 == 0 && d % 4 == 0;
-    if (dtype == SPV_BF16 && compact_ok(d) && ((size_t)d * 2) % 1024 == 0 && (size_t)d * 4 <= (size_t)LDS_LIMIT &&
-        d <= 8 * PT * C_IT && (((uintptr_t)dg | (uintptr_t)dx) & 15) == 0) {
+    switch (permut_bwd_path(dtype, heads, d, batch, al16(dg), al16(dx), al16(idx))) {
+    case PERMUT_REFUSE_EMPTY: return spv_set_error("spv_permut_gather_bwd: empty");
+    case PERMUT_REFUSE_DTYPE: return spv_set_error("spv_permut_gather_bwd: bad dtype %d", dtype);
+    case PERMUT_BWD_DMA: {
         const Compact c = compact_of(idx, (int64_t)heads * d);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_dma_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         const int wgs = std::min(batch, 256);
         hipLaunchKernelGGL(gather_bwd_dma_kernel, dim3(wgs), dim3(PT), (size_t)d * 4, st, (const bf16_t*)dg, c.inv16, c.inv_sg, (bf16_t*)dx, heads, d, batch);
-    } else if (dtype == SPV_BF16 && compact_ok(d) && (size_t)d * 2 <= (size_t)LDS_LIMIT && d <= 8 * PT * C_IT) {
+        break;
+    }
+    case PERMUT_BWD_C16: {
         const Compact c = compact_of(idx, (int64_t)heads * d);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_c16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         hipLaunchKernelGGL(gather_bwd_c16_kernel, dim3(batch), dim3(PT), (size_t)d * 2, st, (const bf16_t*)dg, c.inv16, c.inv_sg, (bf16_t*)dx, heads, d);
-    } else if (aligned && (size_t)d * es <= (size_t)LDS_LIMIT && d <= 4 * PT * MAX_IT) {
-        const size_t lds = (size_t)d * es;
-        if (dtype == SPV_BF16) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_lds_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
-            hipLaunchKernelGGL((gather_bwd_lds_kernel<bf16_t>), dim3(batch), dim3(PT), lds, st, (const bf16_t*)dg, inv, (bf16_t*)dx, heads, d);
-        } else {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_lds_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
-            hipLaunchKernelGGL((gather_bwd_lds_kernel<float>), dim3(batch), dim3(PT), lds, st, (const float*)dg, inv, (float*)dx, heads, d);
-        }
-    } else if (dtype == SPV_BF16 && long_row(d) && d % 8 == 0 && (size_t)scat_len(d) * 4 <= (size_t)LDS_LIMIT) {
+        break;
+    }
+    case PERMUT_BWD_LDS:
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_lds_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
+        hipLaunchKernelGGL((gather_bwd_lds_kernel<float>), dim3(batch), dim3(PT), (size_t)d * 4, st, (const float*)dg, inv, (float*)dx, heads, d);
+        break;
+    case PERMUT_BWD_SCATTER: {
         // the scatter into output parts (lists built by spv_permut_pack behind the other tables)
-        const ScatTail t = scat_of(const_cast<uint32_t*>(idx) + (spv_permut_table_words(heads, d) - scat_words(heads, d)), heads, d);
+        const ScatTail t = scat_of(const_cast<uint32_t*>(idx) + (permut_table_words(heads, d) - scat_words(heads, d)), heads, d);
         const int np = scat_parts(d), L = scat_len(d);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_scatter_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         hipLaunchKernelGGL(gather_bwd_scatter_kernel, dim3(np, batch), dim3(1024), (size_t)L * 4, st, (const bf16_t*)dg, t.off, t.ej, t.et, (bf16_t*)dx, heads, d, L,
                            np);
-    } else if (dtype == SPV_BF16 && d % 8 == 0 && (((uintptr_t)dg | (uintptr_t)dx | (uintptr_t)inv) & 15) == 0) {
+        break;
+    }
+    case PERMUT_BWD_PARTS: {
         // each of a sample's `heads` gradient rows serves only d lookups (the forward's ONE row serves heads x d), so a workgroup stages
-        // heads x parts = 24 parts of 151 KB for its 32 768 results: 581 us per Base layer where the global path measures 438 in the
-        // kernel statistics -- and still the better step (same job, alternating: 27.73 / 27.88 against 28.17 / 28.28 ms), because it
-        // leaves the L2 to the weight-gradient GEMM it runs beside
-        const int part = parts_len(d);
+        // `heads` rows for its 32 768 results; it leaves the L2 to the weight-gradient GEMM it runs beside
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gather_bwd_parts_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_LIMIT);
         const dim3 grid((unsigned)((d + PARTS_CH - 1) / PARTS_CH), batch);
-        hipLaunchKernelGGL(gather_bwd_parts_kernel, grid, dim3(PARTS_T), (size_t)part * 2, st, (const bf16_t*)dg, inv, (bf16_t*)dx, heads, d, part);
-    } else {
+        hipLaunchKernelGGL(gather_bwd_parts_kernel, grid, dim3(PARTS_T), (size_t)d * 2, st, (const bf16_t*)dg, inv, (bf16_t*)dx, heads, d);
+        break;
+    }
+    case PERMUT_BWD_GLOBAL: {   // element-wide accesses: any shape, any alignment of the element type
         dim3 grid((unsigned)std::min((d + 255) / 256, 1024), batch);
         if (dtype == SPV_BF16)
             hipLaunchKernelGGL((gather_bwd_global_kernel<bf16_t>), grid, dim3(256), 0, st, (const bf16_t*)dg, inv, (bf16_t*)dx, heads, d);
         else
             hipLaunchKernelGGL((gather_bwd_global_kernel<float>), grid, dim3(256), 0, st, (const float*)dg, inv, (float*)dx, heads, d);
+        break;
+    }
+    default: return spv_set_error("spv_permut_gather_bwd: no path");
     }
     SPV_LAUNCH_CHECK("spv_permut_gather_bwd");
     return 0;
@@ -893,11 +825,12 @@ namespace {
 template <typename T>
 __global__ __launch_bounds__(256) void permut_row0_fwd_kernel(const T* __restrict__ x, const uint32_t* __restrict__ idx, T* __restrict__ g0,
                                                               T* __restrict__ x0, int d, int n, int E) {
-    const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;
-    if (c >= n) return;
-    const uint32_t w = idx[c];
-    const float v = io<T>::ld(x + (size_t)b * d + (w & 0x7fffffffu));
-    io<T>::st(g0 + (size_t)b * n + c, (w >> 31) ? -v : v);
+    const int b = blockIdx.y, c = blockIdx.x * 256 + threadIdx.x;   // the grid covers max(n, E)
+    if (c < n) {
+        const uint32_t w = idx[c];
+        const float v = io<T>::ld(x + (size_t)b * d + (w & 0x7fffffffu));
+        io<T>::st(g0 + (size_t)b * n + c, (w >> 31) ? -v : v);
+    }
     if (c < E) x0[(size_t)b * E + c] = x[(size_t)b * d + c];
 }
 // the forward with the sample's row in LDS: one coalesced read of the 65 KB row, the n random two-byte reads served by LDS (from global
@@ -971,13 +904,12 @@ __global__ __launch_bounds__(1024) void permut_row0_bwd_lds_kernel(const T* __re
 
 extern "C" int spv_permut_row0_fwd(const void* x, const uint32_t* idx, void* g0, void* x0, int batch, int d, int n, int embed, int dtype,
                                    void* stream) {
-    SPV_CHECK(batch > 0 && d > 0 && n > 0 && n <= d && embed > 0 && embed <= d, "spv_permut_row0_fwd: batch=%d d=%d n=%d embed=%d", batch, d, n, embed);
-    SPV_CHECK(dtype == SPV_F32 || dtype == SPV_BF16, "spv_permut_row0_fwd: bad dtype %d", dtype);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    dim3 grid(cdiv(n, 256), batch);
     const size_t row_bytes = (size_t)d * (dtype == SPV_BF16 ? 2 : 4);
-    const int vec = dtype == SPV_BF16 ? 8 : 4;
-    if (row_bytes <= 150 * 1024 && d % vec == 0 && embed % vec == 0 && ((uintptr_t)x & 15) == 0 && ((uintptr_t)x0 & 15) == 0) {
+    switch (permut_row0_fwd_path(dtype, batch, d, n, embed, al16(x), al16(x0))) {
+    case PERMUT_REFUSE_ROW0_SHAPE: return spv_set_error("spv_permut_row0_fwd: batch=%d d=%d n=%d embed=%d", batch, d, n, embed);
+    case PERMUT_REFUSE_DTYPE: return spv_set_error("spv_permut_row0_fwd: bad dtype %d", dtype);
+    case PERMUT_ROW0_FWD_LDS:
         if (dtype == SPV_BF16) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&permut_row0_fwd_lds_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_bytes);
             hipLaunchKernelGGL(permut_row0_fwd_lds_kernel<bf16_t>, dim3(batch), dim3(1024), row_bytes, st, (const bf16_t*)x, idx, (bf16_t*)g0, (bf16_t*)x0, d, n, embed);
@@ -985,10 +917,17 @@ extern "C" int spv_permut_row0_fwd(const void* x, const uint32_t* idx, void* g0,
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&permut_row0_fwd_lds_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_bytes);
             hipLaunchKernelGGL(permut_row0_fwd_lds_kernel<float>, dim3(batch), dim3(1024), row_bytes, st, (const float*)x, idx, (float*)g0, (float*)x0, d, n, embed);
         }
-    } else if (dtype == SPV_BF16)
-        hipLaunchKernelGGL(permut_row0_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, idx, (bf16_t*)g0, (bf16_t*)x0, d, n, embed);
-    else
-        hipLaunchKernelGGL(permut_row0_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)x, idx, (float*)g0, (float*)x0, d, n, embed);
+        break;
+    case PERMUT_ROW0_FWD_GLOBAL: {
+        dim3 grid(cdiv(std::max(n, embed), 256), batch);   // x0 has embed elements whatever n is
+        if (dtype == SPV_BF16)
+            hipLaunchKernelGGL(permut_row0_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, idx, (bf16_t*)g0, (bf16_t*)x0, d, n, embed);
+        else
+            hipLaunchKernelGGL(permut_row0_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)x, idx, (float*)g0, (float*)x0, d, n, embed);
+        break;
+    }
+    default: return spv_set_error("spv_permut_row0_fwd: no path");
+    }
     SPV_COUNT_PATH(SPV_PATH_PERMUT_ROW0);
     SPV_LAUNCH_CHECK("spv_permut_row0_fwd");
     return 0;
@@ -996,12 +935,13 @@ extern "C" int spv_permut_row0_fwd(const void* x, const uint32_t* idx, void* g0,
 
 extern "C" int spv_permut_row0_bwd(const void* dg0, const void* dx0, const uint32_t* idx, void* dx, int batch, int d, int n, int embed,
                                    int dtype, void* stream) {
-    SPV_CHECK(batch > 0 && d > 0 && n > 0 && n <= d && embed > 0 && embed <= d && d % 8 == 0 && embed % 8 == 0,
-              "spv_permut_row0_bwd: batch=%d d=%d n=%d embed=%d (d, embed multiples of 8)", batch, d, n, embed);
-    SPV_CHECK(dtype == SPV_F32 || dtype == SPV_BF16, "spv_permut_row0_bwd: bad dtype %d", dtype);
     hipStream_t st = static_cast<hipStream_t>(stream);
     const size_t row_bytes = (size_t)d * (dtype == SPV_BF16 ? 2 : 4);
-    if (row_bytes <= 150 * 1024 && (dtype == SPV_BF16 ? d % 8 == 0 : d % 4 == 0) && ((uintptr_t)dx & 15) == 0 && ((uintptr_t)dx0 & 15) == 0) {
+    switch (permut_row0_bwd_path(dtype, batch, d, n, embed, al16(dx), al16(dx0))) {
+    case PERMUT_REFUSE_ROW0_SHAPE:
+        return spv_set_error("spv_permut_row0_bwd: batch=%d d=%d n=%d embed=%d (d, embed multiples of 8)", batch, d, n, embed);
+    case PERMUT_REFUSE_DTYPE: return spv_set_error("spv_permut_row0_bwd: bad dtype %d", dtype);
+    case PERMUT_ROW0_BWD_LDS:
         // one workgroup per sample, the row in LDS
         if (dtype == SPV_BF16) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&permut_row0_bwd_lds_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)row_bytes);
@@ -1012,12 +952,17 @@ extern "C" int spv_permut_row0_bwd(const void* dg0, const void* dx0, const uint3
             hipLaunchKernelGGL(permut_row0_bwd_lds_kernel<float>, dim3(batch), dim3(1024), row_bytes, st, (const float*)dg0, (const float*)dx0, idx, (float*)dx, d, n,
                                embed);
         }
-    } else if (dtype == SPV_BF16) {
-        hipLaunchKernelGGL(permut_row0_init_kernel<bf16_t>, dim3(cdiv(d / 8, 256), batch), dim3(256), 0, st, (const bf16_t*)dx0, (bf16_t*)dx, d, embed);
-        hipLaunchKernelGGL(permut_row0_scatter_kernel<bf16_t>, dim3(cdiv(n, 256), batch), dim3(256), 0, st, (const bf16_t*)dg0, idx, (bf16_t*)dx, d, n);
-    } else {
-        hipLaunchKernelGGL(permut_row0_init_kernel<float>, dim3(cdiv(d / 8, 256), batch), dim3(256), 0, st, (const float*)dx0, (float*)dx, d, embed);
-        hipLaunchKernelGGL(permut_row0_scatter_kernel<float>, dim3(cdiv(n, 256), batch), dim3(256), 0, st, (const float*)dg0, idx, (float*)dx, d, n);
+        break;
+    case PERMUT_ROW0_BWD_GLOBAL:
+        if (dtype == SPV_BF16) {
+            hipLaunchKernelGGL(permut_row0_init_kernel<bf16_t>, dim3(cdiv(d / 8, 256), batch), dim3(256), 0, st, (const bf16_t*)dx0, (bf16_t*)dx, d, embed);
+            hipLaunchKernelGGL(permut_row0_scatter_kernel<bf16_t>, dim3(cdiv(n, 256), batch), dim3(256), 0, st, (const bf16_t*)dg0, idx, (bf16_t*)dx, d, n);
+        } else {
+            hipLaunchKernelGGL(permut_row0_init_kernel<float>, dim3(cdiv(d / 8, 256), batch), dim3(256), 0, st, (const float*)dx0, (float*)dx, d, embed);
+            hipLaunchKernelGGL(permut_row0_scatter_kernel<float>, dim3(cdiv(n, 256), batch), dim3(256), 0, st, (const float*)dg0, idx, (float*)dx, d, n);
+        }
+        break;
+    default: return spv_set_error("spv_permut_row0_bwd: no path");
     }
     SPV_COUNT_PATH(SPV_PATH_PERMUT_ROW0);
     SPV_LAUNCH_CHECK("spv_permut_row0_bwd");
