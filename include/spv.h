@@ -466,6 +466,55 @@ int spv_adamw_multi_ctl_ema(const void* table, const int* chunk_tensor, const in
 int spv_fwht(const void* x, void* y, const void* residual, int rows, int n_in, int n, int n_out, int mode, int repeat,
              float scale, int dtype, void* stream);
 
+/* ---- Walsh-Hadamard token mixer  y = crop_{N,D}( H_Np . pad_{Np,Dp}(x) . H_Dp ) . scale  over (tokens, dim) -------------------
+ * The 2-D operator of the same file's functions: fwht(fwht(F.pad(x, (0, Dp - D, 0, Np - N)), dim=-1), dim=-2)[..., :N, :D] with
+ * Np / Dp = next_pow2 (hadamar.py:12-32, LearnableHadamard's pad / crop :130-139); H natural order (Sylvester); the caller passes
+ * scale = (Np Dp)^-1/2 for fwht's default normalize=True, 1 otherwise.  crop = pad^T and H is symmetric, so the same call is its
+ * own backward.  `add_in` (nullable, same shape / dtype as y) is added to the output: in the backward, the residual-stream gradient
+ * that bypasses the mixer (spectre.py:66).  fp32 and bf16; any tokens >= 1, any dim >= 1 with Dp <= 16384.
+ *   one kernel   dim % 8 == 0, tokens <= 128 and tokens * Dp * 4 <= 160 KiB (the padded image in LDS as fp32, no other scratch): one
+ *                read of x, one write of y.  Moves 16 bytes per access: x, y and add_in must be 16-byte aligned, else refused.
+ *   generic      everything else with Np <= 32768: rows along dim into `workspace` (spv_hadamard_workspace_floats floats, fp32), then
+ *                column slabs along tokens.  Any alignment of the element type.
+ * spv_hadamard_path: which of the two spv_hadamard_mix would take for a shape (the answer of the host-pure selector in
+ * csrc/spv_hadamard_core.h, which the entry point itself switches on), or why it refuses.  Pointer alignment is not a shape: a
+ * misaligned one-kernel call is refused by spv_hadamard_mix itself. */
+#define SPV_HADAMARD_ONE_KERNEL 1
+#define SPV_HADAMARD_GENERIC 2
+#define SPV_HADAMARD_REFUSE_EMPTY (-1)      /* tokens < 1 or dim < 1 */
+#define SPV_HADAMARD_REFUSE_DTYPE (-2)
+#define SPV_HADAMARD_REFUSE_DIM (-3)        /* next_pow2(dim) > 16384 */
+#define SPV_HADAMARD_REFUSE_TOKENS (-4)     /* generic path: next_pow2(tokens) > 32768 */
+#define SPV_HADAMARD_REFUSE_WORKSPACE (-5)  /* generic path without a workspace */
+int spv_hadamard_path(int dtype, int tokens, int dim, int has_workspace);
+int64_t spv_hadamard_workspace_floats(int batch, int tokens, int dim);
+int spv_hadamard_mix(const void* x, void* y, const void* add_in, int batch, int tokens, int dim, float scale, int dtype,
+                     float* workspace, void* stream);
+/* First half of the encoder layer as ONE kernel each way: x1 = LayerNorm1(mix(x)) + x (spectre.py:66 with the Hadamard mixer), the
+ * argument shape of spv_fnet_ln_fwd / _bwd with `scale` in the twiddle table's place.  Window (spv_hadamard_ln_supported): bf16,
+ * dim 512, 2 <= tokens <= 65; otherwise callers compose spv_hadamard_mix with spv_add_layernorm_*.
+ *   fwd: prenorm = mix(x) (kept for the backward), out = LN(prenorm) * gamma + beta + x, mean / rstd [batch * tokens].
+ *   bwd: dx = mix(LN1-backward(dout)) + dout; partials: batch * 2 * dim floats = each sample's dgamma / dbeta contribution;
+ *        dgamma / dbeta [dim], or both NULL: the caller folds `partials` (parts = batch, nsum = 2, n = dim: spv_fold_multi or a
+ *        riding fold).
+ * The token axis runs on the MFMA against the +-1 corner H_Np[:N, :N] (exact in bf16); the backward's fp32 LayerNorm gradient enters
+ * it as a hi + lo pair of bf16 values.  No global scratch.  x / prenorm / out, dout / dx, gamma and beta 16-byte aligned. */
+int spv_hadamard_ln_supported(int tokens, int dim, int dtype);
+int spv_hadamard_ln_fwd(const void* x, void* prenorm, void* out, const float* gamma, const float* beta, float* mean, float* rstd,
+                        float scale, int batch, int tokens, int dim, int dtype, void* stream);
+int spv_hadamard_ln_bwd(const void* dout, const void* prenorm, const float* mean, const float* rstd, const float* gamma, void* dx,
+                        float* dgamma, float* dbeta, float* partials, float scale, int batch, int tokens, int dim, int dtype,
+                        void* stream);
+/* Row 0 only of the same node (the last layer of a stack whose consumer reads the CLS row, as spv_fnet_cls_*): row 0 of H_Np is all
+ * ones, so m0 = scale * H_D . (sum over tokens of x): one pass over the sample and ONE dim-point transform.  dim 256 / 512 / 1024,
+ * tokens >= 1, both dtypes.  out [batch, dim], m0 [batch, dim] fp32, mean / rstd [batch].  Backward: g1 [batch, dim] -> dx [batch,
+ * tokens, dim] (every row the same transformed row, row 0 + g1), partials [batch][2][dim].  x, out and dx 16-byte aligned. */
+int spv_hadamard_cls_supported(int tokens, int dim, int dtype);
+int spv_hadamard_cls_fwd(const void* x, const float* gamma, const float* beta, void* out, float* m0, float* mean, float* rstd,
+                         float scale, int batch, int tokens, int dim, int dtype, void* stream);
+int spv_hadamard_cls_bwd(const void* g1, const float* m0, const float* mean, const float* rstd, const float* gamma, void* dx,
+                         float* partials, float scale, int batch, int tokens, int dim, int dtype, void* stream);
+
 /* ---- patch embedding ---------------------------------------------------------------------------
  * tokens[b,0,:] = cls + pos[0]; tokens[b,1+n,:] = W_full . patch(b,n) + bias + pos[1+n]
  * where patch(b,n) is the (c,p,q)-ordered P x P pixel block.  With W_full = conv weight this is

@@ -725,6 +725,50 @@ class FNetMixFn(torch.autograd.Function):
         return _fnet_raw(dy)
 
 
+_hadamard_ws = {}
+
+
+def _next_pow2(n):
+    return 1 << max(0, int(n) - 1).bit_length()
+
+
+def hadamard_scale(tokens, dim, normalize=True):
+    """s of y = crop(H_Np pad(x) H_Dp) s: (Np Dp)^-1/2 (fwht's normalize=True on both axes) or 1; the kernels receive it rounded to float32"""
+    return float(_next_pow2(tokens) * _next_pow2(dim)) ** -0.5 if normalize else 1.0
+
+
+def _hadamard_raw(x, normalize=True, add_in=None):
+    B, N, D = x.shape
+    xc = x.contiguous()
+    y = torch.empty_like(xc)
+    wsn = _native.call("spv_hadamard_workspace_floats", B, N, D)
+    ws = None
+    if wsn:   # one workspace per shape and device, reused by every call (stream-ordered; nothing here synchronises the host)
+        key = (B, N, D, xc.device)
+        ws = _hadamard_ws.get(key)
+        if ws is None:
+            ws = _hadamard_ws[key] = torch.empty((wsn,), dtype=torch.float32, device=xc.device)
+    if add_in is not None:
+        add_in = add_in.contiguous()
+    _native.call("spv_hadamard_mix", _p(xc), _p(y), _p(add_in), B, N, D, hadamard_scale(N, D, normalize), _dt(xc), _p(ws), _stream())
+    return y
+
+
+class HadamardMixFn(torch.autograd.Function):
+    """y = crop(H_Np . pad(x) . H_Dp) s over the last two axes (reference hadamar.py: fwht on both axes with LearnableHadamard's pad /
+    crop); symmetric operator => backward is the same kernel."""
+
+    @staticmethod
+    def forward(ctx, x, normalize):
+        _require_gpu(x)
+        ctx.normalize = normalize
+        return _hadamard_raw(x, normalize)
+
+    @staticmethod
+    def backward(ctx, dy):
+        return _hadamard_raw(dy, ctx.normalize), None
+
+
 class RfftRealFn(torch.autograd.Function):
     """rfft(x, dim=-1).real (reference spectre_vit/modules/spectre.py:9-14)."""
 
@@ -1873,6 +1917,100 @@ class FNetClsFn(torch.autograd.Function):
             arr = _fold_array([_Fold(partials, _addrs((dn1w, dn1b)), B, D)])
             _native.call("spv_fold_multi", ctypes.addressof(arr), 1, _stream())
         return dx, dn1w, dn1b
+
+
+def hadamard_ln_ok(x):
+    """the Hadamard mixer + LayerNorm-1 + residual can run as the fused kernels (spv_hadamard_ln_fwd / _bwd)"""
+    return x.is_cuda and x.dim() == 3 and x.dtype in _DT and bool(_native.call("spv_hadamard_ln_supported", x.shape[1], x.shape[2], _dt(x)))
+
+
+def hadamard_cls_ok(x):
+    """row 0 of the same node can come from the one-transform kernels (spv_hadamard_cls_fwd / _bwd)"""
+    return x.is_cuda and x.dim() == 3 and x.dtype in _DT and bool(_native.call("spv_hadamard_cls_supported", x.shape[1], x.shape[2], _dt(x)))
+
+
+class HadamardResidualFn(torch.autograd.Function):
+    """x1 = LayerNorm1(hadamard_mix(x)) + x   (reference spectre.py:66 with the Walsh-Hadamard mixer): one kernel each way inside
+    spv_hadamard_ln_supported's window, spv_hadamard_mix + the LayerNorm kernels outside it."""
+
+    @staticmethod
+    def forward(ctx, x, n1w, n1b, normalize):
+        _require_gpu(x)
+        B, N, D = x.shape
+        xc = x.contiguous()
+        ctx.shape = (B, N, D)
+        ctx.normalize = normalize
+        if _native.call("spv_hadamard_ln_supported", N, D, _dt(xc)):
+            dev = xc.device
+            m = torch.empty_like(xc)
+            out = torch.empty_like(xc)
+            mean, rstd = _row_stats(B * N, dev)
+            _native.call("spv_hadamard_ln_fwd", _p(xc), _p(m), _p(out), _p(n1w), _p(n1b), _p(mean), _p(rstd), hadamard_scale(N, D, normalize),
+                         B, N, D, _dt(xc), _stream())
+            ctx.saved = _FNetLN1Saved(m, mean, rstd, n1w, (_sink(n1w), _sink(n1b)))
+            return out
+        m = _hadamard_raw(xc, normalize)
+        out, sn = _addln_forward(m.reshape(-1, D), xc.reshape(-1, D), n1w, n1b, 0)
+        ctx.saved = sn
+        return out.reshape(B, N, D)
+
+    @staticmethod
+    def backward(ctx, dout):
+        sn = ctx.saved
+        B, N, D = ctx.shape
+        d2 = _rows2d(dout, D)
+        if isinstance(sn, _FNetLN1Saved):
+            m, mean, rstd, gamma, sinks = sn
+            dev = m.device
+            dx = torch.empty_like(m)
+            dn1w = _grad_buf(sinks[0], (D,), dev)
+            dn1b = _grad_buf(sinks[1], (D,), dev)
+            partials = torch.empty((B * 2 * D,), dtype=torch.float32, device=dev)
+            held = _hold_fold(partials, (dn1w, dn1b), sinks, B, D)   # the fold travels with the next weight-gradient reduce
+            _native.call("spv_hadamard_ln_bwd", _p(d2), _p(m), _p(mean), _p(rstd), _p(gamma), _p(dx), 0 if held else _p(dn1w),
+                         0 if held else _p(dn1b), _p(partials), hadamard_scale(N, D, ctx.normalize), B, N, D, _dt(m), _stream())
+            return dx, dn1w, dn1b, None
+        dm, dn1w, dn1b = _addln_backward(d2, sn)
+        dx = _hadamard_raw(dm.reshape(B, N, D), ctx.normalize, add_in=d2)  # symmetric operator; + the residual gradient, folded in
+        return dx, dn1w, dn1b, None
+
+
+class HadamardClsFn(torch.autograd.Function):
+    """x (B, N, D) -> (LayerNorm1(hadamard_mix(x)) + x)[:, 0, :] as (B, D): row 0 of H_Np is all ones, so the row is ONE D-point transform
+    of the token sum (spv_hadamard_cls_fwd: one pass over x); the backward hands every token the same transformed row (+ the residual's
+    gradient in row 0)."""
+
+    @staticmethod
+    def forward(ctx, x, n1w, n1b, normalize):
+        _require_gpu(x)
+        B, N, D = x.shape
+        xc = x.contiguous()
+        dev = xc.device
+        out = torch.empty((B, D), dtype=xc.dtype, device=dev)
+        m0 = torch.empty((B, D), dtype=torch.float32, device=dev)
+        mean, rstd = _row_stats(B, dev)
+        scale = hadamard_scale(N, D, normalize)
+        _native.call("spv_hadamard_cls_fwd", _p(xc), _p(n1w), _p(n1b), _p(out), _p(m0), _p(mean), _p(rstd), scale, B, N, D, _dt(xc), _stream())
+        ctx.saved = (m0, mean, rstd, n1w, (_sink(n1w), _sink(n1b)))
+        ctx.meta = (B, N, D, xc.dtype, scale)
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        m0, mean, rstd, n1w, sinks = ctx.saved
+        B, N, D, dtype, scale = ctx.meta
+        dev = m0.device
+        g = g.to(dtype).contiguous()
+        dx = torch.empty((B, N, D), dtype=dtype, device=dev)
+        dn1w = _grad_buf(sinks[0], (D,), dev)
+        dn1b = _grad_buf(sinks[1], (D,), dev)
+        partials = torch.empty((B * 2 * D,), dtype=torch.float32, device=dev)
+        _native.call("spv_hadamard_cls_bwd", _p(g), _p(m0), _p(mean), _p(rstd), _p(n1w), _p(dx), _p(partials), scale, B, N, D, _DT[dtype],
+                     _stream())
+        if not _hold_fold(partials, (dn1w, dn1b), sinks, B, D):   # the batch sums of dgamma / dbeta: with the next reduce, or now
+            arr = _fold_array([_Fold(partials, _addrs((dn1w, dn1b)), B, D)])
+            _native.call("spv_fold_multi", ctypes.addressof(arr), 1, _stream())
+        return dx, dn1w, dn1b, None
 
 
 class HaarResidualFn(torch.autograd.Function):

@@ -4,7 +4,7 @@ Class names, constructor arguments, forward signatures and state_dict keys follo
 (SURVEY.md 8b); the arithmetic runs in libspv_hip.so.  One labelled extension: ``mixer=`` on
 SpectreViT / SpectreEncoderLayer selects the token mixer ("permut" = the reference's HEAD default
 MHPermutMix, "fft" = FNet Re(fft2), "dwt_embed" / "dwt_token" = Haar DWT, "attention" = self-attention over
-the tokens with nn.MultiheadAttention's parameters) -- the modes the reference's docstring lists
+the tokens with nn.MultiheadAttention's parameters, "hadamard" = the 2-D Walsh-Hadamard transform of the reference's hadamar.py) -- the modes the reference's docstring lists
 (spectre.py:29-35; its undefined "fft_mh" aside) and BASELINE.json benchmarks.
 """
 import torch
@@ -13,9 +13,9 @@ from torch.nn.modules.transformer import _get_activation_fn, _get_clones
 
 from spectre_vit import hip_ops, shadows
 from spectre_vit.models.spectre.layers import MHPermutMix, SpectreLinear
-from spectre_vit.modules.mixers import FNetMixer, HaarDWTMixer, SelfAttentionMixer
+from spectre_vit.modules.mixers import FNetMixer, HaarDWTMixer, HadamardMixer, SelfAttentionMixer
 
-MIXERS = ("permut", "fft", "dwt_embed", "dwt_token", "attention")
+MIXERS = ("permut", "fft", "dwt_embed", "dwt_token", "attention", "hadamard")
 
 
 class Transpose(nn.Module):
@@ -40,6 +40,8 @@ def _make_mixer(mixer, d_model, seq_length, nhead, dwt_levels, dwt_mode="passthr
         return HaarDWTMixer("token", dwt_levels, dwt_mode)
     if mixer == "attention":
         return SelfAttentionMixer(d_model, nhead, dropout)
+    if mixer == "hadamard":
+        return HadamardMixer()
     raise ValueError(f"mixer must be one of {MIXERS}, got {mixer!r}")
 
 
@@ -83,6 +85,11 @@ class SpectreEncoderLayer(nn.Module):
             if hip_ops.fnet_cls_ok(xc):
                 # row 0 of Re(fft2(x)) is one FFT of the token sum: the mixer half as one pass over x, its backward one write
                 return self._ff(hip_ops.FNetClsFn.apply(xc, self.norm1.weight, self.norm1.bias))
+        if self.mixer == "hadamard":
+            xc = hip_ops.cast(x, hip_ops.compute_dtype(x))
+            if hip_ops.hadamard_cls_ok(xc):
+                # row 0 of H is all ones: one transform of the token sum, as for the FFT mixer
+                return self._ff(hip_ops.HadamardClsFn.apply(xc, self.norm1.weight, self.norm1.bias, self.mix_layer.normalize))
         if self.mixer == "attention":
             xc = hip_ops.cast(x, hip_ops.compute_dtype(x))
             if hip_ops.attn_row0_ok(xc, self.mix_layer.num_heads):
@@ -99,6 +106,8 @@ class SpectreEncoderLayer(nn.Module):
         x = hip_ops.cast(x, hip_ops.compute_dtype(x))
         if self.mixer == "fft":  # mixer + norm1 + residual as one autograd node (residual gradient folded into the FFT kernel)
             x = hip_ops.FNetResidualFn.apply(x, self.norm1.weight, self.norm1.bias)
+        elif self.mixer == "hadamard" and hip_ops.hadamard_ln_ok(x):   # the same node for the Walsh-Hadamard mixer, inside its window
+            x = hip_ops.HadamardResidualFn.apply(x, self.norm1.weight, self.norm1.bias, self.mix_layer.normalize)
         elif self.mixer == "dwt_embed" and hip_ops.haar_ln_ok(x, self.mix_layer.axis, self.mix_layer.levels):
             x = hip_ops.HaarResidualFn.apply(x, self.norm1.weight, self.norm1.bias)   # mixer + norm1 + residual as one row kernel each way
         else:

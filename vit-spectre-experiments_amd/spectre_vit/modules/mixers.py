@@ -17,6 +17,23 @@ class FNetMixer(nn.Module):
         return hip_ops.FNetMixFn.apply(hip_ops.cast(x, hip_ops.compute_dtype(x)))
 
 
+class HadamardMixer(nn.Module):
+    """y = crop_{N,D}(H_Np . pad_{Np,Dp}(x) . H_Dp) . s over (tokens, dim): the natural-order Walsh-Hadamard transform along both axes,
+    each zero-padded at its end to the next power of two and cropped back (reference spectre_vit/models/spectre/hadamar.py: fwht
+    :12-32 on dim -1 then dim -2, LearnableHadamard's pad / crop :130-139).  normalize=True (fwht's default): s = (Np Dp)^-1/2.
+    No parameters; the operator is symmetric, so its backward is the same kernel."""
+
+    def __init__(self, normalize: bool = True):
+        super().__init__()
+        self.normalize = bool(normalize)
+
+    def forward(self, x):
+        return hip_ops.HadamardMixFn.apply(hip_ops.cast(x, hip_ops.compute_dtype(x)), self.normalize)
+
+    def extra_repr(self):
+        return f"normalize={self.normalize}"
+
+
 class HaarDWTMixer(nn.Module):
     """J-level Haar DWT along dim ('dwt_embed') or tokens ('dwt_token'); output bands [a_J | d_J | ... | d_1] (pywt.wavedec's order)
     in place of the transformed axis, pairs a = (x0 + x1) / sqrt2, d = (x0 - x1) / sqrt2 (PyWavelets' documented 'haar').
