@@ -35,17 +35,18 @@ int spv_version(void);
 /* Dispatch census (test aid; no reference counterpart): how many calls each kernel family has served in this process, so a
  * parity test can assert that the shapes it ran really took the fused / strip kernels the benchmark times. */
 enum {
-    SPV_PATH_GEMM_STRIP = 0,     /* gemm_nt_strip_kernel<*, false> */
-    SPV_PATH_GEMM_STRIP_ACC = 1, /* gemm_nt_strip_kernel<*, true>  */
-    SPV_PATH_GEMM_TN = 2,        /* weight-gradient kernel (spv_gemm_tn) */
+    SPV_PATH_GEMM_STRIP = 0,     /* gemm_nt_strip_kernel<MB, 0>: store */
+    SPV_PATH_GEMM_STRIP_ACC = 1, /* gemm_nt_strip_kernel<MB, 1>: accumulate */
+    SPV_PATH_GEMM_TN = 2,        /* every served spv_gemm_tn / _fold call and every spv_gemm_tn_batch GEMM launch, whichever TN kernel ran */
     SPV_PATH_TAIL_LC = 3,        /* lane-contiguous SpectreLinear tail kernels */
     SPV_PATH_TAIL_UP = 4,        /* spv_spectre_tail_bwd_up */
     SPV_PATH_TAIL_LN = 5,        /* spv_spectre_tail_ln_fwd / _bwd */
     SPV_PATH_FNET_MFMA = 6,      /* fnet_mfma_kernel (bf16, dim 512) */
     SPV_PATH_GATHER_LDS = 7,     /* LDS-staged MHPermutMix gather */
     SPV_PATH_DISTILL_CACHED = 8, /* spv_distill_loss_idx_fwd (the distillation loss against the resident teacher-logit cache): one per launch */
-    SPV_PATH_GEMM_TN_WIDE = 9,   /* gemm_tn_wide_kernel (256 x 128 tile; M % 256 == 0, N % 128 == 0) */
-    SPV_PATH_GEMM_TN_BATCH = 10, /* gemm_tn_batch_kernel: up to eight weight gradients in one launch (spv_gemm_tn_batch) */
+    SPV_PATH_GEMM_TN_WIDE = 9,   /* gemm_tn_wide_kernel / gemm_tn_batch_wide_kernel (256 x 128 tile; M % 256 == 0, N % 128 == 0, and for spv_gemm_tn at
+                                  * least 4 slabs and 128 workgroups, unless the tall kernel takes the call) */
+    SPV_PATH_GEMM_TN_BATCH = 10, /* gemm_tn_batch_kernel / gemm_tn_batch_wide_kernel: up to eight weight gradients in one launch (spv_gemm_tn_batch) */
     SPV_PATH_GEMM_STRIP_POOL = 11, /* gemm_nt_strip_kernel<*, 2 / 3>: data gradient + pooled-broadcast term (spv_gemm_nt_pool_bwd) */
     SPV_PATH_GEMM_ROWS = 13,     /* gemm_nt_rows_kernel: few-rows NT GEMM, one 32 x 32 tile per workgroup, no split-K (the CLS-only last layer) */
     SPV_PATH_PERMUT_ROW0 = 12,   /* spv_permut_row0_fwd / _bwd: MHPermutMix at token row 0 (the CLS-only last layer) */
@@ -89,9 +90,12 @@ int spv_weight_shadows_multi(const void* table, const int* tile_tensor, const in
  * nn.Linear inside SpectreLinear (spectre_vit/models/spectre/layers.py:85-86,100), its data and
  * weight gradients, and the patch projection (spectre.py:148).  MFMA: v_mfma_f32_32x32x16_bf16
  * (bf16 in) or v_mfma_f32_32x32x2_f32 (exact fp32 in); fp32 accumulate.
- * K, lda, ldb must be multiples of 16 bytes / sizeof(in element); A,B 16-byte aligned.
+ * K, lda, ldb must be multiples of 16 bytes / sizeof(in element); A,B 16-byte aligned.  C and bias take any alignment of their
+ * element type (off 16 bytes they are served by element-wide stores and loads); ldc >= N is free.
  * splits > 1: split-K over `splits` slices, fp32 partial slabs in `workspace`
- * (>= splits*M*N*4 bytes), reduced by a second kernel (deterministic). */
+ * (>= splits*M*N*4 bytes, 16-byte aligned), reduced by a second kernel (deterministic).  The slices are whole K-tiles (64 bf16 /
+ * 32 fp32 elements), so fewer than `splits` slabs may be written and a request may collapse to one (no workspace access then).
+ * Which kernel serves a call: csrc/spv_gemm_core.h (gemm_nt_plan), DESIGN.md "Which GEMM kernel serves a call". */
 int spv_gemm_nt(const void* A, const void* B, const float* bias, void* C, int M, int N, int K, int lda,
                 int ldb, int ldc, int in_dtype, int out_dtype, int accumulate, int splits,
                 void* workspace, void* stream);
@@ -102,7 +106,8 @@ int spv_gemm_nt_grouped_rows(const void* A, const void* B, const float* bias, co
                              int N, int K, int lda, int ldb, int ldc, int in_dtype, int out_dtype,
                              int rows_per_group, int group_stride, int row_offset, void* stream);
 /* The same with the dropout that follows the projection (spectre.py:156) applied in the epilogue: the mask of spv_dropout /
- * spv_embed_bwd for the same seed over the flat index of the (contiguous, ldc == N) output. */
+ * spv_embed_bwd for the same seed over the flat index of the (contiguous, ldc == N) output: mask(i) = hash(key(i >> 12), i & 4095) for
+ * every element, whatever N is (spv_embed_bwd itself needs N % 8 == 0). */
 int spv_gemm_nt_grouped_rows_drop(const void* A, const void* B, const float* bias, const float* bias2d, void* C, int M, int N, int K,
                                   int lda, int ldb, int ldc, int in_dtype, int out_dtype, int rows_per_group, int group_stride,
                                   int row_offset, float p_drop, uint64_t seed, void* stream);
@@ -119,14 +124,16 @@ int spv_gemm_nt_pool_bwd(const void* A, const void* B, void* C, const void* dout
 int spv_set_reserved_cus(int n);
 /* TN contraction C[M,N] = sum_k A[k][m] B[k][n], A [K,lda>=M], B [K,ldb>=N] row-major bf16: the weight gradient
  * dW = dh^T . x (backward of layers.py:86) straight from the row-major activations (transposing LDS reads,
- * ds_read_b64_tr_b16); M, N, lda, ldb multiples of 8; split-K as above. */
+ * ds_read_b64_tr_b16); M, N, lda, ldb multiples of 8; split-K as above, in slices of whole 64-row K-tiles.  K itself is free (a
+ * partial last K-tile is zero-filled). */
 int spv_gemm_tn(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int out_dtype,
                 int accumulate, int splits, void* workspace, void* stream);
 /* The same, with up to sixteen folds of row kernels' per-workgroup partial column sums riding in the split-K reduce launch as extra
  * workgroups: out[p][c] = sum_w partials[w][p][c], p < nsum <= 5 (dgamma, dbeta, dbias[, dgamma2, dbeta2]), c < n, fixed order.
  * The row kernel (spv_spectre_tail_bwd*, spv_spectre_tail_ln_bwd, spv_fnet_ln_bwd) is then called with its parameter-gradient
  * pointers NULL: it writes the partials and launches no fold (parts = spv_tail_bwd_parts(rows) for the tails, batch for the FNet
- * kernel).  With splits == 1 the folds run as one launch of their own.  Why: a 5-us launch between two large kernels costs the
+ * kernel).  With one slab (splits == 1, or a request that collapses to one) the folds run as one launch of their own.  The fold jobs
+ * are checked before anything is launched: a bad one leaves C untouched.  Why: a 5-us launch between two large kernels costs the
  * step ~20 us (eight per-layer fold launches removed: 157 us of 2.26 ms). */
 typedef struct spv_fold_job {
     const float* partials;
@@ -140,7 +147,8 @@ int spv_fold_multi(const spv_fold_job* folds, int nfolds, void* stream);
 int spv_gemm_tn_fold(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int out_dtype,
                      int accumulate, int splits, void* workspace, const spv_fold_job* folds, int nfolds, void* stream);
 /* Up to 8 weight gradients with the same K (C_i [m_i, n_i] fp32 = A_i[K, lda_i]^T . B_i[K, ldb_i], bf16 operands) in ONE launch
- * + ONE split-K reduce that also carries up to 16 fold jobs.  workspace: splits * sum(m_i * n_i) floats.  For gradients that
+ * + ONE split-K reduce that also carries up to 16 fold jobs.  workspace: splits * sum(m_i * n_i) floats, 16-byte aligned (only the
+ * long problems' slabs are written).  m, n, lda, ldb multiples of 8; ldc >= n, a multiple of 4 for a short problem.  For gradients that
  * nobody reads before the backward pass is over (spectre_vit/hip_ops.py holds them back; reference: the nn.Linear weight
  * gradients autograd computes node by node, layers.py:85-101). */
 typedef struct spv_tn_problem {

@@ -13,6 +13,7 @@
 // (exact fp32 fma chain -- the parity path).
 #define SPV_USES_SEED
 #include "spv_common.h"
+#include "spv_gemm_core.h"
 
 #include <stdlib.h>
 
@@ -21,7 +22,7 @@
 
 namespace {
 
-constexpr int BM = 128, BN = 128;
+constexpr int BM = GEMM_BM, BN = GEMM_BN;
 constexpr int ROWB = 128 + 16;  // LDS bytes per tile row
 constexpr int KBYTES = 128;     // bytes of K per tile row
 
@@ -79,7 +80,8 @@ __device__ __forceinline__ void store_acc_tile(f32x16 (*acc)[2], unsigned char* 
     if (wcol < 0) wcol = (wave & 1) * 64;
     float* stage = reinterpret_cast<float*>(smem + wave * 9216);  // 9216 B per wave >= 32 * 68 * 4
     constexpr int SLD = 68;
-    const bool vec_c = ((size_t)ldc * sizeof(TO)) % 16 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0;
+    // (a bias off 16-byte alignment takes the element-wide branch too: the 8-wide one reads it in 16-byte pieces)
+    const bool vec_c = ((size_t)ldc * sizeof(TO)) % 16 == 0 && ((reinterpret_cast<uintptr_t>(C) | reinterpret_cast<uintptr_t>(bias)) & 15) == 0;
     const bool vec_ws = (N & 3) == 0;
     // the replay-time seed word is ONE global load per tile, issued here (inside the chunk loop it was a dependent L2 round trip in
     // front of every chunk's hash: 7.5 of the embedding GEMM's 25 us)
@@ -166,8 +168,11 @@ __device__ __forceinline__ void store_acc_tile(f32x16 (*acc)[2], unsigned char* 
                     const unsigned key = dropout_row_key(seed_live, (uint64_t)fi >> 12);
                     const unsigned c0 = (unsigned)(fi & 4095);
                     const float inv_keep = 1.0f / (1.0f - drop_p);
+                    // an fp32 output needs only ldc % 4 == 0 for this branch, so fi may be 4 (mod 8) and the eight columns may cross
+                    // into the next 4096-element block: those take that block's key and start at its column 0
+                    const unsigned key_next = c0 > 4088u ? dropout_row_key(seed_live, ((uint64_t)fi >> 12) + 1) : key;
 #pragma unroll
-                    for (int u = 0; u < 8; ++u) v[u] *= dropout_scale(key, c0 + u, drop_p, inv_keep);
+                    for (int u = 0; u < 8; ++u) v[u] *= dropout_scale(c0 + u < 4096u ? key : key_next, (c0 + u) & 4095u, drop_p, inv_keep);
                 }
                 if constexpr (sizeof(TO) == 2) {
                     if (accumulate) {
@@ -336,7 +341,7 @@ __global__ __launch_bounds__(256) void gemm_nt_kernel(const T* __restrict__ A, c
 // conflicts are removed by an XOR swizzle of the 16-byte chunk index with (row >> 1) & 7, applied on the per-lane
 // SOURCE address and again on the fragment read (guide rule 21): the 16 rows a ds_read_b128 lane group touches then
 // fall on 8 chunk positions x 2 row parities = all 64 banks.
-constexpr int GBK = 64;  // split-K slices of the direct-to-LDS kernel are multiples of this many bf16 elements
+// (GEMM_GBK, spv_gemm_core.h: split-K slices of this kernel are multiples of that many bf16 elements)
 
 // KB = bytes of K per tile row per stage: 128 (64 bf16, 2 x 32 KiB stages, 2 workgroups per CU: long-K problems) or
 // 64 (32 bf16, 2 x 16 KiB stages, 4 workgroups per CU: the skinny K = 512..768 layer GEMMs, which are bound by load
@@ -820,41 +825,8 @@ __global__ __launch_bounds__(512) void gemm_nt_strip_kernel(const bf16_t* __rest
     }
 }
 
-// the uneven shares of the strip kernel: `groups` row groups of base (+1 for the first rem) 32-row blocks; picks the
-// wave-row height MB whose sub-tiles (2 MB or 2 MB + 1 blocks) cover base and base + 1 without padding
-// CUs the strip kernel leaves alone (spv_set_reserved_cus): a strip workgroup needs a whole CU (2 x 256 VGPRs per SIMD, 155 KiB of
-// LDS), so on a CU that holds a resident RCCL channel it cannot start and would run as a second dispatch round.  16 reserved CUs cost
-// nothing at the layer shapes (the largest share stays 9 / 13 row blocks).
+// CUs the strip kernel leaves alone (spv_set_reserved_cus); strip_plan (spv_gemm_core.h) deals the row blocks over the rest
 static int g_reserved_cus = 0;
-
-inline bool strip_plan(int M, int N, int K, int& MB, int& nstrips, int& groups, int& base, int& rem) {
-    if (N % 256 != 0 || N > 16384 || K % 128 != 0 || K < 128 || M < 8192) return false;   // (Base width: the MHPermutMix data gradient has N = 9216)
-    nstrips = N / 256;
-    const int nblk = cdiv(M, 32);
-    groups = (256 - g_reserved_cus) / nstrips;
-    if (groups < 1) return false;
-    if (groups > nblk) groups = nblk;
-    base = nblk / groups;
-    rem = nblk % groups;
-    auto padded = [&](int mb, int c) {  // MFMA block slots a run of c blocks occupies
-        int slots = 0;
-        while (c > 0) {
-            const int take = (c % (2 * mb) != 0 && c >= 2 * mb + 1) ? 2 * mb + 1 : std::min(2 * mb, c);
-            slots += take >= 2 * mb ? take : 2 * mb;
-            c -= take;
-        }
-        return slots;
-    };
-    int best = 0, best_slots = 1 << 30;
-    const int worst = base + (rem ? 1 : 0);
-    for (int mb = 4; mb >= 2; --mb) {
-        const int s = padded(mb, worst);
-        if (s < best_slots) { best_slots = s; best = mb; }
-    }
-    if (best == 0 || best_slots * 100 > worst * 115) return false;  // more than 15 % padding: the 128 x 128 kernels do better
-    MB = best;
-    return true;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // Few-rows NT GEMM (M <= 2048: the CLS-only last layer's feed-forward half, 512 rows): C[M,N] (+)= A[M,K] . B[N,K]^T (+ bias).
@@ -938,7 +910,7 @@ __global__ __launch_bounds__(256) void gemm_nt_rows_kernel(const bf16_t* __restr
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef unsigned tn_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int TROWB = 256 + 64;  // LDS bytes per k row (128 bf16 + pad)
-constexpr int TBK = 64;          // k rows per stage (16 MFMAs per wave between barriers)
+constexpr int TBK = GEMM_TBK;    // k rows per stage (16 MFMAs per wave between barriers)
 
 __device__ __forceinline__ bf16x8 tr_frag(const unsigned char* base) {
     // base: this lane's address for rows k0..k0+3; the second read covers rows k0+4..k0+7
@@ -1113,7 +1085,7 @@ __global__ __launch_bounds__(256) void gemm_tn_kernel(const bf16_t* __restrict__
 // alone each needs ~21 K-slices to fill the chip (a 25-K-tile loop per workgroup, 33 MB of partial sums written and re-read);
 // eight of them together fill it with 5 slices of 104 K-tiles.  Isolated: 8 x 53 us -> 307 us (emulated as one 768 x 4096 x 33280
 // problem).  Only for gradients nobody reads before the backward pass ends (hip_ops._held_wgrads).
-constexpr int TNB_MAX = 8;
+constexpr int TNB_MAX = GEMM_TNB_MAX;
 struct TnBatch {
     int nprob;
     int nlong;                    // problems [0, nlong) reduce over the call's K rows in nsplit slices; the rest over their own (fewer) rows, unsplit
@@ -1169,7 +1141,7 @@ __global__ __launch_bounds__(256) void gemm_tn_batch_kernel(TnBatch tb, float* _
 // encoder layers (768 x 512 x 33 280) are bound by the L2 -> LDS path, not by MFMA issue: a 128 x 128 tile moves 32 KiB per
 // 2.1 MFLOP K-tile (400 MB per launch through a path that sustains ~14 TB/s chip-wide), the 256 x 128 tile 48 KiB per 4.2 MFLOP
 // (300 MB) at the same number of split-K slabs (12 tiles x 21 slices = one workgroup per CU).
-constexpr int TWM = 256;              // tile rows (m)
+constexpr int TWM = GEMM_TWM;         // tile rows (m)
 constexpr int TWROWA = TWM * 2 + 64;  // LDS bytes per k row of the A tile: 576 = 64 mod 256, the four k rows of a read group land in disjoint banks
 
 template <typename TO>
@@ -1335,8 +1307,8 @@ __global__ __launch_bounds__(512) void gemm_tn_wide_kernel(const bf16_t* __restr
 // MHPermutMix linear's [512, 8192, 33 280] --, where the 128 x 128 kernel's four row tiles of a column block are four workgroups that
 // each stream the same 8.5 MB panel of the gathered matrix and drift apart by more K-tiles than the L2 holds (PMC: 1.47 GB fetched per
 // launch against 0.58 GB of operands: the kernel ran at 4.2 TB/s of HBM).  Here ONE workgroup owns all of M: the panel is read once.
-constexpr int TTM = 512;
-constexpr int TTK = 32;
+constexpr int TTM = GEMM_TTM;
+constexpr int TTK = GEMM_TTK;
 constexpr int TTROWA = TTM * 2 + 64;   // 1088 = 64 mod 256: the four k rows of a transposing read land in disjoint banks
 constexpr int TT_SMEM = 2 * (TTK * TTROWA + TTK * TROWB);   // 90 112 B (>= the epilogue's 8 x 9 216 B)
 template <typename TO>
@@ -1539,7 +1511,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // between two large kernels costs the step ~20 us (eight per-layer fold launches removed: 157 us), so folds travel with launches that
 // happen anyway.  (Keeping the split-K SUMS back until the end of the backward as well was measured and dropped: 2.09 -> 2.23 ms --
 // eight 33 MB workspaces outlive their stay in the 256 MB MALL and the late sum reads them from HBM.)
-constexpr int FJ_MAX = 16;
+constexpr int FJ_MAX = GEMM_FJ_MAX;
+static_assert(GEMM_FOLD_THREADS == FOLD_COLS * FOLD_ROWS, "spv_gemm_core.h sizes the batched reduce by the fold workgroup");
 struct FoldJobs {
     int njobs;
     int first_block[FJ_MAX + 1];
@@ -1591,96 +1564,77 @@ __global__ __launch_bounds__(FOLD_COLS * FOLD_ROWS) void splitk_reduce_batch_ker
     }
 }
 
-inline int kend_len(int K, int k_per_split) { return K < k_per_split ? K : k_per_split; }
-
 // dropout of the grouped-rows epilogue (spv_gemm_nt_grouped_rows_drop sets them around its call; 0 everywhere else)
 static thread_local float t_drop_p = 0.0f;
 static thread_local uint64_t t_drop_seed = 0;
 
+inline int ptr_lo(const void* p) { return p == nullptr ? -1 : (int)(reinterpret_cast<uintptr_t>(p) & 15); }
+
+// launches what gemm_nt_plan (spv_gemm_core.h) named for this call; T / TO are the call's element types
 template <typename T, typename TO>
-int launch_gemm(const void* A, const void* B, const float* bias, void* C, int M, int N, int K, int lda, int ldb,
-                int ldc, int accumulate, int splits, void* workspace, hipStream_t st, int rg = 0, int gs = 0, int roff = 0,
-                const float* bias2d = nullptr, const void* bc = nullptr, int bc_pw = 0, int bc_bf = 0) {
-    constexpr int BK = KT<T>::BK;
+int launch_gemm(const GemmNtPlan& pl, const void* A, const void* B, const float* bias, void* C, int M, int N, int K, int lda, int ldb,
+                int ldc, int accumulate, void* workspace, hipStream_t st, int rg, int gs, int roff, const float* bias2d, const void* bc,
+                int bc_pw, int bc_bf) {
     const int tiles_m = cdiv(M, BM), tiles_n = cdiv(N, BN);
-    int k_per_split = K;
-    if (splits > 1) {
-        k_per_split = cdiv(cdiv(K, splits), BK) * BK;
-        splits = cdiv(K, k_per_split);
-    }
+    const int splits = pl.splits, k_per_split = pl.k_per_split;
     float* ws = splits > 1 ? static_cast<float*>(workspace) : nullptr;
-    dim3 grid(tiles_m * tiles_n * splits);
-    if constexpr (sizeof(T) == 2) {
-        // few rows: one 32 x 32 tile per workgroup straight from the L2-resident operands (no split-K workspace, no reduce launch)
-        // (K <= 1536: a wave walks its K share in batches of 8 k-steps, one L2 round trip each -- at K = 8192 that chain is 40 us against
-        // 15 + 5 for split-K + reduce; <= 1024 tiles: beyond that the 32 x 32 tiles re-read the operands 4x as often as 128 x 128 ones)
-        if (splits == 1 && M <= 2048 && K <= 1536 && rg == 0 && bias2d == nullptr && bc == nullptr && t_drop_p == 0.0f && K % 16 == 0 &&
-            lda % 8 == 0 && ldb % 8 == 0 && ((reinterpret_cast<uintptr_t>(A) | reinterpret_cast<uintptr_t>(B)) & 15) == 0 &&
-            cdiv(M, 32) * cdiv(N, 32) >= 64 && cdiv(M, 32) * cdiv(N, 32) <= 1024) {
-            const int tn32 = cdiv(N, 32);
-            hipLaunchKernelGGL((gemm_nt_rows_kernel<TO>), dim3(cdiv(M, 32) * tn32), dim3(256), 0, st, static_cast<const bf16_t*>(A),
-                               static_cast<const bf16_t*>(B), bias, static_cast<TO*>(C), M, N, K, lda, ldb, ldc, accumulate, tn32);
+    const dim3 grid(pl.grid);
+    switch (pl.kernel) {
+    case GEMM_NT_ROWS:
+        if constexpr (sizeof(T) == 2) {
+            hipLaunchKernelGGL((gemm_nt_rows_kernel<TO>), grid, dim3(256), 0, st, static_cast<const bf16_t*>(A), static_cast<const bf16_t*>(B), bias,
+                               static_cast<TO*>(C), M, N, K, lda, ldb, ldc, accumulate, cdiv(N, 32));
             SPV_LAUNCH_CHECK("spv_gemm_nt(rows)");
             SPV_COUNT_PATH(SPV_PATH_GEMM_ROWS);
             return 0;
         }
-    }
-    if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) {
-        int mb, nstrips, groups, base, rem;
-        const bool bc_ok = bc == nullptr || (bc_bf && !accumulate && bc_pw >= 8 && N % bc_pw == 0);   // (8 columns span <= 2 windows)
-        const bool span32 = (size_t)M * lda * 2 < (1ull << 32) && (size_t)N * ldb * 2 < (1ull << 32);  // 32-bit DMA source offsets
-        if (splits == 1 && rg == 0 && bias2d == nullptr && t_drop_p == 0.0f && bc_ok && span32 && ldc % 8 == 0 && (reinterpret_cast<uintptr_t>(C) & 15) == 0 &&
-            (bias == nullptr || (reinterpret_cast<uintptr_t>(bias) & 3) == 0) && strip_plan(M, N, K, mb, nstrips, groups, base, rem)) {
-            const int nwg = groups * nstrips;
+        return spv_set_error("spv_gemm_nt: the rows kernel takes bf16 operands");
+    case GEMM_NT_STRIP:
+        if constexpr (sizeof(T) == 2 && sizeof(TO) == 2) {
+            const int nwg = pl.grid;
 #define SPV_STRIP(MBV, EPIV)                                                                                                \
     hipLaunchKernelGGL((gemm_nt_strip_kernel<MBV, EPIV>), dim3(nwg), dim3(512), 0, st, static_cast<const bf16_t*>(A),       \
-                       static_cast<const bf16_t*>(B), bias, static_cast<bf16_t*>(C), M, K, lda, ldb, ldc, nstrips, base, rem, nwg, \
+                       static_cast<const bf16_t*>(B), bias, static_cast<bf16_t*>(C), M, K, lda, ldb, ldc, pl.nstrips, pl.base, pl.rem, nwg, \
                        static_cast<const bf16_t*>(bc), bc_pw, bc ? N / bc_pw : 0)
-            SPV_COUNT_PATH(bc != nullptr ? SPV_PATH_GEMM_STRIP_POOL : accumulate ? SPV_PATH_GEMM_STRIP_ACC : SPV_PATH_GEMM_STRIP);
-            if (bc != nullptr && bc_pw % 8 != 0) {   // two-window epilogue: its own instantiation (in the one-window kernel it cost 6 %)
-                if (mb == 4) SPV_STRIP(4, 3);
-                else if (mb == 3) SPV_STRIP(3, 3);
-                else SPV_STRIP(2, 3);
-            } else if (bc != nullptr) {
-                if (mb == 4) SPV_STRIP(4, 2);
-                else if (mb == 3) SPV_STRIP(3, 2);
-                else SPV_STRIP(2, 2);
-            } else if (accumulate) {
-                if (mb == 4) SPV_STRIP(4, 1);
-                else if (mb == 3) SPV_STRIP(3, 1);
-                else SPV_STRIP(2, 1);
-            } else {
-                if (mb == 4) SPV_STRIP(4, 0);
-                else if (mb == 3) SPV_STRIP(3, 0);
-                else SPV_STRIP(2, 0);
+#define SPV_STRIP_MB(EPIV)                  \
+    do {                                    \
+        if (pl.mb == 4) SPV_STRIP(4, EPIV); \
+        else if (pl.mb == 3) SPV_STRIP(3, EPIV); \
+        else SPV_STRIP(2, EPIV);            \
+    } while (0)
+            SPV_COUNT_PATH(pl.epi >= 2 ? SPV_PATH_GEMM_STRIP_POOL : pl.epi == 1 ? SPV_PATH_GEMM_STRIP_ACC : SPV_PATH_GEMM_STRIP);
+            switch (pl.epi) {
+            case 3: SPV_STRIP_MB(3); break;
+            case 2: SPV_STRIP_MB(2); break;
+            case 1: SPV_STRIP_MB(1); break;
+            default: SPV_STRIP_MB(0); break;
             }
+#undef SPV_STRIP_MB
 #undef SPV_STRIP
             SPV_LAUNCH_CHECK("spv_gemm_nt(strip)");
             return 0;
         }
-    }
-    if constexpr (sizeof(T) == 2) {
-        // direct-to-LDS double-buffered kernel for long reductions (measured: 896 vs 795 TFLOP/s at 4096^3, 755 vs 700 on
-        // the 512 x 8192 x 33280 weight gradient); the skinny K <= 1024 layer GEMMs are faster on the register-staged
-        // kernel (42 vs 50 us at 33280 x 768 x 512: three workgroups per CU instead of two)
-        // K <= 1024 (the layer GEMMs) stays on the register-staged kernel: the three-stage 64-byte-row ring measures the
-        // same step time (2.978 vs 2.972 ms over three alternating runs) and 4 us more per isolated launch
-        if (K % GBK == 0 && k_per_split % GBK == 0 && kend_len(K, k_per_split) > 1024) {
+        return spv_set_error("spv_gemm_nt: the strip kernel takes bf16 operands and a bf16 output");
+    case GEMM_NT_GLDS:
+        if constexpr (sizeof(T) == 2) {
             hipLaunchKernelGGL((gemm_nt_glds_kernel<TO, 128, 2>), grid, dim3(256), 0, st, static_cast<const bf16_t*>(A),
                                static_cast<const bf16_t*>(B), bias, static_cast<TO*>(C), ws, M, N, K, lda, ldb, ldc, k_per_split,
                                accumulate, tiles_n, tiles_m * tiles_n, splits, rg, gs, roff, bias2d, bc, bc_pw, bc_bf, t_drop_p, t_drop_seed);
             SPV_LAUNCH_CHECK("spv_gemm_nt(glds)");
-            goto reduce;
+            break;
         }
+        return spv_set_error("spv_gemm_nt: the direct-to-LDS kernel takes bf16 operands");
+    case GEMM_NT_TILE:
+        hipLaunchKernelGGL((gemm_nt_kernel<T, TO>), grid, dim3(256), 0, st, static_cast<const T*>(A),
+                           static_cast<const T*>(B), bias, static_cast<TO*>(C), ws, M, N, K, lda, ldb, ldc, k_per_split,
+                           accumulate, tiles_n, tiles_m * tiles_n, splits, rg, gs, roff, bias2d, bc, bc_pw, bc_bf, t_drop_p, t_drop_seed);
+        SPV_LAUNCH_CHECK("spv_gemm_nt");
+        break;
+    default:
+        return spv_set_error("spv_gemm_nt: no kernel for plan %d", (int)pl.kernel);
     }
-    hipLaunchKernelGGL((gemm_nt_kernel<T, TO>), grid, dim3(256), 0, st, static_cast<const T*>(A),
-                       static_cast<const T*>(B), bias, static_cast<TO*>(C), ws, M, N, K, lda, ldb, ldc, k_per_split,
-                       accumulate, tiles_n, tiles_m * tiles_n, splits, rg, gs, roff, bias2d, bc, bc_pw, bc_bf, t_drop_p, t_drop_seed);
-    SPV_LAUNCH_CHECK("spv_gemm_nt");
-reduce:
-    if (splits > 1) {
-        int blocks = (int)std::min<int64_t>(((int64_t)M * N / ((N & 3) == 0 ? 4 : 1) + 255) / 256, 2048);
-        hipLaunchKernelGGL((splitk_reduce_kernel<TO>), dim3(blocks), dim3(256), 0, st, ws, bias, static_cast<TO*>(C), M,
+    if (pl.reduce) {
+        hipLaunchKernelGGL((splitk_reduce_kernel<TO>), dim3(pl.reduce_blocks), dim3(256), 0, st, ws, bias, static_cast<TO*>(C), M,
                            N, ldc, splits, accumulate);
         SPV_LAUNCH_CHECK("spv_gemm_nt(split-k reduce)");
     }
@@ -1743,25 +1697,26 @@ int spv_seed_ptr_set_gemm(const unsigned long long* p) { return spv_seed_symbol_
 static int gemm_entry(const void* A, const void* B, const float* bias, void* C, int M, int N, int K, int lda, int ldb, int ldc,
                       int in_dtype, int out_dtype, int accumulate, int splits, void* workspace, void* stream, int rg, int gs,
                       int roff, const float* bias2d, const void* bc, int bc_pw, int bc_bf) {
-    SPV_CHECK(M > 0 && N > 0 && K > 0, "spv_gemm_nt: empty problem M=%d N=%d K=%d", M, N, K);
-    SPV_CHECK(in_dtype == SPV_F32 || in_dtype == SPV_BF16, "spv_gemm_nt: bad in_dtype %d", in_dtype);
-    SPV_CHECK(out_dtype == SPV_F32 || out_dtype == SPV_BF16, "spv_gemm_nt: bad out_dtype %d", out_dtype);
-    const int ch = in_dtype == SPV_BF16 ? 8 : 4;
-    SPV_CHECK(K % ch == 0 && lda % ch == 0 && ldb % ch == 0,
-              "spv_gemm_nt: K=%d lda=%d ldb=%d must be multiples of %d elements (16 bytes)", K, lda, ldb, ch);
-    SPV_CHECK(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0, "spv_gemm_nt: A/B must be 16-byte aligned");
-    SPV_CHECK(lda >= K && ldb >= K && ldc >= N, "spv_gemm_nt: leading dimension too small");
-    SPV_CHECK(splits >= 1, "spv_gemm_nt: splits=%d", splits);
-    SPV_CHECK(splits == 1 || workspace != nullptr, "spv_gemm_nt: split-K needs a workspace");
+    const GemmNtCall call{in_dtype, out_dtype, M, N, K, lda, ldb, ldc, ptr_lo(A), ptr_lo(B), ptr_lo(C), ptr_lo(bias), accumulate, splits, ptr_lo(workspace),
+                          rg, ptr_lo(bias2d), bc != nullptr, bc_pw, bc_bf, t_drop_p > 0.0f, g_reserved_cus};
+    const GemmNtPlan pl = gemm_nt_plan(call);
+    SPV_CHECK(pl.kernel != GEMM_NT_REFUSE_EMPTY, "spv_gemm_nt: empty problem M=%d N=%d K=%d", M, N, K);
+    SPV_CHECK(pl.kernel != GEMM_NT_REFUSE_DTYPE, "spv_gemm_nt: bad in_dtype %d or out_dtype %d", in_dtype, out_dtype);
+    SPV_CHECK(pl.kernel != GEMM_NT_REFUSE_CHUNK, "spv_gemm_nt: K=%d lda=%d ldb=%d must be multiples of %d elements (16 bytes)", K, lda, ldb,
+              in_dtype == SPV_BF16 ? 8 : 4);
+    SPV_CHECK(pl.kernel != GEMM_NT_REFUSE_ALIGN, "spv_gemm_nt: A/B must be 16-byte aligned");
+    SPV_CHECK(pl.kernel != GEMM_NT_REFUSE_LD, "spv_gemm_nt: leading dimension too small");
+    SPV_CHECK(pl.kernel != GEMM_NT_REFUSE_SPLITS, "spv_gemm_nt: splits=%d", splits);
+    SPV_CHECK(pl.kernel != GEMM_NT_REFUSE_WORKSPACE, "spv_gemm_nt: split-K needs a 16-byte aligned workspace");
     hipStream_t st = static_cast<hipStream_t>(stream);
     if (in_dtype == SPV_BF16) {
         if (out_dtype == SPV_BF16)
-            return launch_gemm<bf16_t, bf16_t>(A, B, bias, C, M, N, K, lda, ldb, ldc, accumulate, splits, workspace, st, rg, gs, roff, bias2d, bc, bc_pw, bc_bf);
-        return launch_gemm<bf16_t, float>(A, B, bias, C, M, N, K, lda, ldb, ldc, accumulate, splits, workspace, st, rg, gs, roff, bias2d, bc, bc_pw, bc_bf);
+            return launch_gemm<bf16_t, bf16_t>(pl, A, B, bias, C, M, N, K, lda, ldb, ldc, accumulate, workspace, st, rg, gs, roff, bias2d, bc, bc_pw, bc_bf);
+        return launch_gemm<bf16_t, float>(pl, A, B, bias, C, M, N, K, lda, ldb, ldc, accumulate, workspace, st, rg, gs, roff, bias2d, bc, bc_pw, bc_bf);
     }
     if (out_dtype == SPV_BF16)
-        return launch_gemm<float, bf16_t>(A, B, bias, C, M, N, K, lda, ldb, ldc, accumulate, splits, workspace, st, rg, gs, roff, bias2d, bc, bc_pw, bc_bf);
-    return launch_gemm<float, float>(A, B, bias, C, M, N, K, lda, ldb, ldc, accumulate, splits, workspace, st, rg, gs, roff, bias2d, bc, bc_pw, bc_bf);
+        return launch_gemm<float, bf16_t>(pl, A, B, bias, C, M, N, K, lda, ldb, ldc, accumulate, workspace, st, rg, gs, roff, bias2d, bc, bc_pw, bc_bf);
+    return launch_gemm<float, float>(pl, A, B, bias, C, M, N, K, lda, ldb, ldc, accumulate, workspace, st, rg, gs, roff, bias2d, bc, bc_pw, bc_bf);
 }
 
 static int fill_fold_jobs(const spv_fold_job* folds, int nfolds, FoldJobs& fj, int& blocks) {
@@ -1782,100 +1737,102 @@ static int fill_fold_jobs(const spv_fold_job* folds, int nfolds, FoldJobs& fj, i
     return 0;
 }
 
+// fold jobs -> FoldJobs and its workgroup count; -1 for a count outside 0..FJ_MAX or a bad job (nothing is launched then)
+static int fold_blocks_of(const spv_fold_job* folds, int nfolds, FoldJobs& fj) {
+    int blocks = 0;
+    if (!(nfolds >= 0 && nfolds <= FJ_MAX && (nfolds == 0 || folds != nullptr))) return -1;
+    return fill_fold_jobs(folds, nfolds, fj, blocks) == 0 ? blocks : -1;
+}
+
 static int gemm_tn_impl(const void* A, const void* B, void* C, int M, int N, int K, int lda, int ldb, int ldc, int out_dtype,
                         int accumulate, int splits, void* workspace, void* stream, const spv_fold_job* folds, int nfolds) {
+    FoldJobs fj{};
+    const int fold_blocks = fold_blocks_of(folds, nfolds, fj);
+    const GemmTnPlan pl = gemm_tn_plan(out_dtype, M, N, K, lda, ldb, ldc, ptr_lo(A), ptr_lo(B), splits, ptr_lo(workspace), fold_blocks);
+    SPV_CHECK(pl.kernel != GEMM_TN_REFUSE_EMPTY, "spv_gemm_tn: empty problem M=%d N=%d K=%d", M, N, K);
+    SPV_CHECK(pl.kernel != GEMM_TN_REFUSE_DTYPE, "spv_gemm_tn: bad out_dtype %d", out_dtype);
+    SPV_CHECK(pl.kernel != GEMM_TN_REFUSE_CHUNK, "spv_gemm_tn: M=%d N=%d lda=%d ldb=%d must be multiples of 8 (bf16, 16-byte chunks)", M, N, lda, ldb);
+    SPV_CHECK(pl.kernel != GEMM_TN_REFUSE_ALIGN, "spv_gemm_tn: A/B must be 16-byte aligned");
+    SPV_CHECK(pl.kernel != GEMM_TN_REFUSE_LD, "spv_gemm_tn: leading dimension too small");
+    SPV_CHECK(pl.kernel != GEMM_TN_REFUSE_WORKSPACE, "spv_gemm_tn: split-K needs a 16-byte aligned workspace (splits=%d)", splits);
+    SPV_CHECK(pl.kernel != GEMM_TN_REFUSE_FOLDS, "spv_gemm_tn_fold: 0..%d fold jobs, each with partials, parts > 0, nsum 1..5, n > 0 and out[0]", FJ_MAX);
     SPV_COUNT_PATH(SPV_PATH_GEMM_TN);
-    SPV_CHECK(M > 0 && N > 0 && K > 0, "spv_gemm_tn: empty problem M=%d N=%d K=%d", M, N, K);
-    SPV_CHECK(out_dtype == SPV_F32 || out_dtype == SPV_BF16, "spv_gemm_tn: bad out_dtype %d", out_dtype);
-    SPV_CHECK(M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0,
-              "spv_gemm_tn: M=%d N=%d lda=%d ldb=%d must be multiples of 8 (bf16, 16-byte chunks)", M, N, lda, ldb);
-    SPV_CHECK(((uintptr_t)A & 15) == 0 && ((uintptr_t)B & 15) == 0, "spv_gemm_tn: A/B must be 16-byte aligned");
-    SPV_CHECK(lda >= M && ldb >= N && ldc >= N, "spv_gemm_tn: leading dimension too small");
-    SPV_CHECK(splits >= 1 && (splits == 1 || workspace != nullptr), "spv_gemm_tn: split-K needs a workspace");
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int tiles_m = cdiv(M, BM), tiles_n = cdiv(N, BN);
-    int k_per_split = K;
-    if (splits > 1) {
-        k_per_split = cdiv(cdiv(K, splits), TBK) * TBK;
-        splits = cdiv(K, k_per_split);
-    }
+    splits = pl.splits;
+    const int k_per_split = pl.k_per_split;
     float* ws = splits > 1 ? static_cast<float*>(workspace) : nullptr;
-    constexpr int wide_min = 4;   // fewest split-K slabs that pay for the 256 x 128 tile (see below)
-    if (M == TTM && N % BN == 0 && N >= 8 * BN && tiles_n * splits >= 192 && k_per_split >= 16 * TTK) {
-        // all of M in one workgroup: the B panel (the gathered matrix of the MHPermutMix gradient) is read once
-        const int nwg = tiles_n * splits;
-        if (out_dtype == SPV_BF16) {
+    const dim3 grid(pl.grid);
+    const bool bf = out_dtype == SPV_BF16;
+    switch (pl.kernel) {
+    case GEMM_TN_TALL:
+        if (bf) {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_tall_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, TT_SMEM);
-            hipLaunchKernelGGL((gemm_tn_tall_kernel<bf16_t>), dim3(nwg), dim3(512), TT_SMEM, st, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, ws, M, N, K, lda, ldb,
+            hipLaunchKernelGGL((gemm_tn_tall_kernel<bf16_t>), grid, dim3(512), TT_SMEM, st, (const bf16_t*)A, (const bf16_t*)B, (bf16_t*)C, ws, M, N, K, lda, ldb,
                                ldc, k_per_split, accumulate, tiles_n, tiles_n, splits);
         } else {
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_tall_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, TT_SMEM);
-            hipLaunchKernelGGL((gemm_tn_tall_kernel<float>), dim3(nwg), dim3(512), TT_SMEM, st, (const bf16_t*)A, (const bf16_t*)B, (float*)C, ws, M, N, K, lda, ldb,
+            hipLaunchKernelGGL((gemm_tn_tall_kernel<float>), grid, dim3(512), TT_SMEM, st, (const bf16_t*)A, (const bf16_t*)B, (float*)C, ws, M, N, K, lda, ldb,
                                ldc, k_per_split, accumulate, tiles_n, tiles_n, splits);
         }
         SPV_LAUNCH_CHECK("spv_gemm_tn(tall)");
-    } else if (splits >= wide_min && M % TWM == 0 && N % BN == 0 && (M / TWM) * tiles_n * splits >= 128) {
-        // the 256 x 128 tile (8 waves, one workgroup per CU): the split-K layer weight gradients.  Measured in graph mode, alternating,
-        // against the 128 x 128 kernel: 2.372 vs 2.385 ms/step -- 1.6 us per launch; without split-K (the MHPermutMix weight gradient,
-        // 512 x 8192 x 33 280) it is SLOWER (651 vs 510 us), hence splits >= 4
+        break;
+    case GEMM_TN_WIDE: {
         const int wt = (M / TWM) * tiles_n;
 #define SPV_TNW(TOV)                                                                                                                      \
     do {                                                                                                                                  \
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_wide_kernel<TOV>), hipFuncAttributeMaxDynamicSharedMemorySize, TW_SMEM_DB); \
-        hipLaunchKernelGGL((gemm_tn_wide_kernel<TOV>), dim3(wt * splits), dim3(512), TW_SMEM_DB, st, (const bf16_t*)A, (const bf16_t*)B, (TOV*)C, \
+        hipLaunchKernelGGL((gemm_tn_wide_kernel<TOV>), grid, dim3(512), TW_SMEM_DB, st, (const bf16_t*)A, (const bf16_t*)B, (TOV*)C,     \
                            ws, M, N, K, lda, ldb, ldc, k_per_split, accumulate, tiles_n, wt, splits);                                     \
     } while (0)
-        if (out_dtype == SPV_BF16) SPV_TNW(bf16_t);
+        if (bf) SPV_TNW(bf16_t);
         else SPV_TNW(float);
 #undef SPV_TNW
         SPV_LAUNCH_CHECK("spv_gemm_tn(wide)");
         SPV_COUNT_PATH(SPV_PATH_GEMM_TN_WIDE);
-    } else {
-        dim3 grid(tiles_m * tiles_n * splits);
-        // One K-tile in flight (144 VGPRs, 40 KB of LDS) for the sliver-shaped gradient of the patch embedding (512 x 48 x 33 280): that
-        // launch runs on the main stream BESIDE the batched layer gradients, whose workgroups (8 waves x 184 VGPRs, 112 KB) leave exactly
-        // 144 VGPRs per SIMD and 45 KB per CU -- with three tiles in flight (216 VGPRs) its workgroups waited for those CUs to drain.
-        const int depth = N <= 64 ? 1 : 3;
+        break;
+    }
+    case GEMM_TN_TILE1:
+    case GEMM_TN_TILE3:
 #define SPV_TN(TOV, DV)                                                                                                     \
     hipLaunchKernelGGL((gemm_tn_kernel<TOV, DV>), grid, dim3(256), 0, st, (const bf16_t*)A, (const bf16_t*)B, (TOV*)C, ws, M, N, K, \
                        lda, ldb, ldc, k_per_split, accumulate, tiles_n, tiles_m * tiles_n, splits)
-        if (out_dtype == SPV_BF16) {
-            if (depth == 1) SPV_TN(bf16_t, 1); else SPV_TN(bf16_t, 3);
+        if (bf) {
+            if (pl.kernel == GEMM_TN_TILE1) SPV_TN(bf16_t, 1); else SPV_TN(bf16_t, 3);
         } else {
-            if (depth == 1) SPV_TN(float, 1); else SPV_TN(float, 3);
+            if (pl.kernel == GEMM_TN_TILE1) SPV_TN(float, 1); else SPV_TN(float, 3);
         }
 #undef SPV_TN
         SPV_LAUNCH_CHECK("spv_gemm_tn");
+        break;
+    default:
+        return spv_set_error("spv_gemm_tn: no kernel for plan %d", (int)pl.kernel);
     }
-    FoldJobs fj{};
-    int fold_blocks = 0;
-    SPV_CHECK(nfolds >= 0 && nfolds <= FJ_MAX && (nfolds == 0 || folds != nullptr), "spv_gemm_tn_fold: 0..%d fold jobs", FJ_MAX);
-    SPV_CHECK(fill_fold_jobs(folds, nfolds, fj, fold_blocks) == 0, "spv_gemm_tn_fold: bad fold job");
-    if (splits > 1) {
-        if (fold_blocks > 0) {
-            constexpr int RT1 = FOLD_COLS * FOLD_ROWS;
-            const int blocks = (int)std::min<int64_t>(((int64_t)M * N / ((N & 3) == 0 ? 4 : 1) + 255) / 256, 2048);
-            if (out_dtype == SPV_BF16)
-                hipLaunchKernelGGL((splitk_reduce_fold_kernel<bf16_t>), dim3(blocks + fold_blocks), dim3(RT1), 0, st, ws, (bf16_t*)C, M, N, ldc, splits,
-                                   accumulate, blocks, fj);
-            else
-                hipLaunchKernelGGL((splitk_reduce_fold_kernel<float>), dim3(blocks + fold_blocks), dim3(RT1), 0, st, ws, (float*)C, M, N, ldc, splits,
-                                   accumulate, blocks, fj);
-            SPV_LAUNCH_CHECK("spv_gemm_tn_fold(split-k reduce + fold)");
-            return 0;
-        }
-        int blocks = (int)std::min<int64_t>(((int64_t)M * N / ((N & 3) == 0 ? 4 : 1) + 255) / 256, 2048);
-        if (out_dtype == SPV_BF16)
-            hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3(blocks), dim3(256), 0, st, ws, (const float*)nullptr, (bf16_t*)C, M, N,
+    switch (pl.reduce) {
+    case GEMM_TN_REDUCE_FOLDS:
+        if (bf)
+            hipLaunchKernelGGL((splitk_reduce_fold_kernel<bf16_t>), dim3(pl.reduce_blocks + fold_blocks), dim3(FOLD_COLS * FOLD_ROWS), 0, st, ws, (bf16_t*)C, M, N,
+                               ldc, splits, accumulate, pl.reduce_blocks, fj);
+        else
+            hipLaunchKernelGGL((splitk_reduce_fold_kernel<float>), dim3(pl.reduce_blocks + fold_blocks), dim3(FOLD_COLS * FOLD_ROWS), 0, st, ws, (float*)C, M, N,
+                               ldc, splits, accumulate, pl.reduce_blocks, fj);
+        SPV_LAUNCH_CHECK("spv_gemm_tn_fold(split-k reduce + fold)");
+        break;
+    case GEMM_TN_REDUCE_PLAIN:
+        if (bf)
+            hipLaunchKernelGGL((splitk_reduce_kernel<bf16_t>), dim3(pl.reduce_blocks), dim3(256), 0, st, ws, (const float*)nullptr, (bf16_t*)C, M, N,
                                ldc, splits, accumulate);
         else
-            hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3(blocks), dim3(256), 0, st, ws, (const float*)nullptr, (float*)C, M, N, ldc,
+            hipLaunchKernelGGL((splitk_reduce_kernel<float>), dim3(pl.reduce_blocks), dim3(256), 0, st, ws, (const float*)nullptr, (float*)C, M, N, ldc,
                                splits, accumulate);
         SPV_LAUNCH_CHECK("spv_gemm_tn(split-k reduce)");
-    }
-    if (fold_blocks > 0 && splits <= 1) {   // no reduce to ride on: the fold runs by itself
+        break;
+    case GEMM_TN_FOLD_ALONE:   // no reduce to ride on: the fold runs by itself
         hipLaunchKernelGGL(fold_multi_kernel, dim3(fold_blocks), dim3(FOLD_COLS * FOLD_ROWS / FOLD_NARROW), 0, st, fj);
         SPV_LAUNCH_CHECK("spv_gemm_tn_fold(fold)");
+        break;
+    case GEMM_TN_NO_REDUCE:
+        break;
     }
     return 0;
 }
@@ -1905,82 +1862,54 @@ extern "C" int spv_fold_multi(const spv_fold_job* folds, int nfolds, void* strea
 
 static int gemm_tn_batch_impl(const spv_tn_problem* probs, int nprob, int K, int splits, void* workspace, const spv_fold_job* folds,
                               int nfolds, void* stream, int parts) {
-    SPV_CHECK(probs != nullptr && nprob >= 1 && nprob <= TNB_MAX, "spv_gemm_tn_batch: 1..%d problems", TNB_MAX);
-    SPV_CHECK(K > 0 && splits >= 1 && workspace != nullptr, "spv_gemm_tn_batch: K=%d splits=%d need a workspace", K, splits);
-    SPV_CHECK(nfolds >= 0 && nfolds <= FJ_MAX && (nfolds == 0 || folds != nullptr), "spv_gemm_tn_batch: 0..%d fold jobs", FJ_MAX);
+    FoldJobs fj{};
+    const int fold_blocks = fold_blocks_of(folds, nfolds, fj);
+    GemmTnBatchProblem qs[TNB_MAX];
+    const bool listed = probs != nullptr && nprob >= 1 && nprob <= TNB_MAX;   // (otherwise the call is refused without a look at probs[])
+    for (int i = 0; listed && i < nprob; ++i) {
+        const spv_tn_problem& q = probs[i];
+        qs[i] = {q.m, q.n, q.lda, q.ldb, q.ldc, q.k, ptr_lo(q.a), ptr_lo(q.b), q.a != nullptr && q.b != nullptr && q.c != nullptr};
+    }
+    const GemmTnBatchPlan pl = gemm_tn_batch_plan(listed ? qs : nullptr, nprob, K, splits, ptr_lo(workspace), fold_blocks);
+    SPV_CHECK(pl.kernel != GEMM_TNB_REFUSE_COUNT, "spv_gemm_tn_batch: 1..%d problems", TNB_MAX);
+    SPV_CHECK(pl.kernel != GEMM_TNB_REFUSE_CALL, "spv_gemm_tn_batch: K=%d splits=%d need a 16-byte aligned workspace", K, splits);
+    SPV_CHECK(pl.kernel != GEMM_TNB_REFUSE_FOLDS, "spv_gemm_tn_batch: 0..%d fold jobs, each with partials, parts > 0, nsum 1..5, n > 0 and out[0]", FJ_MAX);
+    SPV_CHECK(pl.kernel != GEMM_TNB_REFUSE_K, "spv_gemm_tn_batch: problem %d: k must be 0 (= K) or 1..K=%d", pl.bad, K);
+    SPV_CHECK(pl.kernel != GEMM_TNB_REFUSE_NO_LONG, "spv_gemm_tn_batch: no problem reduces over the call's K=%d rows", K);
+    SPV_CHECK(pl.kernel != GEMM_TNB_REFUSE_EMPTY, "spv_gemm_tn_batch: empty problem %d", pl.bad);
+    SPV_CHECK(pl.kernel != GEMM_TNB_REFUSE_SHAPE, "spv_gemm_tn_batch: problem %d: M, N, lda, ldb must be multiples of 8, leading dimensions >= extents", pl.bad);
+    SPV_CHECK(pl.kernel != GEMM_TNB_REFUSE_ALIGN, "spv_gemm_tn_batch: problem %d: A/B must be 16-byte aligned", pl.bad);
+    SPV_CHECK(pl.kernel != GEMM_TNB_REFUSE_SHORT_LDC, "spv_gemm_tn_batch: problem %d (short): ldc must be a multiple of 4", pl.bad);
+    // the long problems (k == 0 or k == K: the call's K rows, split-K) first, then the short ones (k < K: their own rows, unsplit, stored
+    // by the GEMM launch itself); pl.order[] maps the kernel's problem index to the caller's
     TnBatch tb{};
     tb.nprob = nprob;
-    int tiles = 0;
-    long long off = 0;
-    int k_per_split = cdiv(cdiv(K, splits), TBK) * TBK;
-    splits = cdiv(K, k_per_split);
-    int reduce_blocks = 1;
-    // the long problems (k == 0 or k == K: the call's K rows, split-K) first, then the short ones (k < K: their own rows, unsplit, stored
-    // by the GEMM launch itself); order[] maps the kernel's problem index to the caller's
-    int order[TNB_MAX], nlong = 0, no = 0;
+    tb.nlong = pl.nlong;
+    const bool wide = pl.kernel == GEMM_TNB_WIDE;
     for (int i = 0; i < nprob; ++i) {
-        SPV_CHECK(probs[i].k >= 0 && probs[i].k <= K, "spv_gemm_tn_batch: problem %d: k=%d must be 0 (= K) or 1..K=%d", i, probs[i].k, K);
-        if (probs[i].k == 0 || probs[i].k == K) order[no++] = i;
-    }
-    nlong = no;
-    for (int i = 0; i < nprob; ++i)
-        if (!(probs[i].k == 0 || probs[i].k == K)) order[no++] = i;
-    SPV_CHECK(nlong >= 1, "spv_gemm_tn_batch: no problem reduces over the call's K=%d rows", K);
-    tb.nlong = nlong;
-    int long_tiles = 0;
-    for (int i = 0; i < nprob; ++i) {
-        const spv_tn_problem& q = probs[order[i]];
-        SPV_CHECK(q.a != nullptr && q.b != nullptr && q.c != nullptr && q.m > 0 && q.n > 0, "spv_gemm_tn_batch: empty problem %d", order[i]);
-        SPV_CHECK(q.m % 8 == 0 && q.n % 8 == 0 && q.lda % 8 == 0 && q.ldb % 8 == 0 && q.lda >= q.m && q.ldb >= q.n && q.ldc >= q.n,
-                  "spv_gemm_tn_batch: problem %d: M=%d N=%d lda=%d ldb=%d ldc=%d (multiples of 8, leading dimensions >= extents)", order[i], q.m,
-                  q.n, q.lda, q.ldb, q.ldc);
-        SPV_CHECK(((uintptr_t)q.a & 15) == 0 && ((uintptr_t)q.b & 15) == 0, "spv_gemm_tn_batch: problem %d: A/B must be 16-byte aligned", order[i]);
-        SPV_CHECK(i < nlong || q.ldc % 4 == 0, "spv_gemm_tn_batch: problem %d (short): ldc=%d must be a multiple of 4", order[i], q.ldc);
-        tb.first_tile[i] = tiles;
-        tb.ws_off[i] = off;
+        const spv_tn_problem& q = probs[pl.order[i]];
+        tb.first_tile[i] = wide ? pl.wide_first_tile[i] : pl.first_tile[i];
+        tb.ws_off[i] = pl.ws_off[i];
         tb.p[i] = {static_cast<const bf16_t*>(q.a), static_cast<const bf16_t*>(q.b), static_cast<float*>(q.c), q.m, q.n, q.lda, q.ldb, q.ldc, cdiv(q.n, BN),
-                   i < nlong ? K : q.k};
-        tiles += cdiv(q.m, BM) * cdiv(q.n, BN);
-        if (i < nlong) {
-            long_tiles = tiles;
-            off += (long long)splits * q.m * q.n;
-            constexpr int RT = FOLD_COLS * FOLD_ROWS;
-            reduce_blocks = std::max(reduce_blocks, (int)std::min<int64_t>(((int64_t)q.m * q.n / ((q.n & 3) == 0 ? 4 : 1) + RT - 1) / RT, 2048));
-        }
+                   i < pl.nlong ? K : q.k};
     }
-    tb.first_tile[nprob] = tiles;
+    tb.first_tile[nprob] = wide ? pl.wide_first_tile[nprob] : pl.first_tile[nprob];
     hipStream_t st = static_cast<hipStream_t>(stream);
-    // the 256 x 128 tile when every problem divides into it and the K-slices are long enough to pay for its longer prologue
-    bool wide = k_per_split >= 8 * TBK;
-    for (int i = 0; i < nprob && wide; ++i) wide = probs[i].m % TWM == 0 && probs[i].n % BN == 0 && (probs[i].k == 0 || probs[i].k >= TBK);
     if (parts & 1) {
         SPV_COUNT_PATH(SPV_PATH_GEMM_TN);
         SPV_COUNT_PATH(SPV_PATH_GEMM_TN_BATCH);
         if (wide) {
-            TnBatch tw = tb;
-            int wt = 0, wlong = 0;
-            for (int i = 0; i < nprob; ++i) {
-                tw.first_tile[i] = wt;
-                wt += (tb.p[i].M / TWM) * tb.p[i].tiles_n;
-                if (i < nlong) wlong = wt;
-            }
-            tw.first_tile[nprob] = wt;
-            const int wgrid = wlong * splits + ((wt - wlong + 7) & ~7);
             (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&gemm_tn_batch_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, TW_SMEM_DB);
-            hipLaunchKernelGGL(gemm_tn_batch_wide_kernel, dim3(wgrid), dim3(512), TW_SMEM_DB, st, tw, static_cast<float*>(workspace), K, k_per_split, splits);
+            hipLaunchKernelGGL(gemm_tn_batch_wide_kernel, dim3(pl.grid), dim3(512), TW_SMEM_DB, st, tb, static_cast<float*>(workspace), K, pl.k_per_split, pl.splits);
             SPV_COUNT_PATH(SPV_PATH_GEMM_TN_WIDE);
         } else {
-            const int grid128 = long_tiles * splits + ((tiles - long_tiles + 7) & ~7);
-            hipLaunchKernelGGL(gemm_tn_batch_kernel<3>, dim3(grid128), dim3(256), 0, st, tb, static_cast<float*>(workspace), K, k_per_split, splits);
+            hipLaunchKernelGGL(gemm_tn_batch_kernel<3>, dim3(pl.grid), dim3(256), 0, st, tb, static_cast<float*>(workspace), K, pl.k_per_split, pl.splits);
         }
         SPV_LAUNCH_CHECK("spv_gemm_tn_batch");
     }
     if (parts & 2) {
-        FoldJobs fj{};
-        int fold_blocks = 0;
-        SPV_CHECK(fill_fold_jobs(folds, nfolds, fj, fold_blocks) == 0, "spv_gemm_tn_batch: bad fold job");
-        hipLaunchKernelGGL(splitk_reduce_batch_kernel, dim3(fold_blocks + nlong * reduce_blocks), dim3(FOLD_COLS * FOLD_ROWS), 0, st, tb,
-                           static_cast<const float*>(workspace), splits, reduce_blocks, fj);
+        hipLaunchKernelGGL(splitk_reduce_batch_kernel, dim3(fold_blocks + pl.nlong * pl.reduce_blocks), dim3(FOLD_COLS * FOLD_ROWS), 0, st, tb,
+                           static_cast<const float*>(workspace), pl.splits, pl.reduce_blocks, fj);
         SPV_LAUNCH_CHECK("spv_gemm_tn_batch(split-k reduce + fold)");
     }
     return 0;
