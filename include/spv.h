@@ -58,7 +58,7 @@ enum {
     SPV_PATH_TOKEN_UNPOOL = 19,  /* spv_token_pool_bwd */
     SPV_PATH_ATTN_ROW0_FWD = 20, /* spv_attention_row0_fwd (the attention mixer's CLS-only last layer) */
     SPV_PATH_ATTN_ROW0_BWD = 21, /* spv_attention_row0_bwd */
-    SPV_PATH_AUGMENT = 22,       /* spv_augment_u8 (one workgroup per image) or spv_augment_tiled_u8 (output tiles): one per call */
+    SPV_PATH_AUGMENT = 22,       /* spv_augment_u8 / spv_loader_fetch_augment (one workgroup per image) or spv_augment_tiled_u8 (output tiles): one per call */
     SPV_PATH_TEACHER_VIEW = 23,  /* spv_teacher_view_u8 (the distillation teacher's 224 view, one workgroup per image and row band) */
     SPV_PATH_ATTN_V1 = 24,       /* spv_attention_fwd / _bwd served by the general kernels (attn_*_kernel): one per call */
     SPV_PATH_ATTN_V2 = 25,       /* ... by the LDS-staged kernels (attn2_*_kernel; head dim 16 / 32 / 64) */
@@ -895,6 +895,29 @@ int64_t spv_loader_cursor_bytes(void);
 int spv_loader_fetch(const unsigned char* src_nhwc, const void* labels_src, void* cursor, int64_t* index, int64_t* labels, void* img,
                      const float* mean, const float* inv_std, int n, int batch, int chans, int height, int width, int world, int rank,
                      int steps_per_epoch, uint64_t seed, int shuffle, int mode, int label_dtype, void* stream);
+/* Fetch and augment in ONE launch: what spv_loader_fetch(SPV_LOADER_NONE) at the cursor's step t, spv_augment_params(step = t) and
+ * spv_augment_u8 do one after the other, bit for bit, with no by-value step -- so a captured launch fetches a new batch AND draws a new
+ * table at every replay (the by-value step of spv_augment_params would replay one step's table for ever).  One 256-thread workgroup
+ * per image (grid = batch).  Each reads t from the cursor block (the protocol above, groups = batch; the last workgroup to arrive
+ * stores t + 1), works the sample's row out with the order above under `loader_seed`, and writes, all at fixed addresses,
+ *   index[b], labels[b]   as spv_loader_fetch does;
+ *   params[b]             fp32 [batch][SPV_AUG_NPARAM], 16-byte aligned: the sample's table row, drawn with key (augment_seed, t, b)
+ *                         exactly as spv_augment_params draws it -- the step's table stays observable;
+ *   out_nchw[b]           fp32 [chans][height][width]: spv_augment_u8's chain on src_nhwc[index[b]] with that row.
+ * Inside the workgroup the row and the table pass from the threads that work them out to the others through LDS, never through
+ * `params`.  Two seeds: under data parallelism the ranks share the loader's seed (one permutation, disjoint parts) and differ in the
+ * augmentation's.  cfg is a HOST struct, read during the call.
+ * spv_loader_augment_supported: 1 when the kernel can stage the image -- spv_augment_supported's conditions with, on top of its two
+ * fp32 copies and reduction slots, 80 bytes of LDS for the step, the row and the table row, and sides <= 512 as the loader asks.  A
+ * shape that fills spv_augment_u8's 64 KiB exactly (1 x 89 x 92) is refused; 3 x 32 x 32, 1 x 28 x 28 and 3 x 5 x 7 fit.
+ * Refused on the host, before any launch: everything spv_loader_fetch refuses in its float mode (out_nchw as img), everything
+ * spv_augment_params refuses (null / misaligned params, null cfg, a probability or range outside its domain, sides < 2), a shape the
+ * predicate refuses, out_nchw not 4-byte aligned.  Counts ONE SPV_PATH_AUGMENT per call. */
+int spv_loader_augment_supported(int chans, int height, int width);
+int spv_loader_fetch_augment(const unsigned char* src_nhwc, const void* labels_src, void* cursor, int64_t* index, int64_t* labels,
+                             float* params, float* out_nchw, const float* mean, const float* inv_std, const spv_augment_cfg* cfg, int n,
+                             int batch, int chans, int height, int width, int world, int rank, int steps_per_epoch, uint64_t loader_seed,
+                             int shuffle, int label_dtype, uint64_t augment_seed, void* stream);
 
 #ifdef __cplusplus
 }

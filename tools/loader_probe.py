@@ -16,6 +16,16 @@ max - min spread over its blocks.  One JSON line.
     python tools/loader_probe.py [--blocks 3] [--steps 200] [--out FILE]
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/loader_probe.py --blocks 1 --steps 50    # the fetch kernel's duration
 
+--augment: the same question for the augmented step, two arms again:
+
+    three_launch  the harness's path before the fused fetch: ResidentLoader(output="none").fetch(), TrainAugment's draw and apply
+                  (spv_loader_fetch, spv_augment_params, spv_augment_u8) host-issued, the two copies into the captured buffers, the replay
+    fused         GraphedTrainStep(loader=ResidentLoader(output="augment", augment=...)): the replay and nothing else
+
+The record's keys keep their names: host_fed_* is the three-launch arm, loader_fed_* the fused one.
+
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/loader_probe.py --augment --blocks 1 --steps 50   # the four kernels' durations
+
 Only one graph-replayed step may own the library's dropout seed word, so the host-fed step object is closed after its capture and its
 graph replayed directly (as tools/ema_probe.py does): its dropout kernels (p = 0.001) then draw their masks from the loader-fed
 step's seed word, which changes no launch and no byte moved.
@@ -34,6 +44,7 @@ import torch  # noqa: E402
 
 from bench import SMALL  # noqa: E402
 from spectre_vit import shadows  # noqa: E402
+from spectre_vit.augment import TrainAugment  # noqa: E402
 from spectre_vit.data import CIFAR_MEAN, CIFAR_STD, ResidentLoader  # noqa: E402
 from spectre_vit.graph import GraphedTrainStep  # noqa: E402
 from spectre_vit.loss import CrossEntropyLoss  # noqa: E402
@@ -75,6 +86,26 @@ class HostFed:
         shadows.invalidate_weight_shadows()
 
 
+class ThreeLaunch:
+    """the harness's augmented step before the fused fetch (spectre_vit/harness.py train(device_loader=True, augment=True, graph=True)
+    with a loader of output "none"): fetch, draw and apply host-issued in front of a captured step's replay"""
+
+    def __init__(self, images_nhwc, loader, aug, step):
+        self.images, self.loader, self.aug, self.step = images_nhwc, loader, aug, step
+
+    def batch_of_next_step(self):
+        t = self.loader.step
+        self.loader.fetch()
+        return self.aug(self.images, self.loader.index, step=t), self.loader.labels
+
+    def __call__(self):
+        img, labels = self.batch_of_next_step()
+        self.step.img.copy_(img, non_blocking=True)
+        self.step.labels.copy_(labels, non_blocking=True)
+        self.step.graph.replay()   # (the step object is closed: its __call__, minus the check)
+        shadows.invalidate_weight_shadows()
+
+
 def block(run, steps):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -91,6 +122,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--blocks", type=int, default=3)
     ap.add_argument("--steps", type=int, default=200, help="steps per timed block")
+    ap.add_argument("--augment", action="store_true", help="the augmented step: three host-issued launches + replay against the fused fetch")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
     dev = torch.device("cuda:0")
@@ -98,11 +130,18 @@ def main():
     images_nhwc = torch.randint(0, 256, (a.n, 32, 32, 3), dtype=torch.uint8, device=dev, generator=g)
     images_nchw = images_nhwc.permute(0, 3, 1, 2).contiguous()   # the layout harness.SyntheticCifar keeps
     labels = torch.randint(0, 100, (a.n,), device=dev, generator=g).to(torch.uint8)
-    feeder = HostFed(images_nchw, labels, a.batch, None)
+    if a.augment:
+        aug = TrainAugment(CIFAR_MEAN, CIFAR_STD, seed=7)
+        feeder = ThreeLaunch(images_nhwc, ResidentLoader(images_nhwc, labels, a.batch, seed=42, output="none"), aug, None)
+    else:
+        feeder = HostFed(images_nchw, labels, a.batch, None)
     img0, lab0 = feeder.batch_of_next_step()
     feeder.step = build(img0, lab0, None)
     feeder.step.close()
-    loader = ResidentLoader(images_nhwc, labels, a.batch, seed=42)
+    if a.augment:
+        loader = ResidentLoader(images_nhwc, labels, a.batch, seed=42, output="augment", augment=aug)
+    else:
+        loader = ResidentLoader(images_nhwc, labels, a.batch, seed=42)
     fed = build(None, None, loader)
     try:
         for _ in range(a.warmup):
@@ -114,11 +153,14 @@ def main():
             t_loader.append(block(fed, a.steps))
         med = statistics.median
         spread = max(t_host) - min(t_host)
-        rec = {"workload": f"SpectreViT Small fft, bs {a.batch}, bf16, graph replay, resident set of {a.n}", "blocks": a.blocks,
+        rec = {"workload": f"SpectreViT Small fft, bs {a.batch}, bf16, graph replay, resident set of {a.n}" + (", augmented" if a.augment else ""),
+               "arms": {"host_fed": "three_launch", "loader_fed": "fused"} if a.augment else {"host_fed": "host_fed", "loader_fed": "loader_fed"},
+               "blocks": a.blocks,
                "steps_per_block": a.steps, "host_fed_ms": med(t_host), "loader_fed_ms": med(t_loader), "host_fed_ms_blocks": t_host,
                "loader_fed_ms_blocks": t_loader, "host_fed_spread_ms": spread, "delta_us": (med(t_loader) - med(t_host)) * 1e3,
                "within_bound": bool(med(t_loader) <= med(t_host) + spread),
-               "host_issued_per_step": {"host_fed": "9 launches + 1 replay", "loader_fed": "1 replay"},
+               "host_issued_per_step": {"host_fed": "3 launches + 2 copies + 1 replay" if a.augment else "9 launches + 1 replay",
+                                        "loader_fed": "1 replay"},
                "loss_host_fed": float(feeder.step.loss.detach()), "loss_loader_fed": float(fed.loss.detach()), "loader_step": loader.step,
                "loader_device_step": loader.device_step()}
     finally:

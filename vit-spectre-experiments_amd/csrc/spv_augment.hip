@@ -1,9 +1,12 @@
 // Training augmentation on the device: the transform chain of the reference's loader (spectre_vit/repl/train.py:100-115,
 // RandomHorizontalFlip -> ColorJitter -> RandomGrayscale -> RandomAffine -> RandomApply([GaussianBlur(3)]) -> ToTensor -> Normalize ->
 // RandomErasing) as two kernels: spv_augment_params draws the per-sample parameter table, spv_augment_u8 applies it, one workgroup per
-// image with the image staged in LDS.  Definitions: include/spv.h and DESIGN.md section 4c.
+// image with the image staged in LDS.  Definitions: include/spv.h and DESIGN.md section 4c.  At the end of the file the resident
+// loader's fetch, the draw and the chain as ONE kernel that reads the step from the loader's device cursor (spv_loader_fetch_augment,
+// DESIGN.md section 4k): draw and chain are device functions with one definition each, called from both places.
 #include "spv_common.h"
 #include "spv_augment_core.h"   // clamp01, grey_of, hue_shift: shared with the tiled kernels
+#include "spv_loader_core.h"    // the fused fetch at the end of this file: the sample order and the cursor's protocol
 #include <math.h>
 
 constexpr int AUG_THREADS = 256;
@@ -21,6 +24,18 @@ extern "C" int spv_augment_supported(int chans, int height, int width) {
     return aug_lds_bytes(chans, height, width) <= (size_t)AUG_LDS_BYTES ? 1 : 0;
 }
 
+// the fused fetch keeps, behind the chain's floats, what its workgroup hands from one thread to the others: the sample's table row,
+// the step (64 bits) and the row of the set, padded to 16 bytes
+constexpr int FUSED_TAIL_FLOATS = SPV_AUG_NPARAM + 4;
+static inline size_t fused_lds_bytes(int chans, int height, int width) {
+    return aug_lds_bytes(chans, height, width) + FUSED_TAIL_FLOATS * sizeof(float);
+}
+
+extern "C" int spv_loader_augment_supported(int chans, int height, int width) {
+    if (!spv_augment_supported(chans, height, width) || height > 512 || width > 512) return 0;   // the chain's shapes that the loader takes
+    return fused_lds_bytes(chans, height, width) <= (size_t)AUG_LDS_BYTES ? 1 : 0;
+}
+
 // ---------------------------------------------------------------- parameter draws
 // uniform in [0, 1) with 24 bits, draw `d` of the sample whose key is `key`
 __device__ __forceinline__ float aug_u01(unsigned key, unsigned d) {
@@ -28,14 +43,18 @@ __device__ __forceinline__ float aug_u01(unsigned key, unsigned d) {
 }
 __device__ __forceinline__ float aug_range(float lo, float hi, float u) { return lo + (hi - lo) * u; }
 
-__global__ __launch_bounds__(AUG_THREADS) void augment_params_kernel(float* __restrict__ params, int B, int H, int W, spv_augment_cfg c,
-                                                                     uint64_t seed, uint64_t step) {
-    const int s = blockIdx.x * AUG_THREADS + threadIdx.x;
-    if (s >= B) return;
+// the sixteen numbers of one sample: the table row
+struct AugRow {
+    float v[SPV_AUG_NPARAM];
+};
+
+// sample slot `s` of `step`: ONE definition of the draw, for the table kernel below and for the fused fetch at the end of this file
+__device__ __forceinline__ AugRow aug_draw(int H, int W, const spv_augment_cfg& c, uint64_t seed, uint64_t step, unsigned s) {
     unsigned key = mix32((unsigned)seed + 0x9e3779b1u) ^ mix32((unsigned)(seed >> 32) + 0x7f4a7c15u);
     key = mix32(key + (unsigned)step * 0x85ebca6bu) ^ mix32((unsigned)(step >> 32) + 0x27d4eb2fu);
-    key = mix32(key + (unsigned)s * 0x9e3779b1u);
-    float p[SPV_AUG_NPARAM];
+    key = mix32(key + s * 0x9e3779b1u);
+    AugRow row;
+    float* p = row.v;
 #pragma unroll
     for (int i = 0; i < SPV_AUG_NPARAM; ++i) p[i] = 0.0f;
     p[SPV_AUG_FLIP] = aug_u01(key, 0) < c.flip_p ? 1.0f : 0.0f;
@@ -64,26 +83,44 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_params_kernel(float* __re
             break;
         }
     }
+    return row;
+}
+// the row to the table (params 16-byte aligned: four 16-byte stores)
+__device__ __forceinline__ void aug_store_row(float* params, unsigned s, const AugRow& row) {
     float4* o = reinterpret_cast<float4*>(params + (size_t)s * SPV_AUG_NPARAM);
 #pragma unroll
-    for (int i = 0; i < SPV_AUG_NPARAM / 4; ++i) o[i] = make_float4(p[4 * i], p[4 * i + 1], p[4 * i + 2], p[4 * i + 3]);
+    for (int i = 0; i < SPV_AUG_NPARAM / 4; ++i) o[i] = make_float4(row.v[4 * i], row.v[4 * i + 1], row.v[4 * i + 2], row.v[4 * i + 3]);
 }
 
-extern "C" int spv_augment_params(float* params, int batch, int chans, int height, int width, const spv_augment_cfg* cfg, uint64_t seed,
-                                  uint64_t step, void* stream) {
-    SPV_CHECK(params != nullptr && cfg != nullptr, "spv_augment_params: params / cfg missing");
-    SPV_CHECK(((uintptr_t)params & 15) == 0, "spv_augment_params: params must be 16-byte aligned");
+__global__ __launch_bounds__(AUG_THREADS) void augment_params_kernel(float* __restrict__ params, int B, int H, int W, spv_augment_cfg c,
+                                                                     uint64_t seed, uint64_t step) {
+    const int s = blockIdx.x * AUG_THREADS + threadIdx.x;
+    if (s >= B) return;
+    aug_store_row(params, (unsigned)s, aug_draw(H, W, c, seed, step, (unsigned)s));
+}
+
+// the checks of every entry point that draws a table (spv_augment_params, spv_loader_fetch_augment): on the host, before any launch
+static int aug_draw_check(const char* name, const float* params, const spv_augment_cfg* cfg, int batch, int chans, int height, int width) {
+    SPV_CHECK(params != nullptr && cfg != nullptr, "%s: params / cfg missing", name);
+    SPV_CHECK(((uintptr_t)params & 15) == 0, "%s: params must be 16-byte aligned", name);
     SPV_CHECK(batch > 0 && (chans == 1 || chans == 3) && height >= 2 && width >= 2 && height <= 4096 && width <= 4096,
-              "spv_augment_params: bad shape batch=%d chans=%d %dx%d", batch, chans, height, width);
+              "%s: bad shape batch=%d chans=%d %dx%d", name, batch, chans, height, width);
     const spv_augment_cfg& c = *cfg;
     const bool probs = c.flip_p >= 0.0f && c.flip_p <= 1.0f && c.gray_p >= 0.0f && c.gray_p <= 1.0f && c.blur_p >= 0.0f &&
                        c.blur_p <= 1.0f && c.erase_p >= 0.0f && c.erase_p <= 1.0f;
-    SPV_CHECK(probs, "spv_augment_params: a probability outside [0, 1]");
+    SPV_CHECK(probs, "%s: a probability outside [0, 1]", name);
     const bool ranges = c.bright_lo >= 0.0f && c.bright_lo <= c.bright_hi && c.contrast_lo >= 0.0f && c.contrast_lo <= c.contrast_hi &&
                         c.sat_lo >= 0.0f && c.sat_lo <= c.sat_hi && c.hue_lo >= -0.5f && c.hue_lo <= c.hue_hi && c.hue_hi <= 0.5f &&
                         c.degrees >= 0.0f && c.degrees <= 180.0f && c.sigma_lo > 0.0f && c.sigma_lo <= c.sigma_hi && c.scale_lo >= 0.0f &&
                         c.scale_lo <= c.scale_hi && c.scale_hi <= 1.0f && c.ratio_lo > 0.0f && c.ratio_lo <= c.ratio_hi;
-    SPV_CHECK(ranges, "spv_augment_params: a range is empty or outside its op's domain");
+    SPV_CHECK(ranges, "%s: a range is empty or outside its op's domain", name);
+    return 0;
+}
+
+extern "C" int spv_augment_params(float* params, int batch, int chans, int height, int width, const spv_augment_cfg* cfg, uint64_t seed,
+                                  uint64_t step, void* stream) {
+    if (int rc = aug_draw_check("spv_augment_params", params, cfg, batch, chans, height, width)) return rc;
+    const spv_augment_cfg& c = *cfg;
     hipLaunchKernelGGL(augment_params_kernel, dim3(cdiv(batch, AUG_THREADS)), dim3(AUG_THREADS), 0, static_cast<hipStream_t>(stream), params,
                        batch, height, width, c, seed, step);
     SPV_LAUNCH_CHECK("spv_augment_params");
@@ -98,24 +135,14 @@ extern "C" int spv_augment_params(float* params, int batch, int chans, int heigh
 // Thread t owns pixels t, t + 256, ... through the jitter and grayscale ops (no barrier between them; the contrast mean is the one
 // workgroup reduction); rotation and blur read neighbours, with a barrier in front of each pass.
 template <int C>
-__global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const unsigned char* __restrict__ src, const int64_t* __restrict__ index,
-                                                                 const float* __restrict__ params, const float* __restrict__ mean,
-                                                                 const float* __restrict__ inv_std, float* __restrict__ out, int n_src,
-                                                                 int H, int W, int vec) {
-    extern __shared__ float lds[];
+__device__ __forceinline__ void aug_chain(const unsigned char* __restrict__ img, const AugRow row, float* __restrict__ o, float* lds,
+                                          const float* __restrict__ mean, const float* __restrict__ inv_std, int H, int W, int vec) {
     const int HW = H * W, CHW = C * HW;
     float* cur = lds;
     float* oth = lds + CHW;
     float* red = lds + 2 * CHW;
-    const int b = blockIdx.x, tid = threadIdx.x;
-    const float* p = params + (size_t)b * SPV_AUG_NPARAM;
-    float* o = out + (size_t)b * CHW;
-    const int64_t row = index != nullptr ? index[b] : (int64_t)b;
-    if (row < 0 || row >= (int64_t)n_src) {   // workgroup uniform: nothing is read, the image is poisoned
-        for (int e = tid; e < CHW; e += AUG_THREADS) o[e] = __builtin_nanf("");
-        return;
-    }
-    const unsigned char* img = src + (size_t)row * CHW;
+    const int tid = threadIdx.x;
+    const float* p = row.v;
 
     // 1. load u8 / 255, mirrored in W if flip: the owner of output pixel (y, x) reads source pixel (y, W - 1 - x)
     const bool flip = p[SPV_AUG_FLIP] != 0.0f;
@@ -276,6 +303,26 @@ __global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const unsigned 
     }
 }
 
+template <int C>
+__global__ __launch_bounds__(AUG_THREADS) void augment_u8_kernel(const unsigned char* __restrict__ src, const int64_t* __restrict__ index,
+                                                                 const float* __restrict__ params, const float* __restrict__ mean,
+                                                                 const float* __restrict__ inv_std, float* __restrict__ out, int n_src,
+                                                                 int H, int W, int vec) {
+    extern __shared__ float lds[];
+    const int CHW = C * H * W;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    float* o = out + (size_t)b * CHW;
+    const int64_t row = index != nullptr ? index[b] : (int64_t)b;
+    if (row < 0 || row >= (int64_t)n_src) {   // workgroup uniform: nothing is read, the image is poisoned
+        for (int e = tid; e < CHW; e += AUG_THREADS) o[e] = __builtin_nanf("");
+        return;
+    }
+    AugRow r;
+#pragma unroll
+    for (int i = 0; i < SPV_AUG_NPARAM; ++i) r.v[i] = params[(size_t)b * SPV_AUG_NPARAM + i];
+    aug_chain<C>(src + (size_t)row * CHW, r, o, lds, mean, inv_std, H, W, vec);
+}
+
 extern "C" int spv_augment_u8(const unsigned char* src_nhwc, const int64_t* index, const float* params, const float* mean,
                               const float* inv_std, float* out_nchw, int batch, int n_src, int chans, int height, int width, void* stream) {
     SPV_CHECK(batch > 0 && n_src > 0 && chans > 0 && height > 0 && width > 0, "spv_augment_u8: bad shape");
@@ -297,6 +344,106 @@ extern "C" int spv_augment_u8(const unsigned char* src_nhwc, const int64_t* inde
         hipLaunchKernelGGL(augment_u8_kernel<1>, dim3(batch), dim3(AUG_THREADS), lds, st, src_nhwc, index, params, mean, inv_std, out_nchw,
                            n_src, height, width, vec);
     SPV_LAUNCH_CHECK("spv_augment_u8");
+    SPV_COUNT_PATH(SPV_PATH_AUGMENT);
+    return 0;
+}
+
+// ---------------------------------------------------------------- fetch and augment in one launch
+// spv_loader_fetch(mode none) at the cursor's step t, spv_augment_params(step = t) and spv_augment_u8 as ONE launch, one workgroup per
+// image: nothing of it is a by-value function of the step, so a captured launch draws a new batch AND a new table at every replay.
+struct FusedArgs {
+    const unsigned char* src;     // [n][H][W][C]
+    const void* labels_src;       // [n] uint8 or int64
+    unsigned long long* cursor;   // the loader's cursor block
+    int64_t* index;               // [batch]
+    int64_t* labels;              // [batch]
+    float* params;                // [batch][16]
+    float* out;                   // [batch][C][H][W]
+    const float* mean;
+    const float* inv_std;
+    uint64_t loader_seed, augment_seed;
+    LdrGeom g;
+    spv_augment_cfg cfg;
+    int H, W, vec, label_i64;
+};
+
+// Thread 0 reads the step and hands it round; then the row of the set (wave 0) and the table row (wave 1) -- both functions of (t, b)
+// alone -- are worked out side by side and handed round through LDS (never through `params` in global memory: a line of it cached
+// from the previous replay may be stale in this CU's vector cache), and wave 2 takes the workgroup's ticket while the others already
+// load the image.  The ticket comes after the read of t in every workgroup, which is all the protocol asks: the last workgroup to
+// arrive knows that every other one holds its copy of t, and only then stores t + 1.
+template <int C>
+__global__ __launch_bounds__(AUG_THREADS) void loader_augment_kernel(FusedArgs a) {
+    extern __shared__ float lds[];
+    const int CHW = C * a.H * a.W;
+    float* row_sh = lds + 2 * CHW + AUG_RED_FLOATS;                                               // [16]
+    unsigned long long* t_sh = reinterpret_cast<unsigned long long*>(row_sh + SPV_AUG_NPARAM);   // 8-byte aligned: 8 CHW + 96 bytes in
+    uint32_t* idx_sh = reinterpret_cast<uint32_t*>(t_sh + 1);
+    const uint32_t b = blockIdx.x;
+    const int tid = threadIdx.x;
+    if (tid == 0) *t_sh = ldr_read_step(a.cursor);
+    __syncthreads();
+    const uint64_t t = *t_sh;
+    if (tid == 0) {
+        const uint32_t idx = ldr_index(a.loader_seed, t, b, a.g);
+        a.index[b] = (int64_t)idx;
+        a.labels[b] = a.label_i64 ? static_cast<const int64_t*>(a.labels_src)[idx]
+                                  : (int64_t) static_cast<const unsigned char*>(a.labels_src)[idx];
+        *idx_sh = idx;
+    } else if (tid == 64) {
+        const AugRow r = aug_draw(a.H, a.W, a.cfg, a.augment_seed, t, b);
+        aug_store_row(a.params, b, r);
+#pragma unroll
+        for (int i = 0; i < SPV_AUG_NPARAM; ++i) row_sh[i] = r.v[i];
+    }
+    __syncthreads();
+    if (tid == 128) ldr_arrive<false>(a.cursor, t, a.g.batch);   // groups = batch; t came through LDS behind two barriers: the read is done
+    AugRow r;
+#pragma unroll
+    for (int i = 0; i < SPV_AUG_NPARAM; ++i) r.v[i] = row_sh[i];
+    const uint32_t idx = *idx_sh;   // < n by construction (spv_loader_core.h)
+    aug_chain<C>(a.src + (size_t)idx * CHW, r, a.out + (size_t)b * CHW, lds, a.mean, a.inv_std, a.H, a.W, a.vec);
+}
+
+extern "C" int spv_loader_fetch_augment(const unsigned char* src_nhwc, const void* labels_src, void* cursor, int64_t* index, int64_t* labels,
+                                        float* params, float* out_nchw, const float* mean, const float* inv_std,
+                                        const spv_augment_cfg* cfg, int n, int batch, int chans, int height, int width, int world, int rank,
+                                        int steps_per_epoch, uint64_t loader_seed, int shuffle, int label_dtype, uint64_t augment_seed,
+                                        void* stream) {
+    const char* name = "spv_loader_fetch_augment";
+    // the fetch's refusals (as its float mode: src, img, mean and inv_std are all read), then the draw's, then this kernel's own
+    if (int rc = spv_loader_check(name, src_nhwc, labels_src, cursor, index, labels, out_nchw, mean, inv_std, n, batch, chans, height, width,
+                                  world, rank, steps_per_epoch, SPV_LOADER_FLOAT, label_dtype))
+        return rc;
+    if (int rc = aug_draw_check(name, params, cfg, batch, chans, height, width)) return rc;
+    SPV_CHECK(spv_loader_augment_supported(chans, height, width),
+              "%s: a %d x %d x %d image is not supported (two fp32 copies of the image, the reduction slots and %d bytes of hand-over "
+              "within %d bytes of LDS): fetch with mode none, then spv_augment_params and spv_augment_u8 / spv_augment_tiled_u8",
+              name, chans, height, width, (int)(FUSED_TAIL_FLOATS * sizeof(float)), AUG_LDS_BYTES);
+    SPV_CHECK(((uintptr_t)out_nchw & 3) == 0, "%s: out must be 4-byte aligned", name);
+    FusedArgs a;
+    a.src = src_nhwc;
+    a.labels_src = labels_src;
+    a.cursor = static_cast<unsigned long long*>(cursor);
+    a.index = index;
+    a.labels = labels;
+    a.params = params;
+    a.out = out_nchw;
+    a.mean = mean;
+    a.inv_std = inv_std;
+    a.loader_seed = loader_seed;
+    a.augment_seed = augment_seed;
+    a.g = LdrGeom{(uint32_t)n, (uint32_t)batch, (uint32_t)world, (uint32_t)rank, (uint32_t)steps_per_epoch, shuffle != 0};
+    a.cfg = *cfg;
+    a.H = height;
+    a.W = width;
+    a.vec = (height * width) % 4 == 0 && ((uintptr_t)out_nchw & 15) == 0;
+    a.label_i64 = label_dtype == SPV_LOADER_LABEL_I64;
+    const size_t lds = fused_lds_bytes(chans, height, width);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (chans == 3) hipLaunchKernelGGL(loader_augment_kernel<3>, dim3(batch), dim3(AUG_THREADS), lds, st, a);
+    else hipLaunchKernelGGL(loader_augment_kernel<1>, dim3(batch), dim3(AUG_THREADS), lds, st, a);
+    SPV_LAUNCH_CHECK(name);
     SPV_COUNT_PATH(SPV_PATH_AUGMENT);
     return 0;
 }

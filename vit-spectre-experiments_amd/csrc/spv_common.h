@@ -161,6 +161,11 @@ __device__ __forceinline__ void fold_partials_block(const FoldJob& j, int bid, i
 // host: the checks the three metered loss forwards share (spv_head.hip)
 int spv_train_meter_check(const char* name, const void* meter, int k, int rows, int classes);
 
+// host: the checks every resident-loader fetch shares (spv_loader.hip; `mode` says which of src / img / mean / inv_std must be there)
+int spv_loader_check(const char* name, const unsigned char* src_nhwc, const void* labels_src, const void* cursor, const int64_t* index,
+                     const int64_t* labels, const void* img, const float* mean, const float* inv_std, int n, int batch, int chans,
+                     int height, int width, int world, int rank, int steps_per_epoch, int mode, int label_dtype);
+
 // the meter block's words
 constexpr int TM_CURSOR = 0, TM_CAPACITY = 1, TM_DROPPED = 2, TM_SEEN = 3, TM_TOP1 = 4, TM_TOPK = 5, TM_LOSS = 6, TM_SOFT = 7, TM_CE = 8;
 constexpr int TM_HEADER = SPV_TRAIN_METER_HEADER, TM_ROW = SPV_TRAIN_METER_ROW;

@@ -26,17 +26,10 @@ struct LoaderArgs {
     unsigned spans, groups;       // workgroups per image; workgroups of the launch
 };
 
-// Every workgroup reads the step, THEN announces itself; the last one to arrive -- every workgroup has its copy of t by then -- moves
-// the cursor on and re-arms the counter for the next launch (the scheme of the cross-entropy kernel's join, spv_head.hip).  The read
-// is an agent-scope atomic load (never served from a stale line), and the fence keeps it in front of the counter's add.
+// read-then-arrive on the cursor block: the protocol of spv_loader_core.h (shared with the fused fetch of spv_augment.hip)
 __device__ __forceinline__ uint64_t read_step_and_arrive(const LoaderArgs& a) {
-    const uint64_t t = __hip_atomic_load(a.cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __threadfence();
-    unsigned* counter = reinterpret_cast<unsigned*>(a.cursor + 1);
-    if (atomicAdd(counter, 1u) == a.groups - 1) {
-        __hip_atomic_store(a.cursor, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    const uint64_t t = ldr_read_step(a.cursor);
+    ldr_arrive(a.cursor, t, a.groups);
     return t;
 }
 
@@ -144,27 +137,37 @@ bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) ==
 
 }  // namespace
 
+// the checks every fetch shares (spv_loader_fetch here, spv_loader_fetch_augment in spv_augment.hip), on the host before any launch
+int spv_loader_check(const char* name, const unsigned char* src_nhwc, const void* labels_src, const void* cursor, const int64_t* index,
+                     const int64_t* labels, const void* img, const float* mean, const float* inv_std, int n, int batch, int chans,
+                     int height, int width, int world, int rank, int steps_per_epoch, int mode, int label_dtype) {
+    SPV_CHECK(mode == SPV_LOADER_NONE || mode == SPV_LOADER_FLOAT || mode == SPV_LOADER_UINT8, "%s: unknown mode %d", name, mode);
+    SPV_CHECK(label_dtype == SPV_LOADER_LABEL_U8 || label_dtype == SPV_LOADER_LABEL_I64, "%s: unknown label dtype %d", name,
+              label_dtype);
+    SPV_CHECK(labels_src && cursor && index && labels, "%s: null labels_src / cursor / index / labels", name);
+    SPV_CHECK((reinterpret_cast<uintptr_t>(cursor) & 7u) == 0, "%s: cursor block not 8-byte aligned", name);
+    SPV_CHECK(mode == SPV_LOADER_NONE || (src_nhwc && img), "%s: null src_nhwc / img in an image mode", name);
+    SPV_CHECK(mode != SPV_LOADER_FLOAT || (mean && inv_std), "%s: mode float needs mean and inv_std", name);
+    SPV_CHECK(n >= 1, "%s: n = %d samples (1 .. 2^31 - 1)", name, n);
+    SPV_CHECK(batch >= 1, "%s: batch = %d must be positive", name, batch);
+    SPV_CHECK(world >= 1 && rank >= 0 && rank < world, "%s: rank %d outside [0, world = %d)", name, rank, world);
+    SPV_CHECK(steps_per_epoch >= 1 && (int64_t)steps_per_epoch * batch * world <= (int64_t)n,
+              "%s: steps_per_epoch = %d: need 1 <= steps and steps * batch * world <= n (%d * %d * %d vs %d)", name, steps_per_epoch,
+              steps_per_epoch, batch, world, n);
+    SPV_CHECK((chans == 1 || chans == 3) && height >= 1 && height <= 512 && width >= 1 && width <= 512,
+              "%s: chans = %d (1 or 3), height = %d, width = %d (1 .. 512)", name, chans, height, width);
+    return 0;
+}
+
 extern "C" int64_t spv_loader_cursor_bytes() { return SPV_LOADER_CURSOR_BYTES; }
 
 extern "C" int spv_loader_fetch(const unsigned char* src_nhwc, const void* labels_src, void* cursor, int64_t* index, int64_t* labels,
                                 void* img, const float* mean, const float* inv_std, int n, int batch, int chans, int height, int width,
                                 int world, int rank, int steps_per_epoch, uint64_t seed, int shuffle, int mode, int label_dtype,
                                 void* stream) {
-    SPV_CHECK(mode == SPV_LOADER_NONE || mode == SPV_LOADER_FLOAT || mode == SPV_LOADER_UINT8, "spv_loader_fetch: unknown mode %d", mode);
-    SPV_CHECK(label_dtype == SPV_LOADER_LABEL_U8 || label_dtype == SPV_LOADER_LABEL_I64, "spv_loader_fetch: unknown label dtype %d",
-              label_dtype);
-    SPV_CHECK(labels_src && cursor && index && labels, "spv_loader_fetch: null labels_src / cursor / index / labels");
-    SPV_CHECK((reinterpret_cast<uintptr_t>(cursor) & 7u) == 0, "spv_loader_fetch: cursor block not 8-byte aligned");
-    SPV_CHECK(mode == SPV_LOADER_NONE || (src_nhwc && img), "spv_loader_fetch: null src_nhwc / img in an image mode");
-    SPV_CHECK(mode != SPV_LOADER_FLOAT || (mean && inv_std), "spv_loader_fetch: mode float needs mean and inv_std");
-    SPV_CHECK(n >= 1, "spv_loader_fetch: n = %d samples (1 .. 2^31 - 1)", n);
-    SPV_CHECK(batch >= 1, "spv_loader_fetch: batch = %d must be positive", batch);
-    SPV_CHECK(world >= 1 && rank >= 0 && rank < world, "spv_loader_fetch: rank %d outside [0, world = %d)", rank, world);
-    SPV_CHECK(steps_per_epoch >= 1 && (int64_t)steps_per_epoch * batch * world <= (int64_t)n,
-              "spv_loader_fetch: steps_per_epoch = %d: need 1 <= steps and steps * batch * world <= n (%d * %d * %d vs %d)", steps_per_epoch,
-              steps_per_epoch, batch, world, n);
-    SPV_CHECK((chans == 1 || chans == 3) && height >= 1 && height <= 512 && width >= 1 && width <= 512,
-              "spv_loader_fetch: chans = %d (1 or 3), height = %d, width = %d (1 .. 512)", chans, height, width);
+    if (int rc = spv_loader_check("spv_loader_fetch", src_nhwc, labels_src, cursor, index, labels, img, mean, inv_std, n, batch, chans, height,
+                                  width, world, rank, steps_per_epoch, mode, label_dtype))
+        return rc;
     LoaderArgs a;
     a.src = src_nhwc;
     a.labels_src = labels_src;

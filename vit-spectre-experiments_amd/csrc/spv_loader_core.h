@@ -1,7 +1,7 @@
 // The resident loader's sample order (include/spv.h): the keyed bijection on [0, n) that stands in for
 // DataLoader(shuffle=True)'s randperm, and the position rule that shards it over the ranks.  ONE definition for the fetch kernel of
-// spv_loader.hip and for the host: no HIP type in it, tests/test_resident_loader.py compiles it with a plain C++ compiler and holds
-// it, bit for bit, to tests/loader_ref.py.
+// spv_loader.hip and for the host: no HIP type in it outside the __HIPCC__ block at the end (the cursor's protocol, device only);
+// tests/test_resident_loader.py compiles it with a plain C++ compiler and holds it, bit for bit, to tests/loader_ref.py.
 #pragma once
 #include <stdint.h>
 
@@ -71,3 +71,25 @@ SPV_LDR_HD uint32_t ldr_index(uint64_t seed, uint64_t t, uint32_t r, const LdrGe
     const uint32_t pos = ldr_position(t, r, g);
     return g.shuffle ? ldr_permute(ldr_key(seed, ldr_epoch(t, g)), g.n, pos) : pos;
 }
+
+#if defined(__HIPCC__)
+// The cursor block's protocol, ONE definition for every kernel that reads the step from it (spv_loader.hip, spv_augment.hip).
+// Every workgroup reads the step, THEN announces itself; the last one to arrive -- every workgroup has its copy of t by then -- moves
+// the cursor on and re-arms the counter for the next launch (the scheme of the cross-entropy kernel's join, spv_head.hip).  The read
+// is an agent-scope atomic load (never served from a stale line), and the fence keeps it in front of the counter's add.
+__device__ __forceinline__ uint64_t ldr_read_step(const unsigned long long* cursor) {
+    return __hip_atomic_load(cursor, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// FENCED = false is for a caller whose read of t is known to be complete when it arrives: the value went through LDS and a workgroup
+// barrier on its way to the arriving thread, so the load has returned and nothing is left for a fence to order (the fence is an L2
+// write-back and an L1 invalidate on the one wave the rest of the workgroup then waits for: microseconds).
+template <bool FENCED = true>
+__device__ __forceinline__ void ldr_arrive(unsigned long long* cursor, uint64_t t, unsigned groups) {
+    if constexpr (FENCED) __threadfence();
+    unsigned* counter = reinterpret_cast<unsigned*>(cursor + 1);
+    if (atomicAdd(counter, 1u) == groups - 1) {
+        __hip_atomic_store(cursor, t + 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+#endif

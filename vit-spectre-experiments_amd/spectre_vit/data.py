@@ -12,8 +12,14 @@ graph-replayed training step (``spectre_vit.graph.GraphedTrainStep(loader=...)``
 The order is not torch's randperm: each epoch's permutation is a keyed bijection of [0, n) evaluated per sample (a six-round Feistel
 network with cycle-walking, include/spv.h "the resident loader"), sharded over the ranks as ``idx[rank::world]`` with the tail dropped.
 ``ResidentLoader.indices`` restates it on the host.
+
+``output="augment"`` with ``augment=TrainAugment(...)`` fetches AND augments in that one launch (``spv_loader_fetch_augment``,
+csrc/spv_augment.hip): the transform's parameter table is drawn on the device under the key (augment seed, the cursor's step, slot), so
+a captured fetch draws a new table at every replay; ``loader.params`` holds the step's table, ``loader.img`` the augmented batch.
 """
 from __future__ import annotations
+
+import ctypes
 
 import numpy as np
 import torch
@@ -28,6 +34,7 @@ _U64 = (1 << 64) - 1
 _GOLDEN = 0x9E3779B97F4A7C15
 ROUNDS = 6          # SPV_LOADER_ROUNDS
 _MODES = {"none": 0, "float": 1, "uint8": 2}   # SPV_LOADER_NONE / _FLOAT / _UINT8
+_OUTPUTS = tuple(_MODES) + ("augment",)        # "augment": the fused launch, spv_loader_fetch_augment
 
 
 def _mix64(x):
@@ -76,22 +83,36 @@ class ResidentLoader:
     labels          uint8 or int64 (N,), contiguous, on the same device
     output          "float": ``img`` fp32 (B, C, H, W) = (x / 255 - mean) / std (the kernel multiplies by 1 / std, rounded once);
                     "uint8": ``img`` uint8 (B, H, W, C), the rows unchanged (models built with uint8_input=True normalise themselves);
-                    "none": no image -- hand ``index`` to ``TrainAugment`` or to ``DistillationLoss(index=)``
+                    "none": no image -- hand ``index`` to ``TrainAugment`` or to ``DistillationLoss(index=)``;
+                    "augment": ``img`` fp32 (B, C, H, W) = ``augment``'s chain on the step's rows, its table drawn at the cursor's
+                    step, and ``params`` fp32 (B, 16) = that table -- ``augment(images, index, step=t)`` and
+                    ``augment.draw(B, step=t, ...)`` bit for bit, in the same launch as the fetch
+    augment         with output="augment" only: the ``spectre_vit.augment.TrainAugment`` whose mean / std, ranges and seed the launch
+                    takes (``mean`` / ``std`` here are unused); images the fused kernel cannot stage -- the tiled sizes, and the one
+                    LDS border shape -- are refused: output="none", then ``augment(images, loader.index, step=...)`` serves them
     rank, world     this process's shard: position p of the epoch's order belongs to rank p mod world.  Every rank passes the SAME
                     seed (the ranks share one permutation and take disjoint parts of it)
     steps_per_epoch None: every whole batch of the shard, (N // world) // batch_size; a smaller number ends the epoch earlier (the
                     next epoch draws a new permutation)
     shuffle=False   arange order
 
-    ``img``, ``labels`` (int64), ``index`` (int64) keep their addresses for the object's life.  ``step`` is the host's count of the
+    ``img``, ``labels`` (int64), ``index`` (int64), ``params`` keep their addresses for the object's life.  ``step`` is the host's count of the
     fetches (a captured fetch is counted when it is replayed: ``count_replay``); ``device_step()`` reads the device's.
     Every refusal below is raised before a device is touched; there is no CPU fallback."""
 
     def __init__(self, images_u8_nhwc, labels, batch_size, mean=CIFAR_MEAN, std=CIFAR_STD, seed=42, rank=0, world=1, output="float",
-                 shuffle=True, steps_per_epoch=None):
+                 shuffle=True, steps_per_epoch=None, augment=None):
         x = images_u8_nhwc
-        if output not in _MODES:
-            raise ValueError(f"output is one of {tuple(_MODES)}, got {output!r}")
+        if output not in _OUTPUTS:
+            raise ValueError(f"output is one of {_OUTPUTS}, got {output!r}")
+        if augment is not None and output != "augment":
+            raise ValueError(f"augment= goes with output='augment' (the fused fetch), not with output={output!r}")
+        if output == "augment":
+            from spectre_vit.augment import TrainAugment
+            if not isinstance(augment, TrainAugment):
+                raise ValueError(f"output='augment' needs augment=TrainAugment(...), got {augment!r}")
+            if augment.kernel == "tiled":
+                raise ValueError("output='augment' runs the whole-image LDS chain: not with TrainAugment(kernel='tiled')")
         if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous():
             raise TypeError("the resident loader takes a contiguous uint8 (N, H, W, C) set, got "
                             f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
@@ -110,6 +131,14 @@ class ResidentLoader:
                                  f"{0 if std is None else len(std)} channels")
             if min(float(s) for s in std) <= 0.0:
                 raise ValueError(f"std must be positive, got {tuple(std)}")
+        if output == "augment":
+            if len(augment.mean) != C:
+                raise ValueError(f"{C}-channel images, but the TrainAugment's mean / std name {len(augment.mean)} channels")
+            if not _native.call("spv_loader_augment_supported", C, H, W):   # a host predicate: no device is touched
+                raise ValueError(f"a {C} x {H} x {W} image does not fit the fused fetch's LDS staging (two fp32 copies, the reduction "
+                                 "slots and 80 bytes of hand-over within 64 KiB): use output='none', then "
+                                 "augment(images, loader.index, step=...) -- spv_loader_fetch, spv_augment_params and spv_augment_u8 / "
+                                 "spv_augment_tiled_u8 -- which still serves it")
         batch_size, rank, world = int(batch_size), int(rank), int(world)
         if batch_size < 1:
             raise ValueError(f"batch_size={batch_size} must be positive")
@@ -133,26 +162,40 @@ class ResidentLoader:
         self.shuffle = bool(shuffle)
         self.output = output
         dev = x.device
-        self.mean = self.inv_std = None
+        self.mean = self.inv_std = self.params = None
+        self.augment = augment
+        if output == "augment":
+            self.mean, self.inv_std = augment.norm(dev)
+            self.params = torch.zeros((batch_size, 16), dtype=torch.float32, device=dev)   # SPV_AUG_NPARAM
+            self._cfg = augment.cfg()   # a host struct read during each call: kept alive here
         if output == "float":   # (mean, 1 / std) as spectre_vit.augment.TrainAugment.norm makes them: the inverse in float64, rounded once
             self.mean = torch.tensor([float(m) for m in mean], dtype=torch.float32, device=dev)
             self.inv_std = (1.0 / torch.tensor([float(s) for s in std], dtype=torch.float64)).float().to(dev)
         self.img = {"float": lambda: torch.empty((batch_size, C, H, W), dtype=torch.float32, device=dev),
                     "uint8": lambda: torch.empty((batch_size, H, W, C), dtype=torch.uint8, device=dev),
+                    "augment": lambda: torch.empty((batch_size, C, H, W), dtype=torch.float32, device=dev),
                     "none": lambda: None}[output]()
         self.index = torch.zeros(batch_size, dtype=torch.int64, device=dev)
         self.labels = torch.zeros(batch_size, dtype=torch.int64, device=dev)
         self._cursor = torch.zeros(int(_native.call("spv_loader_cursor_bytes")) // 8, dtype=torch.int64, device=dev)
         self.step = 0
-        self._args = (_p(x), _p(labels), _p(self._cursor), _p(self.index), _p(self.labels), _p(self.img), _p(self.mean), _p(self.inv_std),
-                      n, batch_size, C, H, W, world, rank, self.steps_per_epoch, self.seed, int(self.shuffle), _MODES[output],
-                      1 if labels.dtype == torch.int64 else 0)
+        label_dtype = 1 if labels.dtype == torch.int64 else 0
+        if output == "augment":
+            self._entry = "spv_loader_fetch_augment"
+            self._args = (_p(x), _p(labels), _p(self._cursor), _p(self.index), _p(self.labels), _p(self.params), _p(self.img),
+                          _p(self.mean), _p(self.inv_std), ctypes.addressof(self._cfg), n, batch_size, C, H, W, world, rank,
+                          self.steps_per_epoch, self.seed, int(self.shuffle), label_dtype, augment.seed)
+        else:
+            self._entry = "spv_loader_fetch"
+            self._args = (_p(x), _p(labels), _p(self._cursor), _p(self.index), _p(self.labels), _p(self.img), _p(self.mean),
+                          _p(self.inv_std), n, batch_size, C, H, W, world, rank, self.steps_per_epoch, self.seed, int(self.shuffle),
+                          _MODES[output], label_dtype)
 
     # -- the launch -------------------------------------------------------------------------------------------------------------
     def fetch(self):
         """ONE launch on the current stream: the buffers take the batch of the cursor's step, the cursor moves on.  Allocates
         nothing and uploads nothing, so it may be captured; a captured (recorded, not run) fetch is not counted in ``step``."""
-        _native.call("spv_loader_fetch", *self._args, _stream())
+        _native.call(self._entry, *self._args, _stream())
         if not torch.cuda.is_current_stream_capturing():
             self.step += 1
 

@@ -219,7 +219,8 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     augment=True: every training batch goes through the reference's transform chain (train.py:100-115) on the GPU -- the training set
     kept once as uint8 NHWC, the shuffled batch index, the global step and augment_seed(config seed, rank) handed to
     spectre_vit.augment.TrainAugment; validation batches stay ToTensor + Normalize (eval_transform_spectre).  With graph=True its
-    launches (draw and apply; above the LDS kernel's size also the contrast mean's pre-pass) run on the step's stream in front of the replay.  Not with uint8_input (the chain's output is float) or distill.
+    launches (draw and apply; above the LDS kernel's size also the contrast mean's pre-pass) run on the step's stream in front of the replay
+    (with device_loader=True they are inside the replay: below).  Not with uint8_input (the chain's output is float) or distill.
     batch_hook(kind, step, img, label), kind "train" / "val": called with every batch as the model is about to see it (test seam).
     graph_eval=True: the epoch's validation runs through one spectre_vit.inference.InferenceSession -- a graph replay per batch (buckets:
     the validation batch size and the tail rounded up to a multiple of 8), accuracy and loss accumulated on the device by its metrics
@@ -243,8 +244,11 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     -- the epoch's permutation is computed on the device, one launch fetches a step's batch into fixed buffers -- instead of the host's
     randperm, slices, gathers and normalisation; with or without uint8_input.  Its steps per epoch are this loop's (min(per_pass,
     steps_per_epoch)), its seed loader_seed(config seed), its shard this rank's.  With graph=True the fetch is the first node of the
-    step's graph, so a step is one replay and nothing else; with augment=True the loader fetches index and labels only and
-    TrainAugment takes loader.index (draw and apply stay host-issued in front of the step: their step number is a by-value argument).
+    step's graph, so a step is one replay and nothing else -- with augment=True too: the loader then fetches and augments in one
+    launch (ResidentLoader(output="augment"): the table is keyed by the device cursor, which equals the global step, so the batches
+    are the bits TrainAugment(...)(set, loader.index, step=global_step) yields).  Only for images that launch cannot stage (the tiled
+    sizes, the LDS border shape) the loader fetches index and labels alone and TrainAugment takes loader.index, draw and apply
+    host-issued in front of the step (their step number is a by-value argument).
     The host then no longer knows a batch beforehand: batch_hook("train", step, img, label) is called AFTER the step, with the step's
     buffers (the loader's, or the augmented batch) -- valid until the next step overwrites them.  Validation is untouched.  The sample
     ORDER differs from the host randperm's (same distribution, another stream): hence a flag and not the default."""
@@ -310,10 +314,17 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         aug = TrainAugment(CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels], seed=augment_seed(seed, rank))
     if device_loader:
         from spectre_vit.data import ResidentLoader
+        # augment: fetch and augment in ONE launch where the fused kernel can stage the image (the table is then keyed by the loader's
+        # cursor, which equals global_step); otherwise index and labels only, draw and apply host-issued as without the loader
+        from spectre_vit import _native
+        H, W, C = train_nhwc.shape[1:]
+        fused = bool(augment and _native.call("spv_loader_augment_supported", C, H, W))
         loader = ResidentLoader(train_nhwc, train_set.labels, batch_size, CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels],
                                 seed=loader_seed(seed), rank=rank, world=world, steps_per_epoch=min(per_pass, steps_per_epoch or per_pass),
-                                output="none" if augment else ("uint8" if uint8_input else "float"))
-    loader_in_graph = loader is not None and graph and aug is None   # the step fetches its own batch
+                                output="augment" if fused else "none" if augment else ("uint8" if uint8_input else "float"),
+                                augment=aug if fused else None)
+    host_aug = aug if loader is None or loader.output == "none" else None   # the transform the host still issues per batch
+    loader_in_graph = loader is not None and graph and loader.img is not None   # the step fetches its own batch
 
     def train_batches():
         if loader is not None:
@@ -322,7 +333,7 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
                     yield None, None
                     continue
                 loader.fetch()
-                yield loader.img if aug is None else aug(train_nhwc, loader.index, step=global_step), loader.labels
+                yield loader.img if host_aug is None else host_aug(train_nhwc, loader.index, step=global_step), loader.labels
             return
         if aug is None:
             yield from train_set.batches(batch_size, True, gen, rank, world, raw_uint8=uint8_input and not distill)

@@ -106,6 +106,10 @@ _WORK_MODELS = {
     # the image read as uint8 and written as fp32 (mode 1) or uint8 (mode 2)
     "spv_loader_fetch": lambda i: ("loader_fetch", i[1:5], F32, "hbm",
                                    i[1] * (16.0 + (8 if i[10] else 1) + i[2] * i[3] * i[4] * {0: 0, 1: 5, 2: 2}.get(i[9], 0))),
+    # (n, batch, chans, height, width, world, rank, steps, shuffle, label dtype): index, labels and the table row written, the label
+    # read, the image read as uint8 and written as fp32
+    "spv_loader_fetch_augment": lambda i: ("loader_fetch_augment", i[1:5], F32, "hbm",
+                                           i[1] * (16.0 + (8 if i[9] else 1) + 64.0 + i[2] * i[3] * i[4] * 5)),
     "spv_cast": lambda i: ("cast", i[2:3], i[1], "hbm", 1.0 * i[2] * (_es(i[0]) + _es(i[1]))),
 }
 
