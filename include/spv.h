@@ -58,7 +58,7 @@ enum {
     SPV_PATH_TOKEN_UNPOOL = 19,  /* spv_token_pool_bwd */
     SPV_PATH_ATTN_ROW0_FWD = 20, /* spv_attention_row0_fwd (the attention mixer's CLS-only last layer) */
     SPV_PATH_ATTN_ROW0_BWD = 21, /* spv_attention_row0_bwd */
-    SPV_PATH_AUGMENT = 22,       /* spv_augment_u8 / spv_loader_fetch_augment (one workgroup per image) or spv_augment_tiled_u8 (output tiles): one per call */
+    SPV_PATH_AUGMENT = 22,       /* spv_augment_u8 / spv_loader_fetch_augment (one workgroup per image) or spv_augment_tiled_u8 / spv_loader_fetch_augment_tiled (output tiles): one per call */
     SPV_PATH_TEACHER_VIEW = 23,  /* spv_teacher_view_u8 (the distillation teacher's 224 view, one workgroup per image and row band) */
     SPV_PATH_ATTN_V1 = 24,       /* spv_attention_fwd / _bwd served by the general kernels (attn_*_kernel): one per call */
     SPV_PATH_ATTN_V2 = 25,       /* ... by the LDS-staged kernels (attn2_*_kernel; head dim 16 / 32 / 64) */
@@ -918,6 +918,29 @@ int spv_loader_fetch_augment(const unsigned char* src_nhwc, const void* labels_s
                              float* params, float* out_nchw, const float* mean, const float* inv_std, const spv_augment_cfg* cfg, int n,
                              int batch, int chans, int height, int width, int world, int rank, int steps_per_epoch, uint64_t loader_seed,
                              int shuffle, int label_dtype, uint64_t augment_seed, void* stream);
+/* The same for the tiled sizes (64 x 64 ... 224 x 224 ... 512 x 512): what spv_loader_fetch(SPV_LOADER_NONE) at the cursor's step t,
+ * spv_augment_params(step = t) and spv_augment_tiled_u8 do one after the other, bit for bit in index, labels, params and out_nchw, as
+ * TWO launches on `stream`, neither with a by-value step.
+ * (1) The pre-pass's grid: 256-thread workgroup (image b, chunk k of 4096 / width rows), batch * parts workgroups.  EVERY workgroup
+ *     reads t from the cursor block (the protocol above, groups = batch * parts; the last one to arrive stores t + 1), works out its OWN
+ *     sample's row of the set under `loader_seed` and draws its OWN table row with key (augment_seed, t, b) -- both pass to the other
+ *     threads through LDS, never through global memory: within a launch a sibling workgroup's writes to `index` / `params` are not
+ *     visible -- and writes the partial sum workspace[b][k] with spv_augment_tiled_u8's summation (one definition, the same bits).
+ *     Chunk 0 of an image writes index[b], labels[b] and params[b] (16-byte aligned) at their fixed addresses.  A workgroup whose
+ *     sample has contrast factor exactly 1 writes no partial but reads t and arrives like every other.
+ * (2) spv_augment_tiled_u8's tile kernel, unchanged, on index / params / workspace.
+ * spv_loader_augment_tiled_supported: 1 for chans 1 or 3 and 2 <= height, width <= 512 -- the shapes with spv_augment_plan >= 1 inside
+ * the loader's sides (a 32 x 32 image may be forced through it; the result is spv_augment_tiled_u8's, not spv_augment_u8's).
+ * workspace: spv_augment_tiled_ws_bytes(batch, height, width) bytes, 4-byte aligned, at an address that stays valid while a captured
+ * call is replayed.  Refused on the host, before any launch: everything spv_loader_fetch refuses in its float mode (out_nchw as img),
+ * everything spv_augment_params refuses, everything spv_augment_tiled_u8 refuses (shape, out_nchw not 4-byte aligned, workspace
+ * missing, too small or misaligned, too large a grid).  Counts ONE SPV_PATH_AUGMENT per call. */
+int spv_loader_augment_tiled_supported(int chans, int height, int width);
+int spv_loader_fetch_augment_tiled(const unsigned char* src_nhwc, const void* labels_src, void* cursor, int64_t* index, int64_t* labels,
+                                   float* params, float* out_nchw, const float* mean, const float* inv_std, const spv_augment_cfg* cfg,
+                                   int n, int batch, int chans, int height, int width, int world, int rank, int steps_per_epoch,
+                                   uint64_t loader_seed, int shuffle, int label_dtype, uint64_t augment_seed, void* workspace,
+                                   size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

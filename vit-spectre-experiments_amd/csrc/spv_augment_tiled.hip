@@ -2,9 +2,12 @@
 // 512 x 512): the same definition, parameter table and random stream (include/spv.h).  Up to the rotation the
 // chain is a per-pixel function of (source pixel, parameter row, contrast mean), so a tile evaluates it at the gathered source position;
 // the two non-local things are the contrast mean (a pre-pass of per-workgroup partial sums, folded in a fixed order by every tile) and
-// the 3 x 3 blur (a one-pixel halo round the tile, in LDS).
+// the 3 x 3 blur (a one-pixel halo round the tile, in LDS).  At the end of the file the resident loader's fetch, the draw and the
+// pre-pass as ONE kernel that reads the step from the loader's device cursor (spv_loader_fetch_augment_tiled).
 #include "spv_common.h"
 #include "spv_augment_core.h"
+#include "spv_augment_draw.h"   // the fused fetch: the draw of a table row and its host checks
+#include "spv_loader_core.h"    // the fused fetch: the sample order and the cursor's protocol
 #include <limits.h>
 
 constexpr int AUGT_THREADS = 256;
@@ -61,14 +64,12 @@ __device__ __forceinline__ void load_pixel(const unsigned char* __restrict__ img
 // ---------------------------------------------------------------- the contrast mean's partial sums
 // Workgroup (image b, chunk k) sums the grey values (after the ops in front of contrast) of rows [k rows, (k + 1) rows) and writes
 // ws[b][k].  A flip permutes a row and is left out.  fp32 only over a thread's <= 16 pixels, a wave, the four waves; no atomics.
+// ONE definition of a workgroup's partial, for the pre-pass below and for the fused fetch at the end of this file: `p` is the sample's
+// table row (global memory there, LDS here), `row` its row of the set, `out` = &ws[b][k], `red` four LDS floats.
 template <int C>
-__global__ __launch_bounds__(AUGT_THREADS) void augment_mean_kernel(const unsigned char* __restrict__ src, const int64_t* __restrict__ index,
-                                                                    const float* __restrict__ params, float* __restrict__ ws, int n_src,
-                                                                    int H, int W, int rows, int parts) {
-    __shared__ float red[4];
-    const int b = blockIdx.x / parts, k = blockIdx.x - b * parts, tid = threadIdx.x;
-    const float* p = params + (size_t)b * SPV_AUG_NPARAM;
-    const int64_t row = index != nullptr ? index[b] : (int64_t)b;
+__device__ __forceinline__ void aug_mean_part(const unsigned char* __restrict__ src, int64_t row, const float* p, float* __restrict__ out,
+                                              float* red, int n_src, int H, int W, int rows, int k) {
+    const int tid = threadIdx.x;
     // workgroup uniform: f x + (1 - f) m is x at f == 1, and a poisoned image reads nothing; the tile kernel skips the fold alike
     if (p[SPV_AUG_CONTRAST] == 1.0f || row < 0 || row >= (int64_t)n_src) return;
     const AugSample s = aug_sample(p);
@@ -83,7 +84,17 @@ __global__ __launch_bounds__(AUGT_THREADS) void augment_mean_kernel(const unsign
     part = wave_sum(part);
     if ((tid & 63) == 0) red[tid >> 6] = part;
     __syncthreads();
-    if (tid == 0) ws[(size_t)b * parts + k] = (red[0] + red[1]) + (red[2] + red[3]);
+    if (tid == 0) *out = (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+template <int C>
+__global__ __launch_bounds__(AUGT_THREADS) void augment_mean_kernel(const unsigned char* __restrict__ src, const int64_t* __restrict__ index,
+                                                                    const float* __restrict__ params, float* __restrict__ ws, int n_src,
+                                                                    int H, int W, int rows, int parts) {
+    __shared__ float red[4];
+    const int b = blockIdx.x / parts, k = blockIdx.x - b * parts;
+    const int64_t row = index != nullptr ? index[b] : (int64_t)b;
+    aug_mean_part<C>(src, row, params + (size_t)b * SPV_AUG_NPARAM, ws + (size_t)b * parts + k, red, n_src, H, W, rows, k);
 }
 
 // ---------------------------------------------------------------- the tile kernel
@@ -242,44 +253,156 @@ __global__ __launch_bounds__(AUGT_THREADS) void augment_tile_kernel(const unsign
     }
 }
 
+// ---------------------------------------------------------------- host: what both entry points check and launch
+static int tiled_check(const char* name, const unsigned char* src_nhwc, const int64_t* index, const float* params, const float* mean,
+                       const float* inv_std, const float* out_nchw, int batch, int n_src, int chans, int height, int width,
+                       const void* workspace, size_t workspace_bytes) {
+    SPV_CHECK(batch > 0 && n_src > 0 && chans > 0 && height > 0 && width > 0, "%s: bad shape", name);
+    SPV_CHECK(tiled_takes(chans, height, width), "%s: a %d x %d x %d image is not supported (1 or 3 channels, height and width in [2, %d])",
+              name, chans, height, width, AUGT_MAX_SIDE);
+    SPV_CHECK(src_nhwc != nullptr && out_nchw != nullptr, "%s: src / out missing", name);
+    SPV_CHECK(params != nullptr, "%s: params missing", name);
+    SPV_CHECK(mean != nullptr && inv_std != nullptr, "%s: mean / inv_std missing", name);
+    SPV_CHECK(index != nullptr || batch <= n_src, "%s: index == NULL reads rows 0..batch-1, but batch=%d > n_src=%d", name, batch, n_src);
+    SPV_CHECK(((uintptr_t)out_nchw & 3) == 0 && ((uintptr_t)params & 3) == 0, "%s: out / params must be 4-byte aligned", name);
+    const size_t need = spv_augment_tiled_ws_bytes(batch, height, width);
+    SPV_CHECK(workspace != nullptr && workspace_bytes >= need,
+              "%s: workspace missing or too small (%zu bytes, spv_augment_tiled_ws_bytes asks for %zu)", name,
+              workspace == nullptr ? (size_t)0 : workspace_bytes, need);
+    SPV_CHECK(((uintptr_t)workspace & 3) == 0, "%s: workspace must be 4-byte aligned", name);
+    static_assert(AUGT_MAX_PARTS >= AUGT_MAX_SIDE / (AUGT_MEAN_PIXELS / AUGT_MAX_SIDE), "the fold is at most 64 additions");
+    const int64_t tiles = (int64_t)cdiv(width, AUGT_TW) * cdiv(height, AUGT_TH);
+    SPV_CHECK((int64_t)batch * tiles <= INT_MAX && (int64_t)batch * mean_parts(height, width) <= INT_MAX, "%s: batch=%d is too large a grid",
+              name, batch);
+    return 0;
+}
+
+static void launch_tiles(const unsigned char* src_nhwc, const int64_t* index, const float* params, const float* mean, const float* inv_std,
+                         const float* ws, float* out_nchw, int batch, int n_src, int chans, int height, int width, hipStream_t st) {
+    const int parts = mean_parts(height, width);
+    const int tiles_x = cdiv(width, AUGT_TW), tiles = tiles_x * cdiv(height, AUGT_TH);
+    const int vec = width % 4 == 0 && ((uintptr_t)out_nchw & 15) == 0;
+    if (chans == 3)
+        hipLaunchKernelGGL(augment_tile_kernel<3>, dim3(batch * tiles), dim3(AUGT_THREADS), 0, st, src_nhwc, index, params, mean, inv_std, ws,
+                           out_nchw, n_src, height, width, tiles_x, tiles, parts, vec);
+    else
+        hipLaunchKernelGGL(augment_tile_kernel<1>, dim3(batch * tiles), dim3(AUGT_THREADS), 0, st, src_nhwc, index, params, mean, inv_std, ws,
+                           out_nchw, n_src, height, width, tiles_x, tiles, parts, vec);
+}
+
 extern "C" int spv_augment_tiled_u8(const unsigned char* src_nhwc, const int64_t* index, const float* params, const float* mean,
                                     const float* inv_std, float* out_nchw, int batch, int n_src, int chans, int height, int width,
                                     void* workspace, size_t workspace_bytes, void* stream) {
-    SPV_CHECK(batch > 0 && n_src > 0 && chans > 0 && height > 0 && width > 0, "spv_augment_tiled_u8: bad shape");
-    SPV_CHECK(tiled_takes(chans, height, width),
-              "spv_augment_tiled_u8: a %d x %d x %d image is not supported (1 or 3 channels, height and width in [2, %d])", chans, height,
-              width, AUGT_MAX_SIDE);
-    SPV_CHECK(src_nhwc != nullptr && out_nchw != nullptr, "spv_augment_tiled_u8: src / out missing");
-    SPV_CHECK(params != nullptr, "spv_augment_tiled_u8: params missing");
-    SPV_CHECK(mean != nullptr && inv_std != nullptr, "spv_augment_tiled_u8: mean / inv_std missing");
-    SPV_CHECK(index != nullptr || batch <= n_src, "spv_augment_tiled_u8: index == NULL reads rows 0..batch-1, but batch=%d > n_src=%d", batch,
-              n_src);
-    SPV_CHECK(((uintptr_t)out_nchw & 3) == 0 && ((uintptr_t)params & 3) == 0, "spv_augment_tiled_u8: out / params must be 4-byte aligned");
-    const size_t need = spv_augment_tiled_ws_bytes(batch, height, width);
-    SPV_CHECK(workspace != nullptr && workspace_bytes >= need,
-              "spv_augment_tiled_u8: workspace missing or too small (%zu bytes, spv_augment_tiled_ws_bytes asks for %zu)",
-              workspace == nullptr ? (size_t)0 : workspace_bytes, need);
-    SPV_CHECK(((uintptr_t)workspace & 3) == 0, "spv_augment_tiled_u8: workspace must be 4-byte aligned");
+    if (int rc = tiled_check("spv_augment_tiled_u8", src_nhwc, index, params, mean, inv_std, out_nchw, batch, n_src, chans, height, width,
+                             workspace, workspace_bytes))
+        return rc;
     const int parts = mean_parts(height, width), rows = mean_rows(width);
-    const int tiles_x = cdiv(width, AUGT_TW), tiles = tiles_x * cdiv(height, AUGT_TH);
-    static_assert(AUGT_MAX_PARTS >= AUGT_MAX_SIDE / (AUGT_MEAN_PIXELS / AUGT_MAX_SIDE), "the fold is at most 64 additions");
-    SPV_CHECK((int64_t)batch * tiles <= INT_MAX && (int64_t)batch * parts <= INT_MAX, "spv_augment_tiled_u8: batch=%d is too large a grid",
-              batch);
-    const int vec = width % 4 == 0 && ((uintptr_t)out_nchw & 15) == 0;
     float* ws = static_cast<float*>(workspace);
     hipStream_t st = static_cast<hipStream_t>(stream);
-    if (chans == 3) {
+    if (chans == 3)
         hipLaunchKernelGGL(augment_mean_kernel<3>, dim3(batch * parts), dim3(AUGT_THREADS), 0, st, src_nhwc, index, params, ws, n_src, height,
                            width, rows, parts);
-        hipLaunchKernelGGL(augment_tile_kernel<3>, dim3(batch * tiles), dim3(AUGT_THREADS), 0, st, src_nhwc, index, params, mean, inv_std, ws,
-                           out_nchw, n_src, height, width, tiles_x, tiles, parts, vec);
-    } else {
+    else
         hipLaunchKernelGGL(augment_mean_kernel<1>, dim3(batch * parts), dim3(AUGT_THREADS), 0, st, src_nhwc, index, params, ws, n_src, height,
                            width, rows, parts);
-        hipLaunchKernelGGL(augment_tile_kernel<1>, dim3(batch * tiles), dim3(AUGT_THREADS), 0, st, src_nhwc, index, params, mean, inv_std, ws,
-                           out_nchw, n_src, height, width, tiles_x, tiles, parts, vec);
-    }
+    launch_tiles(src_nhwc, index, params, mean, inv_std, ws, out_nchw, batch, n_src, chans, height, width, st);
     SPV_LAUNCH_CHECK("spv_augment_tiled_u8");
     SPV_COUNT_PATH(SPV_PATH_AUGMENT);
     return 0;
 }
+
+// ---------------------------------------------------------------- fetch, draw and pre-pass in one launch
+// spv_loader_fetch(mode none) at the cursor's step t, spv_augment_params(step = t) and the pre-pass above as ONE launch on the
+// pre-pass's grid, then the tile kernel unchanged: nothing of either launch is a by-value function of the step, so a captured pair
+// draws a new batch AND a new table at every replay.
+struct TiledFetchArgs {
+    const unsigned char* src;     // [n][H][W][C]
+    const void* labels_src;       // [n] uint8 or int64
+    unsigned long long* cursor;   // the loader's cursor block
+    int64_t* index;               // [batch]
+    int64_t* labels;              // [batch]
+    float* params;                // [batch][16]
+    float* ws;                    // [batch][parts]
+    uint64_t loader_seed, augment_seed;
+    LdrGeom g;
+    spv_augment_cfg cfg;
+    int H, W, rows, parts, label_i64;
+};
+
+// Workgroup (image b, chunk k).  Thread 0 reads the step and hands it round; the sample's row of the set (wave 0) and its table row
+// (wave 1) -- functions of (t, b) alone, so all `parts` workgroups of an image work out the same two -- go round through LDS, never
+// through `index` / `params` in global memory: what a sibling workgroup writes there is not visible inside the launch.  Chunk 0 records
+// them for the tile kernel and the caller.  Wave 2 takes the ticket behind the read of t (it came through LDS and two barriers, so the
+// load has returned: no fence); EVERY workgroup takes one, also the one whose contrast factor is 1 and whose partial nobody reads --
+// the early return sits inside aug_mean_part, behind the ticket.
+template <int C>
+__global__ __launch_bounds__(AUGT_THREADS) void loader_mean_kernel(TiledFetchArgs a) {
+    __shared__ __attribute__((aligned(16))) float row_sh[SPV_AUG_NPARAM];
+    __shared__ unsigned long long t_sh;
+    __shared__ uint32_t idx_sh;
+    __shared__ float red[4];
+    const uint32_t b = blockIdx.x / (uint32_t)a.parts;
+    const int k = (int)(blockIdx.x - b * (uint32_t)a.parts), tid = threadIdx.x;
+    if (tid == 0) t_sh = ldr_read_step(a.cursor);
+    __syncthreads();
+    const uint64_t t = t_sh;
+    if (tid == 0) {
+        const uint32_t idx = ldr_index(a.loader_seed, t, b, a.g);   // < n by construction (spv_loader_core.h)
+        if (k == 0) {
+            a.index[b] = (int64_t)idx;
+            a.labels[b] = a.label_i64 ? static_cast<const int64_t*>(a.labels_src)[idx]
+                                      : (int64_t) static_cast<const unsigned char*>(a.labels_src)[idx];
+        }
+        idx_sh = idx;
+    } else if (tid == 64) {
+        const AugRow r = aug_draw(a.H, a.W, a.cfg, a.augment_seed, t, b);
+        if (k == 0) aug_store_row(a.params, b, r);
+#pragma unroll
+        for (int i = 0; i < SPV_AUG_NPARAM; ++i) row_sh[i] = r.v[i];
+    }
+    __syncthreads();
+    if (tid == 128) ldr_arrive<false>(a.cursor, t, a.g.batch * (unsigned)a.parts);   // groups = batch * parts: the whole grid
+    aug_mean_part<C>(a.src, (int64_t)idx_sh, row_sh, a.ws + (size_t)b * a.parts + k, red, (int)a.g.n, a.H, a.W, a.rows, k);
+}
+
+extern "C" int spv_loader_augment_tiled_supported(int chans, int height, int width) { return tiled_takes(chans, height, width) ? 1 : 0; }
+
+extern "C" int spv_loader_fetch_augment_tiled(const unsigned char* src_nhwc, const void* labels_src, void* cursor, int64_t* index,
+                                              int64_t* labels, float* params, float* out_nchw, const float* mean, const float* inv_std,
+                                              const spv_augment_cfg* cfg, int n, int batch, int chans, int height, int width, int world,
+                                              int rank, int steps_per_epoch, uint64_t loader_seed, int shuffle, int label_dtype,
+                                              uint64_t augment_seed, void* workspace, size_t workspace_bytes, void* stream) {
+    const char* name = "spv_loader_fetch_augment_tiled";
+    // the fetch's refusals (as its float mode: src, img, mean and inv_std are all read), then the draw's, then the tiled apply's
+    if (int rc = spv_loader_check(name, src_nhwc, labels_src, cursor, index, labels, out_nchw, mean, inv_std, n, batch, chans, height, width,
+                                  world, rank, steps_per_epoch, SPV_LOADER_FLOAT, label_dtype))
+        return rc;
+    if (int rc = aug_draw_check(name, params, cfg, batch, chans, height, width)) return rc;
+    if (int rc = tiled_check(name, src_nhwc, index, params, mean, inv_std, out_nchw, batch, n, chans, height, width, workspace, workspace_bytes))
+        return rc;
+    TiledFetchArgs a;
+    a.src = src_nhwc;
+    a.labels_src = labels_src;
+    a.cursor = static_cast<unsigned long long*>(cursor);
+    a.index = index;
+    a.labels = labels;
+    a.params = params;
+    a.ws = static_cast<float*>(workspace);
+    a.loader_seed = loader_seed;
+    a.augment_seed = augment_seed;
+    a.g = LdrGeom{(uint32_t)n, (uint32_t)batch, (uint32_t)world, (uint32_t)rank, (uint32_t)steps_per_epoch, shuffle != 0};
+    a.cfg = *cfg;
+    a.H = height;
+    a.W = width;
+    a.rows = mean_rows(width);
+    a.parts = mean_parts(height, width);
+    a.label_i64 = label_dtype == SPV_LOADER_LABEL_I64;
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    if (chans == 3) hipLaunchKernelGGL(loader_mean_kernel<3>, dim3(batch * a.parts), dim3(AUGT_THREADS), 0, st, a);
+    else hipLaunchKernelGGL(loader_mean_kernel<1>, dim3(batch * a.parts), dim3(AUGT_THREADS), 0, st, a);
+    launch_tiles(src_nhwc, index, params, mean, inv_std, a.ws, out_nchw, batch, n, chans, height, width, st);
+    SPV_LAUNCH_CHECK(name);
+    SPV_COUNT_PATH(SPV_PATH_AUGMENT);
+    return 0;
+}
+

@@ -16,6 +16,9 @@ network with cycle-walking, include/spv.h "the resident loader"), sharded over t
 ``output="augment"`` with ``augment=TrainAugment(...)`` fetches AND augments in that one launch (``spv_loader_fetch_augment``,
 csrc/spv_augment.hip): the transform's parameter table is drawn on the device under the key (augment seed, the cursor's step, slot), so
 a captured fetch draws a new table at every replay; ``loader.params`` holds the step's table, ``loader.img`` the augmented batch.
+``output="augment_tiled"`` is the same for the images that launch cannot stage, 64 x 64 up to 512 x 512 (``spv_loader_fetch_augment_tiled``,
+csrc/spv_augment_tiled.hip): the fetch and the draw ride in the tiled chain's contrast pre-pass, the tile kernel follows -- two launches,
+neither with a by-value step, so ``fetch()`` is as capturable.
 """
 from __future__ import annotations
 
@@ -34,7 +37,8 @@ _U64 = (1 << 64) - 1
 _GOLDEN = 0x9E3779B97F4A7C15
 ROUNDS = 6          # SPV_LOADER_ROUNDS
 _MODES = {"none": 0, "float": 1, "uint8": 2}   # SPV_LOADER_NONE / _FLOAT / _UINT8
-_OUTPUTS = tuple(_MODES) + ("augment",)        # "augment": the fused launch, spv_loader_fetch_augment
+_FUSED = {"augment": "spv_loader_fetch_augment", "augment_tiled": "spv_loader_fetch_augment_tiled"}   # fetch and augment in one call
+_OUTPUTS = tuple(_MODES) + tuple(_FUSED)
 
 
 def _mix64(x):
@@ -86,8 +90,11 @@ class ResidentLoader:
                     "none": no image -- hand ``index`` to ``TrainAugment`` or to ``DistillationLoss(index=)``;
                     "augment": ``img`` fp32 (B, C, H, W) = ``augment``'s chain on the step's rows, its table drawn at the cursor's
                     step, and ``params`` fp32 (B, 16) = that table -- ``augment(images, index, step=t)`` and
-                    ``augment.draw(B, step=t, ...)`` bit for bit, in the same launch as the fetch
-    augment         with output="augment" only: the ``spectre_vit.augment.TrainAugment`` whose mean / std, ranges and seed the launch
+                    ``augment.draw(B, step=t, ...)`` bit for bit, in the same launch as the fetch;
+                    "augment_tiled": the same buffers from the tiled chain (``TrainAugment(kernel="tiled")``'s bits), for 1 or 3
+                    channels and sides 2 .. 512: fetch, draw and contrast pre-pass in one launch, then the tile kernel; the loader
+                    owns the pre-pass's workspace at a fixed address
+    augment         with output="augment" / "augment_tiled" only: the ``spectre_vit.augment.TrainAugment`` whose mean / std, ranges and seed the launch
                     takes (``mean`` / ``std`` here are unused); images the fused kernel cannot stage -- the tiled sizes, and the one
                     LDS border shape -- are refused: output="none", then ``augment(images, loader.index, step=...)`` serves them
     rank, world     this process's shard: position p of the epoch's order belongs to rank p mod world.  Every rank passes the SAME
@@ -105,14 +112,16 @@ class ResidentLoader:
         x = images_u8_nhwc
         if output not in _OUTPUTS:
             raise ValueError(f"output is one of {_OUTPUTS}, got {output!r}")
-        if augment is not None and output != "augment":
+        if augment is not None and output not in _FUSED:
             raise ValueError(f"augment= goes with output='augment' (the fused fetch), not with output={output!r}")
-        if output == "augment":
+        if output in _FUSED:
             from spectre_vit.augment import TrainAugment
             if not isinstance(augment, TrainAugment):
-                raise ValueError(f"output='augment' needs augment=TrainAugment(...), got {augment!r}")
-            if augment.kernel == "tiled":
+                raise ValueError(f"output={output!r} needs augment=TrainAugment(...), got {augment!r}")
+            if output == "augment" and augment.kernel == "tiled":
                 raise ValueError("output='augment' runs the whole-image LDS chain: not with TrainAugment(kernel='tiled')")
+            if output == "augment_tiled" and augment.kernel == "lds":
+                raise ValueError("output='augment_tiled' runs the tiled chain: not with TrainAugment(kernel='lds')")
         if not isinstance(x, torch.Tensor) or x.dtype != torch.uint8 or x.dim() != 4 or not x.is_contiguous():
             raise TypeError("the resident loader takes a contiguous uint8 (N, H, W, C) set, got "
                             f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
@@ -131,9 +140,11 @@ class ResidentLoader:
                                  f"{0 if std is None else len(std)} channels")
             if min(float(s) for s in std) <= 0.0:
                 raise ValueError(f"std must be positive, got {tuple(std)}")
+        if output in _FUSED and len(augment.mean) != C:
+            raise ValueError(f"{C}-channel images, but the TrainAugment's mean / std name {len(augment.mean)} channels")
+        if output == "augment_tiled" and not _native.call("spv_loader_augment_tiled_supported", C, H, W):   # a host predicate
+            raise ValueError(f"a {C} x {H} x {W} image is outside the tiled fetch's shapes (1 or 3 channels, height and width 2 .. 512)")
         if output == "augment":
-            if len(augment.mean) != C:
-                raise ValueError(f"{C}-channel images, but the TrainAugment's mean / std name {len(augment.mean)} channels")
             if not _native.call("spv_loader_augment_supported", C, H, W):   # a host predicate: no device is touched
                 raise ValueError(f"a {C} x {H} x {W} image does not fit the fused fetch's LDS staging (two fp32 copies, the reduction "
                                  "slots and 80 bytes of hand-over within 64 KiB): use output='none', then "
@@ -162,9 +173,9 @@ class ResidentLoader:
         self.shuffle = bool(shuffle)
         self.output = output
         dev = x.device
-        self.mean = self.inv_std = self.params = None
+        self.mean = self.inv_std = self.params = self._ws = None
         self.augment = augment
-        if output == "augment":
+        if output in _FUSED:
             self.mean, self.inv_std = augment.norm(dev)
             self.params = torch.zeros((batch_size, 16), dtype=torch.float32, device=dev)   # SPV_AUG_NPARAM
             self._cfg = augment.cfg()   # a host struct read during each call: kept alive here
@@ -174,17 +185,21 @@ class ResidentLoader:
         self.img = {"float": lambda: torch.empty((batch_size, C, H, W), dtype=torch.float32, device=dev),
                     "uint8": lambda: torch.empty((batch_size, H, W, C), dtype=torch.uint8, device=dev),
                     "augment": lambda: torch.empty((batch_size, C, H, W), dtype=torch.float32, device=dev),
+                    "augment_tiled": lambda: torch.empty((batch_size, C, H, W), dtype=torch.float32, device=dev),
                     "none": lambda: None}[output]()
         self.index = torch.zeros(batch_size, dtype=torch.int64, device=dev)
         self.labels = torch.zeros(batch_size, dtype=torch.int64, device=dev)
         self._cursor = torch.zeros(int(_native.call("spv_loader_cursor_bytes")) // 8, dtype=torch.int64, device=dev)
         self.step = 0
         label_dtype = 1 if labels.dtype == torch.int64 else 0
-        if output == "augment":
-            self._entry = "spv_loader_fetch_augment"
+        if output in _FUSED:
+            self._entry = _FUSED[output]
             self._args = (_p(x), _p(labels), _p(self._cursor), _p(self.index), _p(self.labels), _p(self.params), _p(self.img),
                           _p(self.mean), _p(self.inv_std), ctypes.addressof(self._cfg), n, batch_size, C, H, W, world, rank,
                           self.steps_per_epoch, self.seed, int(self.shuffle), label_dtype, augment.seed)
+            if output == "augment_tiled":   # the contrast pre-pass's partial sums: written and read inside every fetch
+                self._ws = torch.empty(_native.call("spv_augment_tiled_ws_bytes", batch_size, H, W), dtype=torch.uint8, device=dev)
+                self._args += (_p(self._ws), self._ws.numel())
         else:
             self._entry = "spv_loader_fetch"
             self._args = (_p(x), _p(labels), _p(self._cursor), _p(self.index), _p(self.labels), _p(self.img), _p(self.mean),
@@ -193,7 +208,7 @@ class ResidentLoader:
 
     # -- the launch -------------------------------------------------------------------------------------------------------------
     def fetch(self):
-        """ONE launch on the current stream: the buffers take the batch of the cursor's step, the cursor moves on.  Allocates
+        """ONE launch (output="augment_tiled": two) on the current stream: the buffers take the batch of the cursor's step, the cursor moves on.  Allocates
         nothing and uploads nothing, so it may be captured; a captured (recorded, not run) fetch is not counted in ``step``."""
         _native.call(self._entry, *self._args, _stream())
         if not torch.cuda.is_current_stream_capturing():

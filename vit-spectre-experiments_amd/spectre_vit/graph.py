@@ -72,17 +72,22 @@ def _release_seed_word(obj):
         _seed_owner = None
 
 
+def _check_loader(name, loader, example_img, example_labels):
+    """the refusals of every loader-fed step, raised before a device is touched"""
+    if loader.img is None:
+        raise ValueError(f"{name}(loader=...): the loader has no image output (output='none'); fetch eagerly, "
+                         "build the images from loader.index and feed the step instead")
+    if example_img is not None or example_labels is not None:
+        raise ValueError(f"{name}(loader=...): the batch comes from the loader, pass example_img = example_labels = None")
+
+
 class GraphedTrainStep:
     _dp = False
 
     def __init__(self, model, optimizer, criterion, example_img, example_labels, autocast_dtype=torch.bfloat16, warmup=3,
                  return_features=False, process_group=None, force_collective=False, loader=None):
         if loader is not None:
-            if loader.img is None:
-                raise ValueError(f"{type(self).__name__}(loader=...): the loader has no image output (output='none'); fetch eagerly, "
-                                 "build the images from loader.index and feed the step instead")
-            if example_img is not None or example_labels is not None:
-                raise ValueError(f"{type(self).__name__}(loader=...): the batch comes from the loader, pass example_img = example_labels = None")
+            _check_loader(type(self).__name__, loader, example_img, example_labels)
         elif not example_img.is_cuda:
             raise RuntimeError(f"{type(self).__name__} needs the example batch on the GPU")
         for g in optimizer.param_groups:
@@ -115,9 +120,14 @@ class GraphedTrainStep:
             self.close()
             raise
 
+    @property
+    def fetch_in_graph(self):
+        """the loader's fetch is a node of the captured step (a replay is then counted as one fetch)"""
+        return self.loader is not None
+
     # -- the two halves of a step -----------------------------------------------------------------------------------------------
     def _forward_backward(self):
-        if self.loader is not None:
+        if self.fetch_in_graph:
             self.loader.fetch()   # the first node: this step's batch into self.img / self.labels, the device cursor moved on
         # ONE launch: the seed word's advance and whatever else of the forward's opening depends on nothing but the parameters and
         # the image buffer (hip_ops.step_prologue); the nodes concerned pick their results up instead of launching
@@ -179,7 +189,7 @@ class GraphedTrainStep:
             self.labels.copy_(labels, non_blocking=True)
         self._replay()
         self.replays += 1
-        if self.loader is not None:
+        if self.fetch_in_graph:
             self.loader.count_replay()
         # the replay updated the weights through raw pointers: neither the parameters' version counters nor the optimizer's post-step
         # hook saw it, so the inference-time cache of bf16 weight copies (shadows._ShadowCache) must be told
@@ -249,15 +259,36 @@ class GraphedDistillStep(GraphedTrainStep):
         step = GraphedDistillStep(model, optimizer, DistillationLoss(), img, labels, teacher_cache=cache, example_index=sel)
         loss = step(img, labels, index=sel)
 
+    ``loader=`` (a ``spectre_vit.data.ResidentLoader`` with an image output; pass example_img = example_labels = None and no
+    example_index): the step's image and label buffers ARE the loader's.
+
+    cached teacher -- the loss's index buffer IS ``loader.index`` and ``loader.fetch()`` is the graph's first node: a step is one replay,
+    with no index copy and no host-issued work in front of it (every warm-up step consumes one loader step, the capture none):
+
+        step = GraphedDistillStep(model, optimizer, DistillationLoss(), None, None, teacher_cache=cache, loader=loader)
+        loss = step()                                 # step.img / step.labels / step.index: the batch that replay trained on
+
+    teacher logits per step -- the teacher needs the batch's index BEFORE the replay, so the fetch is NOT captured; the caller fetches,
+    runs the view and the teacher on ``loader.index`` and replays a graph that reads the loader's buffers (the first batch is fetched
+    before the step is built: its warm-up trains on it):
+
+        loader.fetch()
+        step = GraphedDistillStep(model, optimizer, DistillationLoss(), None, None, teacher_logits_of(loader.index), loader=loader)
+        loader.fetch(); loss = step(teacher_logits=teacher_logits_of(loader.index))
+
     Single process only: a graph-replayed data-parallel distillation rank is not built."""
 
     def __init__(self, model, optimizer, criterion, example_img, example_labels, example_teacher_logits=None, autocast_dtype=None, warmup=3,
-                 process_group=None, *, teacher_cache=None, example_index=None):
+                 process_group=None, *, teacher_cache=None, example_index=None, loader=None):
         import torch.distributed as dist
+        if loader is not None:
+            _check_loader("GraphedDistillStep", loader, example_img, example_labels)
+            if example_index is not None:
+                raise ValueError("GraphedDistillStep(loader=...): the loss reads the teacher cache through loader.index, pass no example_index")
         if (example_teacher_logits is None) == (teacher_cache is None):
             raise ValueError("GraphedDistillStep takes example_teacher_logits (the teacher runs in front of every replay) or "
                              "teacher_cache (its logits are resident), one of the two")
-        if (teacher_cache is None) != (example_index is None):
+        if loader is None and (teacher_cache is None) != (example_index is None):
             raise ValueError("GraphedDistillStep: teacher_cache and example_index go together")
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
             raise RuntimeError("GraphedDistillStep is the single-process step: GraphedDPStep is not built for distillation "
@@ -265,15 +296,24 @@ class GraphedDistillStep(GraphedTrainStep):
         self.teacher_cache = teacher_cache
         if teacher_cache is None:
             self.teacher_logits, self.index = example_teacher_logits.detach().clone(), None
+        elif loader is not None:   # the loader's fixed-address index is the loss's
+            self.teacher_logits, self.index = None, loader.index
         else:
             if example_index.dtype != torch.int64 or example_index.shape != example_labels.shape[:1]:
                 raise ValueError(f"GraphedDistillStep: example_index is an int64 vector of the batch's {example_labels.shape[0]} rows, got "
                                  f"{example_index.dtype} {tuple(example_index.shape)}")
             self.teacher_logits, self.index = None, example_index.detach().clone()
         super().__init__(model, optimizer, criterion, example_img, example_labels, autocast_dtype=autocast_dtype, warmup=warmup,
-                         process_group=process_group)
+                         process_group=process_group, loader=loader)
+
+    @property
+    def fetch_in_graph(self):
+        """cache mode only: with a teacher in front of the replay the caller fetches eagerly (the teacher's view needs the index)"""
+        return self.loader is not None and self.teacher_cache is not None
 
     def _forward_backward(self):
+        if self.fetch_in_graph:
+            self.loader.fetch()   # the first node: this step's batch into self.img / self.labels / self.index
         _native.call("spv_seed_advance", self.seed_word.data_ptr(), torch.cuda.current_stream().cuda_stream)
         self.reducer.zero_grad()
         with torch.autocast("cuda", dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None):
@@ -300,6 +340,8 @@ class GraphedDistillStep(GraphedTrainStep):
                     raise ValueError("this step reads the teacher cache: pass index=, not teacher logits")
                 self.teacher_logits.copy_(teacher_logits, non_blocking=True)
             if index is not None:
+                if self.loader is not None:
+                    raise ValueError("this step reads the teacher cache through the loader's index (loader=...): pass no index")
                 if self.index is None:
                     raise ValueError("this step takes the teacher's logits per step: it was built without teacher_cache")
                 self.index.copy_(index, non_blocking=True)

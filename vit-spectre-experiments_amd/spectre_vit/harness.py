@@ -152,6 +152,18 @@ def _check_device_meter(device_meter, distill=False):
                          "path (train_distill has)")
 
 
+def _loader_output(augment, uint8_input, chans, height, width):
+    """the ResidentLoader output that serves a training set's shape: with augmentation the fused LDS fetch where it can stage the image,
+    the fused tiled fetch for the sizes only the tiled chain takes (spv_augment_plan == 2), and index and labels alone ("none": draw and
+    apply host-issued) for what is left -- the LDS border shape, whose whole-image chain the tiled kernels are not held to bit for bit"""
+    from spectre_vit import _native
+    if not augment:
+        return "uint8" if uint8_input else "float"
+    if _native.call("spv_loader_augment_supported", chans, height, width):
+        return "augment"
+    return "augment_tiled" if _native.call("spv_augment_plan", chans, height, width) == 2 else "none"
+
+
 def _check_device_loader(device_loader, distill=False):
     """raises before any device is touched"""
     if not isinstance(device_loader, bool):
@@ -246,9 +258,11 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     steps_per_epoch)), its seed loader_seed(config seed), its shard this rank's.  With graph=True the fetch is the first node of the
     step's graph, so a step is one replay and nothing else -- with augment=True too: the loader then fetches and augments in one
     launch (ResidentLoader(output="augment"): the table is keyed by the device cursor, which equals the global step, so the batches
-    are the bits TrainAugment(...)(set, loader.index, step=global_step) yields).  Only for images that launch cannot stage (the tiled
-    sizes, the LDS border shape) the loader fetches index and labels alone and TrainAugment takes loader.index, draw and apply
-    host-issued in front of the step (their step number is a by-value argument).
+    are the bits TrainAugment(...)(set, loader.index, step=global_step) yields), and for the sizes only the tiled chain takes (64 x 64
+    ... 224 x 224 ... 512 x 512) in two (output="augment_tiled": fetch, draw and contrast pre-pass, then the tile kernel), the same
+    bits again.  Only for the LDS border shape, which neither fused kernel serves with the whole-image chain's bits, the loader fetches
+    index and labels alone and TrainAugment takes loader.index, draw and apply host-issued in front of the step (their step number is
+    a by-value argument).
     The host then no longer knows a batch beforehand: batch_hook("train", step, img, label) is called AFTER the step, with the step's
     buffers (the loader's, or the augmented batch) -- valid until the next step overwrites them.  Validation is untouched.  The sample
     ORDER differs from the host randperm's (same distribution, another stream): hence a flag and not the default."""
@@ -314,15 +328,13 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         aug = TrainAugment(CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels], seed=augment_seed(seed, rank))
     if device_loader:
         from spectre_vit.data import ResidentLoader
-        # augment: fetch and augment in ONE launch where the fused kernel can stage the image (the table is then keyed by the loader's
-        # cursor, which equals global_step); otherwise index and labels only, draw and apply host-issued as without the loader
-        from spectre_vit import _native
+        # augment: fetch and augment in ONE call where a fused kernel takes the image (the table is then keyed by the loader's cursor,
+        # which equals global_step); otherwise index and labels only, draw and apply host-issued as without the loader
         H, W, C = train_nhwc.shape[1:]
-        fused = bool(augment and _native.call("spv_loader_augment_supported", C, H, W))
+        output = _loader_output(augment, uint8_input, C, H, W)
         loader = ResidentLoader(train_nhwc, train_set.labels, batch_size, CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels],
                                 seed=loader_seed(seed), rank=rank, world=world, steps_per_epoch=min(per_pass, steps_per_epoch or per_pass),
-                                output="augment" if fused else "none" if augment else ("uint8" if uint8_input else "float"),
-                                augment=aug if fused else None)
+                                output=output, augment=aug if output.startswith("augment") else None)
     host_aug = aug if loader is None or loader.output == "none" else None   # the transform the host still issues per batch
     loader_in_graph = loader is not None and graph and loader.img is not None   # the step fetches its own batch
 
@@ -481,7 +493,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                   use_amp=False, graph=False, augment=True, teacher=None, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75,
                   resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False,
                   lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False, ema_decay=None,
-                  ema_warmup=False, device_meter=False, cache_teacher=False, teacher_cache_path=None):
+                  ema_warmup=False, device_meter=False, device_loader=False, cache_teacher=False, teacher_cache_path=None):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -501,9 +513,20 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     fill calls batch_hook("teacher_fill", block, img_teacher, index)).  Eager, as a data-parallel rank, and graph=True.
     device_meter=True: as in train() -- the DistillationLoss carries a TrainMeter, the host issues no per-step stack / argmax / == / sum
     / accumulate, and the epoch's "Loss/Train", "Accuracy/Train", "Accuracy/TrainTop5" and the three per-batch loss lines come from
-    ONE read of the meter (its log rows hold each step's loss, soft and CE terms)."""
+    ONE read of the meter (its log rows hold each step's loss, soft and CE terms).
+    device_loader=True: as in train() -- the batches come from a spectre_vit.data.ResidentLoader (seed loader_seed(config seed), this
+    rank's shard, this loop's steps per epoch) whose output is picked by shape: "augment" / "augment_tiled" fetch and augment in one
+    call, "float" with augment=False; the one LDS border shape fetches index and labels alone and TrainAugment takes loader.index.
+    The loader's index serves the teacher's view and the cached loss directly.  With graph=True and cache_teacher=True the step is
+    GraphedDistillStep(loader=..., teacher_cache=...): the fetch is the graph's first node, the loss reads the cache through
+    loader.index, and a step is ONE replay with nothing host-issued in front of it.  Uncached, the teacher needs the index first: the
+    host fetches, runs the view and the teacher, and replays a graph that reads the loader's buffers.  The global step, the
+    augmentation's step and the loader's cursor stay equal.  batch_hook("train", step, img, label) is called AFTER the step with the
+    step's buffers (valid until the next fetch); the "teacher" hook keeps its place in front of the teacher.  The sample order is the
+    loader's, not the host randperm's."""
     from spectre_vit import _native
     _check_device_meter(device_meter)
+    _check_device_loader(device_loader)
     ema = _ema_args(ema_decay, ema_warmup)
     c = parse_config(config_path)
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -574,22 +597,50 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
         if rank == 0:
             log_f.write(json.dumps({"TeacherCache": cache_rec}) + "\n")
             log_f.flush()
+    loader = None
+    if device_loader:
+        from spectre_vit.data import ResidentLoader
+        H, W, C = train_nhwc.shape[1:]
+        output = _loader_output(augment, False, C, H, W)
+        loader = ResidentLoader(train_nhwc, train_set.labels, batch_size, mean, std, seed=loader_seed(seed), rank=rank, world=world,
+                                steps_per_epoch=epoch_steps, output=output, augment=aug if output.startswith("augment") else None)
+    loader_step = loader is not None and graph and loader.img is not None       # the graphed step reads the loader's buffers
+    loader_in_graph = loader_step and cache is not None                         # ... and fetches them itself: a step is one replay
+
+    def index_batches():
+        if loader is None:
+            yield from train_set.index_batches(batch_size, True, gen, rank, world)
+            return
+        for _ in range(loader.steps_per_epoch):
+            if loader_in_graph:
+                yield None
+                continue
+            loader.fetch()
+            yield loader.index
+
     for epoch in range(epochs):
         model.train()
         correct = torch.zeros((), device=device, dtype=torch.int64)
         batch_losses = torch.zeros((max(epoch_steps, 1), 3), device=device)   # (Train, Dist, CE) per step, read once per epoch
         first_step = global_step
         total, steps = 0, 0
-        for sel in train_set.index_batches(batch_size, True, gen, rank, world):
-            label = train_set.labels[sel]
-            if aug is not None:
-                img = aug(train_nhwc, sel, step=global_step)
+        for sel in index_batches():
+            if loader_in_graph:
+                img = label = None   # the replay fetches them
+            elif loader is not None:
+                label = loader.labels
+                img = loader.img if loader.img is not None else aug(train_nhwc, sel, step=global_step)
             else:
-                img = (train_set.images[sel].float() / 255.0 - train_set.mean) / train_set.std
+                label = train_set.labels[sel]
+                if aug is not None:
+                    img = aug(train_nhwc, sel, step=global_step)
+                else:
+                    img = (train_set.images[sel].float() / 255.0 - train_set.mean) / train_set.std
             if cache is None:
                 img_teacher = view(train_nhwc, sel)
             if batch_hook is not None:
-                batch_hook("train", global_step, img, label)
+                if loader is None:
+                    batch_hook("train", global_step, img, label)
                 if cache is None:
                     batch_hook("teacher", global_step, img_teacher, label)
             global_step += 1
@@ -600,13 +651,25 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
             if graph:
                 if gstep is None:   # built on the first batch; its warm-up step WAS this batch's training step
                     from spectre_vit.graph import GraphedDistillStep
-                    teacher_args = dict(example_teacher_logits=teacher_logits) if cache is None else dict(teacher_cache=cache, example_index=sel)
-                    gstep = GraphedDistillStep(model, optimizer, criterion, img, label.long(), autocast_dtype=autocast_dtype, warmup=1,
-                                               **teacher_args)
+                    if loader_step:   # the batch (and, cached, its index) are the loader's buffers
+                        teacher_args = dict(example_teacher_logits=teacher_logits) if cache is None else dict(teacher_cache=cache)
+                        gstep = GraphedDistillStep(model, optimizer, criterion, None, None, autocast_dtype=autocast_dtype, warmup=1,
+                                                   loader=loader, **teacher_args)
+                    else:
+                        teacher_args = dict(example_teacher_logits=teacher_logits) if cache is None else dict(teacher_cache=cache, example_index=sel)
+                        gstep = GraphedDistillStep(model, optimizer, criterion, img, label.long(), autocast_dtype=autocast_dtype, warmup=1,
+                                                   **teacher_args)
                     loss, soft, ce, y_pred = gstep.warm_loss, gstep.warm_soft, gstep.warm_ce, gstep.warm_out
                 else:
-                    loss = gstep(img, label.long(), teacher_logits) if cache is None else gstep(img, label.long(), index=sel)
+                    if loader_in_graph:
+                        loss = gstep()   # ONE replay: fetch, forward, cached loss, backward, optimizer
+                    elif loader_step:
+                        loss = gstep(teacher_logits=teacher_logits)
+                    else:
+                        loss = gstep(img, label.long(), teacher_logits) if cache is None else gstep(img, label.long(), index=sel)
                     soft, ce, y_pred = gstep.soft, gstep.ce, gstep.out
+                if loader_in_graph:
+                    img, label = loader.img, loader.labels   # what the step just trained on
             else:
                 with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
                     y_pred = model(img)
@@ -623,6 +686,8 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                 torch.stack((loss.detach(), soft, ce), out=batch_losses[steps])
                 correct += (label == torch.argmax(y_pred, dim=1)).sum()
                 total += label.size(0)
+            if batch_hook is not None and loader is not None:
+                batch_hook("train", global_step - 1, img, label)
             steps += 1
             if steps >= epoch_steps:
                 break
@@ -718,8 +783,11 @@ def build_parser():
                     help="keep the training loss / accuracy books on the device inside the loss launch (spectre_vit.meter.TrainMeter): "
                          "no host-issued argmax / == / sum / accumulate per step, one read per epoch, per-step loss lines")
     ap.add_argument("--device-loader", action="store_true",
-                    help="fetch the shuffled training batches on the GPU (spectre_vit.data.ResidentLoader): with --graph a step is one "
-                         "replay with no host-issued work in front of it; the sample order differs from the host randperm's")
+                    help="fetch the shuffled training batches on the GPU (spectre_vit.data.ResidentLoader), with --augment augmented in "
+                         "the same call (LDS sizes: one launch; 64 x 64 .. 512 x 512: two): with --graph a step is one replay with no "
+                         "host-issued work in front of it; also with --distill-paired (there one replay with --graph --cache-teacher; "
+                         "uncached the teacher runs between the fetch and the replay); the sample order differs from the host "
+                         "randperm's")
     ap.add_argument("--out", default="runs/spectre_vit")
     return ap
 
@@ -731,7 +799,7 @@ def main(argv=None):
     if a.distill_paired:
         train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out,
                       graph_eval=a.graph_eval, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache,
-                      device_meter=a.device_meter, **control)
+                      device_meter=a.device_meter, device_loader=a.device_loader, **control)
         return
     train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph,
           model=a.model, augment=a.augment, graph_eval=a.graph_eval, device_meter=a.device_meter, device_loader=a.device_loader,

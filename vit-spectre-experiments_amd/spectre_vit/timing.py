@@ -110,6 +110,9 @@ _WORK_MODELS = {
     # read, the image read as uint8 and written as fp32
     "spv_loader_fetch_augment": lambda i: ("loader_fetch_augment", i[1:5], F32, "hbm",
                                            i[1] * (16.0 + (8 if i[9] else 1) + 64.0 + i[2] * i[3] * i[4] * 5)),
+    # the same integers: as above, and the image read a second time by the contrast mean's pre-pass (its partial sums are a few floats)
+    "spv_loader_fetch_augment_tiled": lambda i: ("loader_fetch_augment_tiled", i[1:5], F32, "hbm",
+                                                 i[1] * (16.0 + (8 if i[9] else 1) + 64.0 + i[2] * i[3] * i[4] * 6)),
     "spv_cast": lambda i: ("cast", i[2:3], i[1], "hbm", 1.0 * i[2] * (_es(i[0]) + _es(i[1]))),
 }
 
