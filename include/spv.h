@@ -559,6 +559,20 @@ int spv_spectral_fold_bwd(const float* dw_full, const float* proj_w, const float
                           float* dproj_w, float* dfreq_h, float* dfreq_w, float* scratch, int embed, int chans,
                           int patch, void* stream);
 int spv_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, int dtype, void* stream);
+/* The token GEMM of the embedding's forward on a kernel of its own (thin K: the 128 x 128 tile kernel ran 1040 tiles of one K step each):
+ *   tokens[r][:] = bf16((patches[r][:] . w^T + posbias[r % tokens_per_image][:]) * dropout_scale),  r < rows
+ * patches [rows, k] bf16 token rows (spv_patchify, transposed = 2: the zero CLS row of every image makes row 0 of posbias -- cls + pos[0] --
+ * land there by itself), w [n, k] bf16, posbias [tokens_per_image, n] fp32 (spv_embed_posbias with cls), tokens [rows, n] bf16,
+ * contiguous.  Exactly spv_gemm_nt_grouped_rows_drop(patches, w, NULL, posbias, tokens, rows, n, k, k, k, n, SPV_BF16, SPV_BF16,
+ * tokens_per_image, tokens_per_image, 0, p_drop, seed, stream), bit for bit: v_mfma_f32_32x32x16_bf16 over k / 16 steps in ascending k from
+ * a zero accumulator with the same operand roles, + the posbias row, * the dropout scale, one rounding to bf16; the mask is that call's
+ * (spv_dropout's on the flat index r * n + col with the same seed), so spv_embed_bwd finds it.
+ * spv_token_embed_supported: 1 when dtype == SPV_BF16, rows > 0, k % 16 == 0, 16 <= k <= 64 and n % 64 == 0 (n > 0); every other call
+ * stays with spv_gemm_nt_grouped_rows_drop.  spv_token_embed_fwd refuses, before any launch, an unsupported shape, tokens_per_image <= 0,
+ * p_drop outside [0, 1), a NULL pointer and a pointer off 16-byte alignment. */
+int spv_token_embed_supported(int rows, int n, int k, int dtype);
+int spv_token_embed_fwd(const void* patches, const void* w, const float* posbias, void* tokens, int rows, int n, int k,
+                        int tokens_per_image, float p_drop, uint64_t seed, void* stream);
 /* Backward of the token tensor in one pass + one fold: dtok = dropout_mask(g [+ gcls on the CLS rows]) (the mask of the forward's
  * spv_dropout with the same seed over the same flat index; dtok may be NULL when it would equal g), and the sums over the batch that
  * dpos [tokens][embed], dbias[e] = sum_{t >= 1} dpos[t][e] and dcls[e] = dpos[0][e] are (gradients of position_embeddings, proj.bias

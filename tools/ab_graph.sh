@@ -5,6 +5,9 @@
 #   "TREE=/path/to/checkout"             a whole checkout (built in place) -- its own bench.py, package and library: for changes that
 #                                        touch the host side or the ABI as well
 #   bash tools/ab_graph.sh "TREE=/path/parent" "TREE=$PWD" [rounds] [extra bench args, e.g. --steps 400]
+#   bash tools/ab_graph.sh "TREE=<checkout of the parent commit, built>" "TREE=$PWD" 5 --steps 400 --no-base224   # a commit against its parent
+#                                        (profiles/prologue_v1_ab_graph.txt, profiles/token_embed_v1_ab_graph.txt); a gain counts when
+#                                        every run of the second side lies below every run of the first
 A="$1"; B="$2"; R="${3:-3}"; shift 3 2>/dev/null
 ROOT="$(cd "$(dirname "$0")/.." && pwd)"
 for i in $(seq 1 $R); do

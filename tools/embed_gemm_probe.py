@@ -36,9 +36,20 @@ cases = {
     "grouped rows + bias2d": lambda: _native.call("spv_gemm_nt_grouped_rows", _p(a), _p(w), 0, _p(b2), _p(c), M, N, K, K, K, N, 1, 1, T, T, 0, st),
     "grouped rows + bias2d + dropout 0.001": lambda: _native.call("spv_gemm_nt_grouped_rows_drop", _p(a), _p(w), 0, _p(b2), _p(c), M, N, K, K, K, N, 1, 1,
                                                                   T, T, 0, 0.001, 1234, st),
+    # the same call on the thin-K kernel (the weight in registers, a wave per 32 x 64 output block)
+    "spv_token_embed_fwd, dropout 0.001": lambda: _native.call("spv_token_embed_fwd", _p(a), _p(w), _p(b2), _p(c), M, N, K, T, 0.001, 1234, st),
 }
 for name, fn in cases.items():
     print(f"{name:45s} {t(fn):7.2f} us", flush=True)
+# the two dropout cases write the same bits
+outs = []
+for name in ("grouped rows + bias2d + dropout 0.001", "spv_token_embed_fwd, dropout 0.001"):
+    c.fill_(float("nan"))
+    cases[name]()
+    torch.cuda.synchronize()
+    outs.append(c.clone())
+print("spv_token_embed_fwd == spv_gemm_nt_grouped_rows_drop bit for bit:", torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16)), flush=True)
+assert torch.equal(outs[0].view(torch.int16), outs[1].view(torch.int16))
 # for scale: a plain copy of the output's bytes
 src = torch.empty_like(c)
 print(f"{'copy of 34 MB (torch)':45s} {t(lambda: c.copy_(src)):7.2f} us")

@@ -4,6 +4,9 @@
 #define SPV_USES_SEED
 #include "spv_common.h"
 #include "spv_prologue_core.h"
+#include "spv_token_embed_core.h"
+
+#include <type_traits>
 
 namespace {
 
@@ -162,6 +165,136 @@ __global__ __launch_bounds__(1024) void freq_weight_grad_kernel(const float* __r
 
 inline int ew_blocks(int64_t n) { return patch_ew_blocks(n); }
 
+// ---- the token GEMM of the embedding's forward: tokens[r] = bf16((patches[r] . w^T + posbias[r % T]) * dropout_scale), K = 16 KS <= 64.
+// The launch is 34 MB of output behind 1.6 GFLOP: on the 128 x 128 tile kernel each of its 1040 single-K-step tiles paid two operand
+// stagings and four workgroup barriers.  Here a WAVE is the unit (plan: spv_token_embed_core.h): it loads its 64-column share of w once,
+// as the B fragments of v_mfma_f32_32x32x16_bf16 (2 x KS uint4), and walks 32-row blocks.  Both operands are K-contiguous, so the A
+// fragment of a lane is 16 contiguous bytes of one patch row: a plain 16-byte load, no LDS staging.  The accumulators leave through a
+// wave-private fp32 stage, 16 rows at a time, so that a lane holds 8 consecutive columns of one row: each store instruction of the wave
+// writes 8 whole 128-byte lines.  No workgroup barrier: a wave's LDS accesses run in order.  The next block's loads go out before this
+// block's stores (see the loop).
+// Operand roles, k order and the epilogue (+ posbias row, * dropout scale, one pack per pair) are those of gemm_nt_kernel +
+// store_acc_tile, whose K padding adds exact zeros: the output is that call's bit for bit.
+template <int KS>
+__global__ __launch_bounds__(64 * TE_WAVES, 3) void token_embed_kernel(const bf16_t* __restrict__ P, const bf16_t* __restrict__ Wt,
+                                                                    const float* __restrict__ posbias, bf16_t* __restrict__ out, int rows,
+                                                                    int n, int T, int shares, int walkers, float p, uint64_t seed) {
+    constexpr int K = 16 * KS;
+    constexpr int SLD = TE_COLS + 4;   // fp32 words per stage row (rows 16 bytes apart in the banks, as in store_acc_tile)
+    __shared__ __attribute__((aligned(16))) float stage_all[TE_WAVES][16 * SLD];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int g = blockIdx.x * TE_WAVES + wave;
+    if (g >= shares * walkers) return;   // (the last workgroup's spare waves; nothing below waits for another wave)
+    const int walker = g / shares, n0 = (g % shares) * TE_COLS;
+    const int frow = lane & 31, fh = lane >> 5;
+    float* st = stage_all[wave];
+
+    uint4 b[2][KS];
+#pragma unroll
+    for (int j = 0; j < 2; ++j)
+#pragma unroll
+        for (int s = 0; s < KS; ++s) b[j][s] = *reinterpret_cast<const uint4*>(Wt + (size_t)(n0 + 32 * j + frow) * K + 16 * s + 8 * fh);
+    const uint64_t seed_live = p > 0.0f ? live_seed(seed) : 0;   // one load of the replay-time seed word per wave
+    const float inv_keep = 1.0f / (1.0f - p);
+    const int nblk = (rows + TE_ROWS - 1) / TE_ROWS;
+    const int lr0 = lane >> 3, c8 = lane & 7;   // the lane's stage row (+ 8 t) and 8-column chunk on the way out
+    const int col0 = n0 + c8 * 8;
+
+    auto load_a = [&](int rb, uint4 (&a)[KS]) {   // clamped row: the loads are unconditional
+        const bf16_t* ap = P + (size_t)min(rb * TE_ROWS + frow, rows - 1) * K + 8 * fh;
+#pragma unroll
+        for (int s = 0; s < KS; ++s) a[s] = *reinterpret_cast<const uint4*>(ap + 16 * s);
+    };
+    // row % T of the lane's first row of a block, kept by addition: + 8 per chunk, + 32 walkers per block (one conditional subtraction
+    // each, the steps being reduced mod T once: a modulo per chunk was a tenth of the kernel's instructions)
+    const int step8 = 8 % T, stepw = (int)(((int64_t)walkers * TE_ROWS) % T);
+    auto wrap = [&](int t) { return t - (t >= T ? T : 0); };
+    float4 pb[4][2];   // the position rows of a block's 4 x 8 columns per lane (row % T < T whatever the row: no clamp)
+    auto load_pb = [&](int q, int t) {
+        const float* pp = posbias + (size_t)t * n + col0;
+        pb[q][0] = *reinterpret_cast<const float4*>(pp);
+        pb[q][1] = *reinterpret_cast<const float4*>(pp + 4);
+    };
+    uint4 a[KS];
+    load_a(walker, a);
+    int t0 = (walker * TE_ROWS + lr0) % T;
+    {
+        int t = t0;
+#pragma unroll
+        for (int q = 0; q < 4; ++q) { load_pb(q, t); t = wrap(t + step8); }
+    }
+    // Loads and stores retire in issue order, so a wait for a load also waits for every store issued before it.  The block's four
+    // stores are therefore held back until the NEXT block's loads are out: a (free after the MFMAs) and each chunk's position rows (free
+    // after that chunk's sums).  The wait for those loads at the head of the next trip then leaves the stores in flight.
+    auto block = [&](int rb, auto masked_tag) __attribute__((always_inline)) {
+        constexpr bool MASKED = decltype(masked_tag)::value;
+        f32x16 acc[2];
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[j][r] = 0.0f;
+#pragma unroll
+        for (int s = 0; s < KS; ++s)
+#pragma unroll
+            for (int j = 0; j < 2; ++j)
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a[s]), __builtin_bit_cast(bf16x8, b[j][s]), acc[j], 0, 0, 0);
+        load_a(min(rb + walkers, nblk - 1), a);
+        t0 = wrap(t0 + stepw);
+        {
+            uint4 o[4];
+            int tn = t0;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) {   // rows 16 h .. 16 h + 15 of the block = accumulator registers 8 h .. 8 h + 7
+                // C/D map of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+#pragma unroll
+                    for (int r = 0; r < 8; ++r) st[((r & 3) + 8 * (r >> 2) + 4 * fh) * SLD + 32 * j + frow] = acc[j][8 * h + r];
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+#pragma unroll
+                for (int t = 0; t < 2; ++t) {
+                    const int q = 2 * h + t, lr = lr0 + 8 * t;
+                    const float4 lo = *reinterpret_cast<const float4*>(st + lr * SLD + c8 * 8);
+                    const float4 hi = *reinterpret_cast<const float4*>(st + lr * SLD + c8 * 8 + 4);
+                    float v[8] = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
+                    const float4 p0 = pb[q][0], p1 = pb[q][1];
+                    v[0] += p0.x; v[1] += p0.y; v[2] += p0.z; v[3] += p0.w; v[4] += p1.x; v[5] += p1.y; v[6] += p1.z; v[7] += p1.w;
+                    load_pb(q, tn);
+                    tn = wrap(tn + step8);
+                    if (p > 0.0f) {
+                        // the mask of spv_dropout on the flat index of the output.  fi is a multiple of 8: the 8 columns share a 4096-block
+                        // and start on an even column, so dropout_scale_at's form holds -- one hash per PAIR, the parities known at compile
+                        // time (through dropout_scale hipcc, not knowing c0 even, hashed every column).  The block index is below 2^32
+                        // (the host holds rows * n to 2^40), which folds the key's high-word hash into a constant of the wave.
+                        const size_t fi = (size_t)(rb * TE_ROWS + lr0 + 8 * q) * n + col0;
+                        const unsigned key = dropout_row_key(seed_live, (uint64_t)(unsigned)(fi >> 12));
+                        const unsigned key_base = key + ((unsigned)(fi & 4095) >> 1) * 0x9e3779b1u;
+#pragma unroll
+                        for (int u = 0; u < 8; ++u) v[u] *= dropout_scale_at(key_base, u, p, inv_keep);
+                    }
+                    o[q].x = pack_bf16x2(v[0], v[1]);
+                    o[q].y = pack_bf16x2(v[2], v[3]);
+                    o[q].z = pack_bf16x2(v[4], v[5]);
+                    o[q].w = pack_bf16x2(v[6], v[7]);
+                }
+                __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+            }
+            __builtin_amdgcn_sched_barrier(0);   // (the stores stay behind the loads above)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int row = rb * TE_ROWS + lr0 + 8 * q;
+                if (!MASKED || row < rows) *reinterpret_cast<uint4*>(out + (size_t)row * n + col0) = o[q];
+            }
+        }
+    };
+    // whole blocks store without a branch (behind a branch hipcc cannot count the stores in flight and waits for ALL of them at the next
+    // load it needs); the ragged last block of the tensor, which tests its rows, is the last of its walker and stands outside the loop
+    const int nfull = rows / TE_ROWS;
+    int rb = walker;
+    for (; rb < nfull; rb += walkers) block(rb, std::false_type{});
+    if (rb < nblk) block(rb, std::true_type{});
+}
+
 }  // namespace
 
 extern "C" int spv_patchify(const float* img, void* out, int batch, int chans, int height, int width, int patch, int ld,
@@ -219,6 +352,41 @@ extern "C" int spv_embed_cls_rows(const float* cls, const float* pos, void* toke
     hipLaunchKernelGGL(cls_rows_kernel, dim3(ew_blocks((int64_t)batch * embed)), dim3(256), 0, static_cast<hipStream_t>(stream), cls,
                        pos, tokens, batch, tokens_per_image, embed, dtype == SPV_BF16);
     SPV_LAUNCH_CHECK("spv_embed_cls_rows");
+    return 0;
+}
+
+extern "C" int spv_token_embed_supported(int rows, int n, int k, int dtype) { return token_embed_supported(rows, n, k, dtype); }
+
+extern "C" int spv_token_embed_fwd(const void* patches, const void* w, const float* posbias, void* tokens, int rows, int n, int k,
+                                   int tokens_per_image, float p_drop, uint64_t seed, void* stream) {
+    SPV_CHECK(token_embed_supported(rows, n, k, SPV_BF16) && (int64_t)rows * n <= (1ll << 40),
+              "spv_token_embed_fwd: unsupported shape %d x %d x %d (bf16; k a multiple of 16 in 16..64; n a multiple of 64; rows * n <= 2^40)", rows, n, k);
+    SPV_CHECK(tokens_per_image > 0, "spv_token_embed_fwd: tokens_per_image=%d", tokens_per_image);
+    SPV_CHECK(p_drop >= 0.0f && p_drop < 1.0f, "spv_token_embed_fwd: p_drop=%f", p_drop);
+    SPV_CHECK(patches && w && posbias && tokens, "spv_token_embed_fwd: null pointer");
+    SPV_CHECK((((uintptr_t)patches | (uintptr_t)w | (uintptr_t)posbias | (uintptr_t)tokens) & 15) == 0,
+              "spv_token_embed_fwd: pointers must be 16-byte aligned");
+    static int cus = 0;   // (every device of a process is the same part)
+    if (cus == 0) {
+        int dev = 0, v = 0;
+        SPV_CHECK(hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0,
+                  "spv_token_embed_fwd: no device to size the grid for");
+        cus = v;
+    }
+    const TokenEmbedPlan pl = token_embed_plan(rows, n, cus);
+    hipStream_t st = static_cast<hipStream_t>(stream);
+#define SPV_TOKEN_EMBED(KS)                                                                                                      \
+    hipLaunchKernelGGL((token_embed_kernel<KS>), dim3(pl.grid), dim3(64 * TE_WAVES), 0, st, static_cast<const bf16_t*>(patches), \
+                       static_cast<const bf16_t*>(w), posbias, static_cast<bf16_t*>(tokens), rows, n, tokens_per_image, pl.shares, \
+                       pl.walkers, p_drop, seed)
+    switch (k / 16) {
+    case 1: SPV_TOKEN_EMBED(1); break;
+    case 2: SPV_TOKEN_EMBED(2); break;
+    case 3: SPV_TOKEN_EMBED(3); break;
+    default: SPV_TOKEN_EMBED(4); break;
+    }
+#undef SPV_TOKEN_EMBED
+    SPV_LAUNCH_CHECK("spv_token_embed_fwd");
     return 0;
 }
 

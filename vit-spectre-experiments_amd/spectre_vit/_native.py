@@ -97,6 +97,8 @@ SIGNATURES = {
     "spv_spectral_fold_bf16": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp],
     "spv_spectral_fold_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_vp],
     "spv_dropout": [c_vp, c_vp, c_i64, c_f, c_u64, c_i, c_vp],
+    "spv_token_embed_supported": [c_i, c_i, c_i, c_i],
+    "spv_token_embed_fwd": [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_f, c_u64, c_vp],
     "spv_attention_fwd": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_u64, c_vp],
     "spv_attention_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_u64, c_vp],
     "spv_attention_row0_fwd": [c_vp, c_vp, c_vp, c_i, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_f, c_u64, c_vp],
@@ -166,7 +168,7 @@ _RESTYPES = {"spv_last_error": ctypes.c_char_p, "spv_path_count": ctypes.c_longl
              "spv_eval_head_stats_words": c_i64, "spv_augment_tiled_ws_bytes": ctypes.c_size_t, "spv_train_meter_words": c_i64,
              "spv_cross_entropy_meter_workspace_floats": c_i64, "spv_distill_loss_meter_workspace_floats": c_i64,
              "spv_loader_cursor_bytes": c_i64, "spv_hadamard_workspace_floats": c_i64}
-_NO_STATUS = set(_RESTYPES) | {"spv_hadamard_path", "spv_hadamard_ln_supported", "spv_hadamard_cls_supported", "spv_version", "spv_fnet_ln_supported", "spv_fnet_cls_supported", "spv_tail_ln_supported", "spv_tail_up_supported", "spv_small_sl_supported", "spv_tail_bwd_parts", "spv_embed_bwd_groups", "spv_haar_ln_supported", "spv_permut_pool_supported", "spv_spectrum_floats", "spv_augment_supported", "spv_loader_augment_supported", "spv_loader_augment_tiled_supported", "spv_augment_plan", "spv_teacher_view_supported"}
+_NO_STATUS = set(_RESTYPES) | {"spv_hadamard_path", "spv_hadamard_ln_supported", "spv_hadamard_cls_supported", "spv_version", "spv_fnet_ln_supported", "spv_fnet_cls_supported", "spv_tail_ln_supported", "spv_tail_up_supported", "spv_small_sl_supported", "spv_tail_bwd_parts", "spv_embed_bwd_groups", "spv_haar_ln_supported", "spv_permut_pool_supported", "spv_spectrum_floats", "spv_augment_supported", "spv_loader_augment_supported", "spv_loader_augment_tiled_supported", "spv_augment_plan", "spv_teacher_view_supported", "spv_token_embed_supported"}
 
 class FoldJob(ctypes.Structure):
     """spv_fold_job (include/spv.h): the fold of a tail backward's partial column sums, handed to spv_gemm_tn_fold"""

@@ -909,8 +909,13 @@ class PatchEmbedFn(torch.autograd.Function):
         tokens = torch.empty((B, T, E), dtype=dtype, device=dev)
         seed = _new_seed() if p_drop > 0.0 else 0
         # the dropout rides in the GEMM's epilogue (the mask spv_dropout would draw from the same seed; the backward re-derives it)
-        _native.call("spv_gemm_nt_grouped_rows_drop", _p(patches), _p(wc), 0, _p(posbias), _p(tokens), B * T, E, K, K, K, E,
-                     _DT[dtype], _DT[dtype], T, T, 0, float(p_drop), seed, st)
+        if TOKEN_EMBED_KERNEL and _native.call("spv_token_embed_supported", B * T, E, K, _DT[dtype]):
+            # thin K (16..64), bf16: the kernel that walks row blocks with the weight in registers; the same bits as the call below
+            _native.call("spv_token_embed_fwd", _p(patches), _p(wc), _p(posbias), _p(tokens), B * T, E, K, T, float(p_drop), seed, st)
+            PATH_COUNTS["token_embed"] += 1
+        else:
+            _native.call("spv_gemm_nt_grouped_rows_drop", _p(patches), _p(wc), 0, _p(posbias), _p(tokens), B * T, E, K, K, K, E,
+                         _DT[dtype], _DT[dtype], T, T, 0, float(p_drop), seed, st)
         # bf16: the backward's TN weight-gradient GEMM reads the patch matrix as it lies here (3 MB), so keep it
         ctx.save_for_backward(None if u8 else img, patches if (dtype == torch.bfloat16 or u8) else None)
         ctx.meta = (B, C, H, W, patch, E, K, Np, T, dtype, cls.shape, pos.shape, float(p_drop), seed)
@@ -1163,6 +1168,9 @@ class ClsAddFn(torch.autograd.Function):
 # position/bias rows are mutually independent and all needed only in front of the token GEMM, yet as five dependent graph nodes each
 # paid its own launch and drain.  False: the step issues spv_seed_advance and every node launches for itself, as an eager forward does.
 STEP_PROLOGUE = True
+# The embedding's token GEMM on spv_token_embed_fwd where spv_token_embed_supported says so (bf16, K = 16..64, E % 64 == 0).  False: every
+# call goes to spv_gemm_nt_grouped_rows_drop, as all other shapes do; the two write the same bits (A/B runs, tests).
+TOKEN_EMBED_KERNEL = True
 
 
 def step_prologue(model, img, seed_word, autocast_dtype):
