@@ -424,7 +424,8 @@ typedef struct spv_step_ctl {
     float grad_norm;    /* L2 norm over every gradient of every group, as the last spv_step_control saw it */
     int sched_step;     /* calls of spv_step_control so far = the schedule's t of the NEXT step (advances on dropped steps too) */
     int skipped;        /* dropped steps so far */
-    int reserved[7];
+    int micro;          /* gradient accumulation (spv_step_control_accum): micro-steps already in the open window; stays 0 without it */
+    int reserved[6];
 } spv_step_ctl;
 #define SPV_CTL_SCHEDULE 1   /* flags of spv_step_control */
 #define SPV_CTL_CLIP 2
@@ -450,6 +451,31 @@ int spv_grad_sumsq(const void* table, const int* chunk_tensor, const int* chunk_
  * spv_adamw_multi_ctl reads through step_dev.  step_ptrs is a DEVICE array of device pointers. */
 int spv_step_control(const double* partials, int npartials, float* const* step_ptrs, int nsteps, spv_step_ctl* ctl, int flags,
                      int warmup_steps, int total_steps, double eta_min, float max_norm, void* stream);
+
+/* ---- gradient accumulation: k calls of the step per optimizer step, decided on the device --------------------
+ * A window is accumulate_steps = k consecutive micro-steps; ctl->micro counts the micro-steps already in the open window.  Per
+ * micro-step: spv_grad_accumulate per parameter group, ONE spv_step_control_accum, spv_adamw_multi_ctl[_ema] per group on a table
+ * whose g column holds the accumulators.  One captured graph serves every micro-step; every k-th replay applies the optimizer.
+ *
+ * spv_grad_accumulate: table / chunk_tensor / chunk_off / sizes / nchunks as spv_grad_sumsq (only the g pointers are read);
+ * acc_table is a DEVICE array of one float* per table row, each 16-byte aligned with room for the row's size rounded up to 4.
+ * With ctl->micro == 0, acc = g: an assignment, the old contents are not read (a NaN left there vanishes).  Otherwise
+ * acc = (float)(acc + g), one IEEE add per element.  partials[c] = the fp64 sum of squares of the NEW acc over chunk c, in
+ * spv_grad_sumsq's order and arithmetic (with micro == 0 its bits).  g need not be 16-byte aligned.  Plain vector loads and stores. */
+int spv_grad_accumulate(const void* table, float* const* acc_table, const int* chunk_tensor, const int* chunk_off, const int* sizes,
+                        int nchunks, const spv_step_ctl* ctl, double* partials, void* stream);
+
+/* spv_step_control for a window of accumulate_steps = k >= 1 micro-steps (arguments as there).  m = ctl->micro on entry:
+ *   m <  k - 1   apply = 0, micro = m + 1; nothing else in *ctl changes and no Adam step count moves.
+ *   m >= k - 1   the boundary: sumsq folded as spv_step_control does, norm = (float)(sqrt(sumsq) / (double)k) -- the norm of the MEAN
+ *                gradient, stored as grad_norm; the schedule at t = sched_step, sched_step += 1 (one tick per window, applied or
+ *                dropped); c = spv_step_control's clip expression on norm (1 without SPV_CTL_CLIP) and
+ *                clip_coef = (float)((double)c / (double)k), so that acc * clip_coef is the clipped mean; apply = 0 and skipped += 1
+ *                exactly when SPV_CTL_SKIP_NONFINITE is set and sumsq is not finite (non-finiteness is sticky under addition, so
+ *                deciding at the boundary is exact), otherwise apply = 1 and *step_ptrs[i] += 1; micro = 0 either way.
+ * With k = 1 every expression reduces bit for bit to spv_step_control's. */
+int spv_step_control_accum(const double* partials, int npartials, float* const* step_ptrs, int nsteps, spv_step_ctl* ctl, int flags,
+                           int warmup_steps, int total_steps, double eta_min, float max_norm, int accumulate_steps, void* stream);
 
 /* spv_adamw_multi with lr = (float)(ctl->a * base_lr + ctl->b), the gradient scaled by ctl->clip_coef in registers and nothing
  * written at all when ctl->apply == 0.  The same update body as spv_adamw_multi: with a = 1, b = 0, clip_coef = 1, apply = 1 the

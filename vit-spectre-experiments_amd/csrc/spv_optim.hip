@@ -1,6 +1,6 @@
-// spv_optim.hip -- on-device step control of the optimizer (include/spv.h: spv_step_ctl): the gradient's sum of squares, the
-// one-workgroup kernel that turns it and the step count into this step's learning rate / clip coefficient / apply flag, and the
-// AdamW launch that reads them.  Nothing here is decided on the host, so a captured training step follows the schedule and skips a
+// spv_optim.hip -- on-device step control of the optimizer (include/spv.h: spv_step_ctl): the gradient's sum of squares (or, under
+// gradient accumulation, the accumulator's, formed while the gradient is added to it), the one-workgroup kernel that turns it and the
+// step counts into this step's learning rate / clip coefficient / apply flag, and the AdamW launch that reads them.  Nothing here is decided on the host, so a captured training step follows the schedule and skips a
 // non-finite gradient on every replay.
 #include "spv_common.h"
 #include "spv_adamw_core.h"
@@ -50,11 +50,71 @@ __global__ __launch_bounds__(256) void grad_sumsq_kernel(const AdamTensor* __res
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// Gradient accumulation: the same chunk walk with the accumulator taken along.  ctl->micro == 0 opens a window: acc = g, an
+// assignment that does not read the old accumulator (whatever a dropped window left there, a NaN included, is gone).  Otherwise
+// acc = acc + g, one fp32 add per element.  The chunk's sum of squares is that of the NEW accumulator, in grad_sumsq_kernel's order
+// (with micro == 0 its very bits).  An accumulator slot is 16-byte aligned and padded to four elements, so wherever g takes the
+// float4 branch (i + 3 < n) the accumulator's float4 at the same index is aligned and inside its slot; an unaligned g takes the
+// scalar branch for both.
+__global__ __launch_bounds__(256) void grad_accumulate_kernel(const AdamTensor* __restrict__ tab, float* const* __restrict__ acc_tab,
+                                                              const int* __restrict__ chunk_tensor, const int* __restrict__ chunk_off,
+                                                              const int* __restrict__ sizes, const spv_step_ctl* __restrict__ ctl,
+                                                              double* __restrict__ partials) {
+    __shared__ double wave_part[4];
+    const int t = chunk_tensor[blockIdx.x];
+    const int off = chunk_off[blockIdx.x];
+    const float* __restrict__ g = tab[t].g;
+    float* __restrict__ acc = acc_tab[t];
+    const int n = sizes[t];
+    const bool open = ctl->micro == 0;
+    const int base = off + threadIdx.x * 4;
+    double s = 0.0;
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+        const int i = base + h * 1024;
+        if (i + 3 < n && (reinterpret_cast<uintptr_t>(g) & 15) == 0) {
+            float4 q = *reinterpret_cast<const float4*>(g + i);
+            if (!open) {
+                const float4 a = *reinterpret_cast<const float4*>(acc + i);
+                q.x = a.x + q.x;
+                q.y = a.y + q.y;
+                q.z = a.z + q.z;
+                q.w = a.w + q.w;
+            }
+            *reinterpret_cast<float4*>(acc + i) = q;
+            s += (double)q.x * (double)q.x;
+            s += (double)q.y * (double)q.y;
+            s += (double)q.z * (double)q.z;
+            s += (double)q.w * (double)q.w;
+        } else {
+            for (int u = 0; u < 4; ++u) {
+                const int j = i + u;
+                if (j >= n) break;
+                float v = g[j];
+                if (!open) v = acc[j] + v;
+                acc[j] = v;
+                const double x = (double)v;
+                s += x * x;
+            }
+        }
+    }
+#pragma unroll
+    for (int w = 32; w > 0; w >>= 1) s += __shfl_xor(s, w, 64);
+    if ((threadIdx.x & 63) == 0) wave_part[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) partials[blockIdx.x] = (wave_part[0] + wave_part[1]) + (wave_part[2] + wave_part[3]);
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // One workgroup: partials -> ctl.  Thread i adds partials i, i + 256, ... in that order, a fixed tree joins the 256 sums; the same
 // launch gives the same bits on every replay and on every rank of a data-parallel job (each holds the same averaged gradient).
+// ACCUM: a window of accum_k micro-steps (include/spv.h: spv_step_control_accum).  Inside the window only apply and micro are
+// written; at its boundary the block is filled as without accumulation, from the norm of the mean gradient, and the clip
+// coefficient carries the 1 / accum_k that turns the summed gradient into the mean.  Both divisions are exact for accum_k = 1.
+template <bool ACCUM>
 __global__ __launch_bounds__(256) void step_control_kernel(const double* __restrict__ partials, int npartials, float* const* __restrict__ step_ptrs,
                                                            int nsteps, spv_step_ctl* __restrict__ ctl, int flags, int warmup_steps,
-                                                           int total_steps, double eta_min, float max_norm) {
+                                                           int total_steps, double eta_min, float max_norm, int accum_k) {
     __shared__ double red[256];
     double s = 0.0;
     for (int i = threadIdx.x; i < npartials; i += 256) s += partials[i];
@@ -65,8 +125,17 @@ __global__ __launch_bounds__(256) void step_control_kernel(const double* __restr
         __syncthreads();
     }
     if (threadIdx.x != 0) return;
+    if constexpr (ACCUM) {
+        const int micro = ctl->micro;
+        if (micro < accum_k - 1) {   // inside the window: the optimizer launch writes nothing, the last boundary's values stay
+            ctl->apply = 0;
+            ctl->micro = micro + 1;
+            return;
+        }
+        ctl->micro = 0;
+    }
     const double sumsq = red[0];
-    const float norm = (float)sqrt(sumsq);
+    const float norm = ACCUM ? (float)(sqrt(sumsq) / (double)accum_k) : (float)sqrt(sumsq);
     const int t = ctl->sched_step;
     double a = 1.0, b = 0.0;
     if (flags & SPV_CTL_SCHEDULE) {
@@ -84,6 +153,7 @@ __global__ __launch_bounds__(256) void step_control_kernel(const double* __restr
         const float c = max_norm / (norm + 1e-6f);
         coef = c < 1.0f ? c : (c != c ? c : 1.0f);   // clamp(max=1) that keeps a NaN, as torch's
     }
+    if constexpr (ACCUM) coef = (float)((double)coef / (double)accum_k);
     const int apply = ((flags & SPV_CTL_SKIP_NONFINITE) && !isfinite(sumsq)) ? 0 : 1;
     ctl->a = a;
     ctl->b = b;
@@ -153,9 +223,43 @@ extern "C" int spv_step_control(const double* partials, int npartials, float* co
         SPV_CHECK(eta_min >= 0.0, "spv_step_control: eta_min = %g must be >= 0", eta_min);   // (false for a NaN too)
     }
     if (flags & SPV_CTL_CLIP) SPV_CHECK(max_norm > 0.0f, "spv_step_control: max_norm = %g must be > 0", (double)max_norm);
-    hipLaunchKernelGGL(step_control_kernel, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), partials, npartials, step_ptrs, nsteps,
-                       ctl, flags, warmup_steps, total_steps, eta_min, max_norm);
+    hipLaunchKernelGGL(step_control_kernel<false>, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), partials, npartials, step_ptrs,
+                       nsteps, ctl, flags, warmup_steps, total_steps, eta_min, max_norm, 1);
     SPV_LAUNCH_CHECK("spv_step_control");
+    return 0;
+}
+
+extern "C" int spv_grad_accumulate(const void* table, float* const* acc_table, const int* chunk_tensor, const int* chunk_off,
+                                   const int* sizes, int nchunks, const spv_step_ctl* ctl, double* partials, void* stream) {
+    SPV_CHECK(nchunks >= 0, "spv_grad_accumulate: nchunks = %d", nchunks);
+    SPV_CHECK(table && chunk_tensor && chunk_off && sizes, "spv_grad_accumulate: null table");
+    SPV_CHECK(acc_table, "spv_grad_accumulate: null acc_table");
+    SPV_CHECK(ctl, "spv_grad_accumulate: null control block");
+    SPV_CHECK(partials, "spv_grad_accumulate: null partials");
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(grad_accumulate_kernel, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), acc_table, chunk_tensor, chunk_off, sizes, ctl, partials);
+    SPV_LAUNCH_CHECK("spv_grad_accumulate");
+    return 0;
+}
+
+extern "C" int spv_step_control_accum(const double* partials, int npartials, float* const* step_ptrs, int nsteps, spv_step_ctl* ctl,
+                                      int flags, int warmup_steps, int total_steps, double eta_min, float max_norm, int accumulate_steps,
+                                      void* stream) {
+    SPV_CHECK(npartials >= 0 && nsteps >= 0, "spv_step_control_accum: npartials = %d, nsteps = %d", npartials, nsteps);
+    SPV_CHECK(ctl, "spv_step_control_accum: null control block");
+    SPV_CHECK((partials || npartials == 0) && (step_ptrs || nsteps == 0), "spv_step_control_accum: null partials / step_ptrs");
+    SPV_CHECK((flags & ~(SPV_CTL_SCHEDULE | SPV_CTL_CLIP | SPV_CTL_SKIP_NONFINITE)) == 0, "spv_step_control_accum: unknown flags 0x%x", flags);
+    SPV_CHECK(accumulate_steps >= 1, "spv_step_control_accum: accumulate_steps = %d must be >= 1", accumulate_steps);
+    if (flags & SPV_CTL_SCHEDULE) {
+        SPV_CHECK(warmup_steps >= 0 && total_steps > warmup_steps,
+                  "spv_step_control_accum: schedule needs 0 <= warmup_steps < total_steps (%d, %d)", warmup_steps, total_steps);
+        SPV_CHECK(eta_min >= 0.0, "spv_step_control_accum: eta_min = %g must be >= 0", eta_min);
+    }
+    if (flags & SPV_CTL_CLIP) SPV_CHECK(max_norm > 0.0f, "spv_step_control_accum: max_norm = %g must be > 0", (double)max_norm);
+    hipLaunchKernelGGL(step_control_kernel<true>, dim3(1), dim3(256), 0, static_cast<hipStream_t>(stream), partials, npartials, step_ptrs,
+                       nsteps, ctl, flags, warmup_steps, total_steps, eta_min, max_norm, accumulate_steps);
+    SPV_LAUNCH_CHECK("spv_step_control_accum");
     return 0;
 }
 

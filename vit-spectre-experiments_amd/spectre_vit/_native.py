@@ -113,6 +113,8 @@ SIGNATURES = {
     "spv_adamw_multi_ema": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_f, c_i, c_f, c_vp],
     "spv_grad_sumsq": [c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_vp],
     "spv_step_control": [c_vp, c_i, c_vp, c_i, c_vp, c_i, c_i, c_i, c_d, c_f, c_vp],
+    "spv_grad_accumulate": [c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_vp, c_vp, c_vp],
+    "spv_step_control_accum": [c_vp, c_i, c_vp, c_i, c_vp, c_i, c_i, c_i, c_d, c_f, c_i, c_vp],
     "spv_adamw_multi_ctl": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_vp],
     "spv_adamw_multi_ctl_ema": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_vp, c_f, c_i, c_vp],
     "spv_fwht": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp],

@@ -12,6 +12,11 @@ spectre_vit/repl/train.py:216-238 minus the host-side bookkeeping.  Requirements
     ``param_groups`` between replays has no effect -- ``FusedAdamW(schedule=..., max_grad_norm=..., skip_nonfinite=...)`` decides all
     three on the device inside ``optimizer.step()``, which is what every step class here captures (``GraphedDPStep``: in graph B,
     behind the all-reduce, so every rank decides alike);
+  * gradient accumulation: ``FusedAdamW(accumulate_steps=k)`` -- each replay is one micro-step, the device counts them and every
+    k-th replay applies the optimizer; the graph is the same for all of them and nothing here changes.  The warm-up steps are real
+    MICRO-steps: ``warmup`` a multiple of k keeps the first replay at the start of a window (any other value is valid too: the window
+    is then open when the replays begin, ``optimizer.micro_step()`` tells where).  A ``GraphedDPStep`` rank all-reduces every
+    micro-step, which is correct because the exchange is linear;
   * dropout: seeds are by-value kernel arguments frozen at capture, so every dropout kernel adds a 64-bit device word that this
     class advances once per replay (a role of ``spv_step_prologue``, the first node of the graph) -- fresh masks every step;
   * fixed shapes (one graph per batch shape).

@@ -105,23 +105,36 @@ class SyntheticCifar:
             yield img, self.labels[sel]
 
 
-def _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite, total_steps):
-    """the harness's five step-control arguments -> FusedAdamW keywords; {} when none is on (the optimizer choice is then untouched)"""
+def _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite, total_steps, accumulate_steps=None):
+    """the harness's step-control arguments -> FusedAdamW keywords; {} when none is on (the optimizer choice is then untouched).
+    total_steps counts loader steps; with accumulate_steps=k each is a micro-step and the schedule runs over total_steps // k optimizer
+    steps (warmup_steps counts optimizer steps as well)."""
     if lr_schedule not in (None, "cosine"):
         raise ValueError(f"lr_schedule={lr_schedule!r}: None or 'cosine'")
     if lr_schedule is None and (warmup_steps or eta_min):
         raise ValueError("warmup_steps / eta_min belong to lr_schedule='cosine'")
-    if lr_schedule is None and clip_grad_norm is None and not skip_nonfinite:
+    k = accumulate_steps
+    if k is not None and (isinstance(k, bool) or not isinstance(k, int) or k < 1):
+        raise ValueError(f"accumulate_steps={k!r} must be None or an int >= 1")
+    if lr_schedule is None and clip_grad_norm is None and not skip_nonfinite and k is None:
         return {}
     from spectre_vit.optim import CosineSchedule
-    schedule = CosineSchedule(total_steps, warmup_steps, eta_min) if lr_schedule == "cosine" else None
-    return dict(schedule=schedule, max_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
+    schedule = CosineSchedule(total_steps // (k or 1), warmup_steps, eta_min) if lr_schedule == "cosine" else None
+    control = dict(schedule=schedule, max_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite)
+    if k is not None:
+        control["accumulate_steps"] = k
+    return control
 
 
 def _step_control_record(optimizer):
-    """the epoch record's step-control entries: ONE read of the optimizer's control block"""
+    """the epoch record's step-control entries: ONE read of the optimizer's control block.  Under accumulation they describe the last
+    window boundary, and the record gains the window length and the optimizer steps made so far (windows closed, dropped ones included)"""
     c = optimizer._read_ctl()
-    return {"LR": optimizer.last_lr(c)[0], "GradNorm": c["grad_norm"], "SkippedSteps": c["skipped"]}
+    rec = {"LR": optimizer.last_lr(c)[0], "GradNorm": c["grad_norm"], "SkippedSteps": c["skipped"]}
+    if optimizer.accumulate_steps is not None:
+        rec["AccumulateSteps"] = optimizer.accumulate_steps
+        rec["OptimizerSteps"] = c["sched_step"]
+    return rec
 
 
 def _ema_args(ema_decay, ema_warmup):
@@ -223,7 +236,7 @@ def _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, uint8):
 def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
           use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
           augment=False, batch_hook=None, graph_eval=False, lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None,
-          skip_nonfinite=False, ema_decay=None, ema_warmup=False, device_meter=False, device_loader=False):
+          skip_nonfinite=False, ema_decay=None, ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
@@ -242,6 +255,11 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     (spectre_vit.optim: CosineSchedule over total_steps = steps per epoch * epochs as train.py:202-203, gradient clipping, a step with
     an inf / NaN gradient dropped as GradScaler does, train.py:236-238).  With any of them the optimizer is FusedAdamW(capturable=True)
     on the eager path too, and the epoch record gains "LR" (the last step's rate), "GradNorm" (the last step's) and "SkippedSteps".
+    accumulate_steps=k: on-device gradient accumulation (FusedAdamW(accumulate_steps=k), part of the step control): every loader step
+    is a micro-step and every k-th applies the optimizer to the window's mean gradient -- with graph=True from the same replayed graph.
+    steps_per_epoch keeps counting micro-steps, the schedule's total_steps is (epochs * steps per epoch) // k, and a window may span
+    an epoch boundary.  The record gains "AccumulateSteps" and "OptimizerSteps" (windows closed by the epoch's end); "LR" and
+    "GradNorm" are the last boundary's.
     ema_decay (with ema_warmup): the optimizer keeps an exponential moving average of the weights inside its own launch
     (spectre_vit.optim.FusedAdamW(ema_decay=...), capturable=True on the eager path too).  After each epoch's validation a second pass
     runs on the averaged weights (inside optimizer.ema_weights(); through the same session with graph_eval=True) and the record gains
@@ -298,7 +316,7 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     gstep = session = None
     per_pass = (n_train // world) // batch_size
     control = _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite,
-                                 (min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass) * epochs)
+                                 (min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass) * epochs, accumulate_steps)
     meter = _train_meter(device_meter, min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass, device)
     if meter is not None:   # the training criterion logs every step it computes; validation must not
         criterion = CrossEntropyLoss(meter=meter)
@@ -493,7 +511,8 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                   use_amp=False, graph=False, augment=True, teacher=None, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75,
                   resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False,
                   lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False, ema_decay=None,
-                  ema_warmup=False, device_meter=False, device_loader=False, cache_teacher=False, teacher_cache_path=None):
+                  ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None, cache_teacher=False,
+                  teacher_cache_path=None):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -505,7 +524,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     sample (train.py:365-383).  The three per-batch losses the reference logs (train.py:355-359) are kept on the device and written
     once per epoch as {"step", "Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE"} lines: no host synchronisation per step.
     batch_hook(kind, step, img, label), kind "train" / "teacher" / "val" (test seam).  graph_eval, lr_schedule, warmup_steps, eta_min,
-    clip_grad_norm, skip_nonfinite, ema_decay, ema_warmup: as in train().
+    clip_grad_norm, skip_nonfinite, ema_decay, ema_warmup, accumulate_steps: as in train().
     cache_teacher=True: the teacher's view has no random op and the teacher is frozen, so its logits are a function of the sample alone;
     they are computed once before epoch 0 into a resident spectre_vit.distillation.TeacherLogitCache (sharded over the ranks; loaded from
     teacher_cache_path when that file exists and matches, saved there by rank 0 otherwise), a {"TeacherCache": ...} line is logged, and
@@ -567,7 +586,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     epoch_steps = min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass
     meter = _train_meter(device_meter, epoch_steps, device)
     criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight, **({} if meter is None else {"meter": meter}))
-    control = _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite, epoch_steps * epochs)
+    control = _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite, epoch_steps * epochs, accumulate_steps)
     if graph:
         from spectre_vit.optim import FusedAdamW
         optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
@@ -775,6 +794,9 @@ def build_parser():
     ap.add_argument("--eta-min", type=float, default=0.0, help="--lr-schedule cosine: the rate the schedule ends at")
     ap.add_argument("--clip-grad-norm", type=float, default=None, help="clip the global gradient norm (on the device, inside the optimizer step)")
     ap.add_argument("--skip-nonfinite", action="store_true", help="drop a step whose gradients hold an inf or a NaN (GradScaler's rule)")
+    ap.add_argument("--accumulate-steps", type=int, default=None, metavar="K",
+                    help="accumulate the gradients of K steps on the device and apply the optimizer to their mean on every K-th; "
+                         "--steps-per-epoch keeps counting micro-steps and the schedule runs over (epochs * steps) // K optimizer steps")
     ap.add_argument("--ema-decay", type=float, default=None,
                     help="keep an exponential moving average of the weights inside the optimizer launch, validate it after every epoch "
                          "and save model_ema_best.pt")
@@ -795,7 +817,7 @@ def build_parser():
 def main(argv=None):
     a = build_parser().parse_args(argv)
     control = dict(lr_schedule=a.lr_schedule, warmup_steps=a.warmup_steps, eta_min=a.eta_min, clip_grad_norm=a.clip_grad_norm,
-                   skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup)
+                   skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup, accumulate_steps=a.accumulate_steps)
     if a.distill_paired:
         train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out,
                       graph_eval=a.graph_eval, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache,

@@ -16,12 +16,19 @@ Weight averaging (``ema_decay=``): an exponential moving average of every parame
 optimizer launch itself from the registers that hold the new weight (``spv_adamw_multi_ema`` / ``spv_adamw_multi_ctl_ema``): no extra
 launch, nothing for the host to do between two graph replays, and a dropped step leaves the average where it is.
 ``ema_weights()`` / ``ema_state_dict()`` take the averaged weights to validation and into a checkpoint.
+
+Gradient accumulation (``accumulate_steps=k``): every ``step()`` is a micro-step that adds the gradients to fp32 accumulators; the
+device counts the micro-steps of the open window and every k-th one applies AdamW to the mean.  The decision is the control block's
+``apply`` flag, so ONE captured graph serves every micro-step.  Per micro-step: ``spv_grad_accumulate`` per group (it also forms the
+accumulator's sum of squares, so ``spv_grad_sumsq`` is not launched), one ``spv_step_control_accum``, ``spv_adamw_multi_ctl[_ema]`` per
+group on a table whose gradient column is the accumulator.
 """
 from __future__ import annotations
 
 import contextlib
 import math
 import struct
+import warnings
 
 import numpy as np
 import torch
@@ -30,7 +37,8 @@ from spectre_vit import _native, hip_ops
 from spectre_vit.hip_ops import _stream
 
 _CHUNK = 2048
-_CTL_FMT = "<ddfifii28x"   # include/spv.h: spv_step_ctl (a, b, clip_coef, apply, grad_norm, sched_step, skipped, reserved)
+_CTL_FMT = "<ddfifiii24x"   # include/spv.h: spv_step_ctl (a, b, clip_coef, apply, grad_norm, sched_step, skipped, micro, reserved)
+_CTL_FIELDS = ("a", "b", "clip_coef", "apply", "grad_norm", "sched_step", "skipped", "micro")
 _CTL_SCHEDULE, _CTL_CLIP, _CTL_SKIP = 1, 2, 4
 
 
@@ -89,7 +97,8 @@ def _check_ema_decay(d):
 
 class FusedAdamW(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False, static_grads=False,
-                 schedule=None, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, ema_exclude=None):
+                 schedule=None, max_grad_norm=None, skip_nonfinite=False, ema_decay=None, ema_warmup=False, ema_exclude=None,
+                 accumulate_steps=None):
         """static_grads=True: the caller expects fixed gradient addresses (spectre_vit.dp.GradReducer(model, always=True), or a
         captured graph): after two identical look-ups a step only COMPARES the gradient addresses with the table's (one tuple of
         ``p.grad.data_ptr()`` per group, every step: a caller that swapped a ``.grad`` gets a rebuilt table, never a write through a
@@ -117,7 +126,20 @@ class FusedAdamW(torch.optim.Optimizer):
         ema_weights() / ema_state_dict()), so e_1 = p_0 + w_1 (p_1 - p_0).  state_dict() carries ``"ema"`` with the moments and a
         resumed run continues the average bit for bit; loading a state that has no ``"ema"`` entries (a torch.optim.AdamW
         checkpoint, or one saved with averaging off) keeps this optimizer's ema_decay and starts the average from the current
-        parameters at the next step().  With averaging off in every group state_dict() is exactly what it was without the feature."""
+        parameters at the next step().  With averaging off in every group state_dict() is exactly what it was without the feature.
+
+        accumulate_steps=k (an int >= 1; None = off; needs capturable=True and switches the control path on): every step() call is a
+        MICRO-step, a window is k consecutive micro-steps, and a device counter ``micro`` holds the micro-steps already in the open
+        window.  A micro-step adds every gradient to an fp32 accumulator (micro == 0: acc = g, an assignment that does not read the old
+        contents; otherwise acc = fp32(acc + g)).  Inside the window (micro < k - 1 on entry) nothing else happens: no parameter, moment,
+        average, Adam step count or schedule count moves, and last_lr() / last_grad_norm() / schedule_step() keep describing the last
+        boundary.  The k-th micro-step is the boundary: the norm is that of the MEAN gradient acc / k (last_grad_norm()), the schedule
+        is read at t = schedule_step() and ticks once per window, clipping acts on the mean, AdamW applies acc * (clip / k), and
+        skip_nonfinite drops the whole window (skipped_steps() += 1) when any of its micro-steps held an inf or a NaN.  ``p.grad`` is never
+        rewritten (it holds the last micro-batch's gradient); with a per-micro-batch mean loss, acc / k is the mean over the window.
+        k = 1 is bit for bit the control path without the option.  The accumulators (one fp32 allocation per parameter group, read
+        with accumulated_grads()) do not travel in state_dict(): it carries ``micro_step`` beside the other counters, and
+        load_state_dict() restarts the window at micro = 0, warning when the saved window was open."""
         if lr < 0.0 or eps < 0.0 or weight_decay < 0.0 or not 0.0 <= betas[0] < 1.0 or not 0.0 <= betas[1] < 1.0:
             raise ValueError(f"FusedAdamW: invalid hyper-parameters lr={lr} betas={betas} eps={eps} weight_decay={weight_decay}")
         if schedule is not None and not isinstance(schedule, CosineSchedule):
@@ -127,10 +149,15 @@ class FusedAdamW(torch.optim.Optimizer):
         self.schedule = schedule
         self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
         self.skip_nonfinite = bool(skip_nonfinite)
-        self.step_control = schedule is not None or max_grad_norm is not None or self.skip_nonfinite
+        if accumulate_steps is not None and (isinstance(accumulate_steps, bool) or not isinstance(accumulate_steps, (int, np.integer))
+                                             or accumulate_steps < 1):
+            raise ValueError(f"FusedAdamW: accumulate_steps={accumulate_steps!r} must be None or an int >= 1")
+        self.accumulate_steps = None if accumulate_steps is None else int(accumulate_steps)
+        self.step_control = (schedule is not None or max_grad_norm is not None or self.skip_nonfinite
+                             or self.accumulate_steps is not None)
         if self.step_control and not capturable:
-            raise ValueError("FusedAdamW: schedule / max_grad_norm / skip_nonfinite need capturable=True (a skipped step leaves the "
-                             "Adam step count where it is, so the count must live on the device)")
+            raise ValueError("FusedAdamW: schedule / max_grad_norm / skip_nonfinite / accumulate_steps need capturable=True (a skipped "
+                             "step leaves the Adam step count where it is, so the count must live on the device)")
         defaults = dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable)
         params = list(params)
         # a group default like the others -- but only where averaging is asked for: without it the groups keep exactly their old keys
@@ -153,6 +180,7 @@ class FusedAdamW(torch.optim.Optimizer):
         self._ctl = None
         self._ctl_ws = None
         self._ctl_counts = (0, 0)   # (schedule step, skipped steps) a freshly built block starts from
+        self._acc = {}  # gradient accumulation: group index -> dict(sizes, flat, views), one allocation per group, made once
 
     def _table(self, gi, ps):
         """device-side pointer / chunk tables of one parameter group; rebuilt only when a pointer moved (in the steady state the
@@ -164,6 +192,11 @@ class FusedAdamW(torch.optim.Optimizer):
         emas = [self.state[p].get("ema") if self._averaged(p, self.param_groups[gi]) else None for p in ps]
         if any(e is not None for e in emas):
             key += tuple(0 if e is None else e.data_ptr() for e in emas)
+        accs = None
+        if self.accumulate_steps is not None:   # ... and so do the accumulators'
+            views = self._accumulators(gi)
+            accs = [views[id(p)] for p in ps]
+            key += tuple(a.data_ptr() for a in accs)
         t = self._tables.get(gi)
         if t is not None and t["key"] == key:
             return t
@@ -192,6 +225,11 @@ class FusedAdamW(torch.optim.Optimizer):
                  nchunks=len(ct))
         if any(e is not None for e in emas):   # one float* per table row, NULL = not averaged (include/spv.h: spv_adamw_multi_ema)
             t["ema_table"] = torch.tensor([0 if e is None else e.data_ptr() for e in emas], dtype=torch.int64).to(dev)
+        if accs is not None:   # one float* per table row for spv_grad_accumulate, and the optimizer's table with acc where g was
+            t["acc_table"] = torch.tensor([a.data_ptr() for a in accs], dtype=torch.int64).to(dev)
+            acc_rows = list(rows)
+            acc_rows[1::4] = [a.data_ptr() for a in accs]
+            t["table_acc"] = torch.tensor(acc_rows, dtype=torch.int64).to(dev)
         prev = self._tables.get(gi)
         if prev is not None:  # the step counter outlives a table rebuild
             for k in ("step", "host_step"):
@@ -200,11 +238,50 @@ class FusedAdamW(torch.optim.Optimizer):
         self._tables[gi] = t
         return t
 
+    def _accumulators(self, gi):
+        """id(p) -> the fp32 accumulator of every parameter of group gi: views, shaped like the parameters, into ONE allocation whose
+        slots are rounded up to four elements (16-byte aligned: spv_grad_accumulate's float4 walk relies on it).  Made once, for every
+        parameter of the group whether it has a gradient yet or not, so the addresses never move; never under a graph capture."""
+        group = self.param_groups[gi]
+        sizes = tuple(p.numel() for p in group["params"])
+        a = self._acc.get(gi)
+        if a is not None and a["sizes"] == sizes:
+            return a["views"]
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("FusedAdamW: the gradient accumulators have to be allocated while a HIP graph is being captured (their "
+                               "addresses cannot enter the pointer table inside a capture): run a warm-up step() before the capture")
+        cuda = [p for p in group["params"] if p.is_cuda]
+        if not cuda:
+            raise RuntimeError("FusedAdamW: parameters must be contiguous fp32 tensors on the GPU (no CPU fallback)")
+        flat = torch.zeros(sum((n + 3) // 4 * 4 for n in sizes), dtype=torch.float32, device=cuda[0].device)
+        assert flat.data_ptr() % 16 == 0
+        views, off = {}, 0
+        for p, n in zip(group["params"], sizes):
+            views[id(p)] = flat[off:off + n].view(p.shape)
+            off += (n + 3) // 4 * 4
+        self._acc[gi] = dict(sizes=sizes, flat=flat, views=views)
+        return views
+
+    def accumulated_grads(self):
+        """the accumulators, in parameter order (the tensors themselves, not copies): after a micro-step the fp32 sequential sum of the
+        open window's gradients, after a boundary the whole window's (divide by accumulate_steps for the mean)"""
+        if self.accumulate_steps is None:
+            raise RuntimeError("FusedAdamW: built without accumulate_steps: there is no accumulator")
+        return [self._accumulators(gi)[id(p)] for gi, group in enumerate(self.param_groups) for p in group["params"]]
+
+    def micro_step(self):
+        """micro-steps already in the open window: 0 right after a boundary (and before the first step)"""
+        if self.accumulate_steps is None:
+            raise RuntimeError("FusedAdamW: built without accumulate_steps: there is no micro-step count")
+        return self._read_ctl()["micro"]
+
     def load_state_dict(self, state_dict):
         """torch's loader replaces the per-parameter state (moments, step count): drop the device tables so that the next step() reads
         the loaded step count and points at the loaded moment tensors (in-place resume / rollback of an optimizer that has stepped).
         Averaging: a group's ``ema_decay`` comes from the loaded group when it has one and stays this optimizer's otherwise; parameters
-        that arrive without ``"ema"`` start their average from their current values at the next step()."""
+        that arrive without ``"ema"`` start their average from their current values at the next step().
+        Accumulation: the accumulators are not part of a checkpoint, so the window restarts (micro = 0: the next micro-step assigns);
+        a saved ``micro_step`` other than 0 means that the open window's micro-batches are lost, and warns."""
         if self._ema_swapped:
             raise RuntimeError("FusedAdamW: load_state_dict() inside ema_weights(): the parameters hold the averaged weights")
         mine = [g["ema_decay"] for g in self.param_groups] if "ema_decay" in self.defaults else None
@@ -222,6 +299,9 @@ class FusedAdamW(torch.optim.Optimizer):
             sc = state_dict.get("step_control") or {}
             self._ctl_counts = (int(sc.get("schedule_step", 0)), int(sc.get("skipped_steps", 0)))
             self._ctl = self._ctl_ws = None
+            if self.accumulate_steps is not None and int(sc.get("micro_step", 0)) != 0:
+                warnings.warn(f"FusedAdamW.load_state_dict: the state was saved {int(sc['micro_step'])} micro-step(s) into an accumulation "
+                              "window; the accumulators are not checkpointed, so the window restarts at micro-step 0", stacklevel=2)
 
     def state_dict(self):
         """torch's layout; with step control on, one more top-level entry carries the schedule count and the skipped count, so that a
@@ -233,6 +313,8 @@ class FusedAdamW(torch.optim.Optimizer):
         if self.step_control:
             c = self._read_ctl()
             sd["step_control"] = dict(schedule_step=c["sched_step"], skipped_steps=c["skipped"])
+            if self.accumulate_steps is not None:
+                sd["step_control"]["micro_step"] = c["micro"]
         return sd
 
     # -- weight averaging ---------------------------------------------------------------------------------------------------------
@@ -313,30 +395,33 @@ class FusedAdamW(torch.optim.Optimizer):
     def _read_ctl(self):
         """the control block as the last step() left it (synchronises the host: meant for once an epoch)"""
         if not self.step_control:
-            raise RuntimeError("FusedAdamW: built without schedule / max_grad_norm / skip_nonfinite: there is no step-control block")
-        return dict(zip(("a", "b", "clip_coef", "apply", "grad_norm", "sched_step", "skipped"),
-                        struct.unpack(_CTL_FMT, self.control_block_bytes())))
+            raise RuntimeError("FusedAdamW: built without schedule / max_grad_norm / skip_nonfinite / accumulate_steps: there is no "
+                               "step-control block")
+        return dict(zip(_CTL_FIELDS, struct.unpack(_CTL_FMT, self.control_block_bytes())))
 
     def last_lr(self, _ctl=None):
-        """the rate the last step() used, one float per parameter group: float32(a * lr + b), the kernel's own expression"""
+        """the rate the last step() used, one float per parameter group: float32(a * lr + b), the kernel's own expression (under
+        accumulation: the last boundary's)"""
         c = _ctl or self._read_ctl()
         return [float(np.float32(np.float64(c["a"]) * np.float64(float(g["lr"])) + np.float64(c["b"]))) for g in self.param_groups]
 
     def last_grad_norm(self):
-        """the L2 norm over all gradients that the last step() saw (before clipping)"""
+        """the L2 norm over all gradients that the last step() saw (before clipping); under accumulation the norm of the last
+        boundary's MEAN gradient, accumulator / accumulate_steps"""
         return self._read_ctl()["grad_norm"]
 
     def skipped_steps(self):
         return self._read_ctl()["skipped"]
 
     def schedule_step(self):
-        """step() calls so far, skipped ones included: the schedule's t of the next step"""
+        """step() calls so far, skipped ones included: the schedule's t of the next step (under accumulation: windows closed so far,
+        dropped ones included -- one tick per window)"""
         return self._read_ctl()["sched_step"]
 
     def control_block_bytes(self):
         """the 64 raw bytes of the control block: the device's, or (before the first step) the ones it will start from"""
         if self._ctl is None:
-            return struct.pack(_CTL_FMT, 1.0, 0.0, 1.0, 1, 0.0, *self._ctl_counts)
+            return struct.pack(_CTL_FMT, 1.0, 0.0, 1.0, 1, 0.0, *self._ctl_counts, 0)
         return self._ctl.cpu().numpy().tobytes()
 
     def _control_workspace(self, active):
@@ -364,19 +449,29 @@ class FusedAdamW(torch.optim.Optimizer):
     def _step_controlled(self, active):
         ws = self._control_workspace(active)
         st = _stream()
+        k = self.accumulate_steps
         for (_, t), off in zip(active, ws["offs"]):
+            if k is not None:   # acc (+)= g and the NEW accumulator's sum of squares in one walk
+                _native.call("spv_grad_accumulate", t["table"].data_ptr(), t["acc_table"].data_ptr(), t["chunk_tensor"].data_ptr(),
+                             t["chunk_off"].data_ptr(), t["sizes"].data_ptr(), t["nchunks"], self._ctl.data_ptr(),
+                             ws["partials"].data_ptr() + 8 * off, st)
+                continue
             _native.call("spv_grad_sumsq", t["table"].data_ptr(), t["chunk_tensor"].data_ptr(), t["chunk_off"].data_ptr(),
                          t["sizes"].data_ptr(), t["nchunks"], ws["partials"].data_ptr() + 8 * off, st)
         sch = self.schedule
         flags = ((_CTL_SCHEDULE if sch is not None else 0) | (_CTL_CLIP if self.max_grad_norm is not None else 0)
                  | (_CTL_SKIP if self.skip_nonfinite else 0))
         # (this launch also advances the groups' Adam step counts -- when the step is applied)
-        _native.call("spv_step_control", ws["partials"].data_ptr(), ws["n"], ws["step_ptrs"].data_ptr(), len(active), self._ctl.data_ptr(),
-                     flags, sch.warmup_steps if sch else 0, sch.total_steps if sch else 0, sch.eta_min if sch else 0.0,
-                     self.max_grad_norm or 0.0, st)
+        ctl_args = (ws["partials"].data_ptr(), ws["n"], ws["step_ptrs"].data_ptr(), len(active), self._ctl.data_ptr(), flags,
+                    sch.warmup_steps if sch else 0, sch.total_steps if sch else 0, sch.eta_min if sch else 0.0, self.max_grad_norm or 0.0)
+        if k is not None:   # inside a window: apply = 0 and the count; at its boundary: the block from the mean gradient's norm
+            _native.call("spv_step_control_accum", *ctl_args, k, st)
+        else:
+            _native.call("spv_step_control", *ctl_args, st)
         for group, t in active:
             b1, b2 = group["betas"]
-            args = (t["table"].data_ptr(), t["chunk_tensor"].data_ptr(), t["chunk_off"].data_ptr(), t["sizes"].data_ptr(), t["nchunks"],
+            table = t["table" if k is None else "table_acc"]   # accumulation: the g column holds the accumulators
+            args = (table.data_ptr(), t["chunk_tensor"].data_ptr(), t["chunk_off"].data_ptr(), t["sizes"].data_ptr(), t["nchunks"],
                     float(group["lr"]), float(b1), float(b2), 1.0 - b1, 1.0 - b2, float(group["eps"]), float(group["weight_decay"]),
                     t["step"].data_ptr(), self._ctl.data_ptr())
             if "ema_table" in t:

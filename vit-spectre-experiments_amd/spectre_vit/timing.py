@@ -97,6 +97,9 @@ _WORK_MODELS = {
     # step control: the gradient read once (chunks as above), the per-chunk fp64 partials folded, the optimizer's seven streams
     "spv_grad_sumsq": lambda i: ("grad_sumsq", i[0:1], F32, "hbm", 4.0 * 2048 * i[0]),
     "spv_step_control": lambda i: ("step_control", i[0:2], F32, "hbm", 8.0 * i[0] + 64),
+    # gradient accumulation: the gradient read, the accumulator read and written (chunks as above); the control launch as without
+    "spv_grad_accumulate": lambda i: ("grad_accumulate", i[0:1], F32, "hbm", 3.0 * 4 * 2048 * i[0]),
+    "spv_step_control_accum": lambda i: ("step_control_accum", i[0:2], F32, "hbm", 8.0 * i[0] + 64),
     "spv_adamw_multi_ctl": lambda i: ("adamw_multi_ctl", i[0:1], F32, "hbm", 7.0 * 4 * 2048 * i[0]),
     # one launch for the step's small opening jobs: the sum of its roles' compulsory bytes, handed over as the caller's hint
     "spv_step_prologue": lambda i: ("step_prologue", (), BF16, "hbm", float(i[-1])),
