@@ -491,6 +491,51 @@ int spv_adamw_multi_ctl_ema(const void* table, const int* chunk_tensor, const in
                             const float* step_dev, const spv_step_ctl* ctl, float* const* ema_table, float ema_weight, int ema_warmup,
                             void* stream);
 
+/* ---- torch.optim.Adam and torch.optim.SGD on the same launches ------------------------------------------------
+ * The two other optimizer lines of the script (spectre_vit/repl/train.py:197-198, :307).  Chunk tables, control block, step counts
+ * and the moving average are AdamW's; the four forms of each rule take the arguments of the spv_adamw_multi form of the same suffix.
+ *
+ * Adam (amsgrad / maximize off): AdamW's expressions with the decay in the gradient, d = g * clip + weight_decay * p (product and sum
+ * rounded separately; nothing added when weight_decay == 0), and no decoupled factor.  With weight_decay == 0 the results equal
+ * spv_adamw_multi*'s bit for bit.  Checked besides AdamW's checks: betas in [0, 1), eps >= 0, weight_decay >= 0, lr >= 0. */
+int spv_adam_multi(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr, float beta1,
+                   float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay, float bias_correction1,
+                   float bias_correction2, const float* step_dev, void* stream);
+int spv_adam_multi_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr,
+                       float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                       float bias_correction1, float bias_correction2, const float* step_dev, float* const* ema_table, float ema_weight,
+                       int ema_warmup, float ema_step, void* stream);
+int spv_adam_multi_ctl(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, double base_lr,
+                       float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                       const float* step_dev, const spv_step_ctl* ctl, void* stream);
+int spv_adam_multi_ctl_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, double base_lr,
+                           float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                           const float* step_dev, const spv_step_ctl* ctl, float* const* ema_table, float ema_weight, int ema_warmup,
+                           void* stream);
+
+/* SGD (maximize off).  `table` rows are {float* p; const float* g; float* buf; unused}; buf is neither read nor written (and may be
+ * NULL) with momentum == 0.  Per element, every line ONE fp32 rounding, the same on the float4 and on the scalar walk:
+ *     d = g                                   (_ctl: d = g * clip_coef)
+ *     weight_decay != 0:   t = weight_decay * p;  d = d + t
+ *     momentum != 0:       s == 1:  buf = d       else:  t1 = momentum * buf;  t2 = one_minus_dampening * d;  buf = t1 + t2
+ *                          nesterov:  t = momentum * buf;  d = d + t           else:  d = buf
+ *     t = lr * d;  p = p - t
+ * s = the group's step count of this step, already advanced (1 on its first applied step, where torch clones the gradient into the
+ * buffer): *step_dev, or -- step_dev == NULL, spv_sgd_multi[_ema] only -- `step` by value (>= 1).  The _ema forms' warm-up reads the
+ * same s.  one_minus_dampening = 1 - dampening formed in double and rounded once by the caller.  Checked: momentum in [0, 1),
+ * one_minus_dampening in (0, 1] (dampening in [0, 1)), weight_decay >= 0, lr >= 0, nesterov only with momentum > 0 and dampening == 0. */
+int spv_sgd_multi(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr, float momentum,
+                  float one_minus_dampening, float weight_decay, int nesterov, float step, const float* step_dev, void* stream);
+int spv_sgd_multi_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr,
+                      float momentum, float one_minus_dampening, float weight_decay, int nesterov, float step, const float* step_dev,
+                      float* const* ema_table, float ema_weight, int ema_warmup, void* stream);
+int spv_sgd_multi_ctl(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, double base_lr,
+                      float momentum, float one_minus_dampening, float weight_decay, int nesterov, const float* step_dev,
+                      const spv_step_ctl* ctl, void* stream);
+int spv_sgd_multi_ctl_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, double base_lr,
+                          float momentum, float one_minus_dampening, float weight_decay, int nesterov, const float* step_dev,
+                          const spv_step_ctl* ctl, float* const* ema_table, float ema_weight, int ema_warmup, void* stream);
+
 /* ---- Walsh-Hadamard butterflies along the last axis -----------------------------------
  * spectre_vit/models/spectre/hadamar.py: fwht :12-32 / hadamard_transform :83-112 (mode 0, natural order; scale = n^-1/2
  * when normalised), fwht_fast :58-80 (mode 1: every stage interleaves sum / difference, un-normalised) and its transpose

@@ -20,7 +20,11 @@ constexpr int ADAM_CHUNK = 2048;  // elements per workgroup: 256 threads x 2 x f
 // EMA = false -- the vector and the scalar walk round m and p differently, so the walk must not depend on e or the average would
 // perturb the training it follows; an e that is not 16-byte aligned is read and written element by element inside the vector walk.
 // The e arithmetic is the same expression on every path.
-template <bool SCALED, bool EMA = false>
+//
+// L2: torch.optim.Adam's rule (spv_optim_rules.h: adam_chunk) -- the decay joins the gradient, d = g + wd * p (product and sum rounded
+// separately, skipped when wd == 0, as torch's grad.add(p, alpha=wd)), and the decoupled factor is 1.  Every other expression is the
+// one AdamW uses, so with wd == 0 the two rules give the same bits on either walk.
+template <bool SCALED, bool EMA = false, bool L2 = false>
 __device__ __forceinline__ void adamw_chunk(const AdamTensor a, int n, int off, float lr, float beta1, float beta2, float omb1, float omb2,
                                             float eps, float wd, float bc1, float bc2, const float* __restrict__ step_dev, float gscale,
                                             float* __restrict__ e = nullptr, float ema_w = 0.0f, int ema_warmup = 0,
@@ -33,7 +37,8 @@ __device__ __forceinline__ void adamw_chunk(const AdamTensor a, int n, int off, 
         bc1 = 1.0f - powf(beta1, s);
         bc2 = 1.0f - powf(beta2, s);
     }
-    const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2), decay = fmaf(-lr, wd, 1.0f);
+    const float step_size = lr / bc1, inv_sqrt_bc2 = rsqrtf(bc2), decay = L2 ? 1.0f : fmaf(-lr, wd, 1.0f);
+    const bool l2 = L2 && wd != 0.0f;
     float w_t = ema_w;
     if (EMA && ema_warmup) w_t = fmaxf(ema_w, 9.0f / (10.0f + (step_dev != nullptr ? *step_dev : ema_step)));
     const bool averaged = EMA && e != nullptr;
@@ -55,7 +60,11 @@ __device__ __forceinline__ void adamw_chunk(const AdamTensor a, int n, int off, 
             float* pp = &p.x; float* mm = &m.x; float* vv = &v.x; const float* gg = &g.x; float* ee = &ev.x;
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
-                const float gu = SCALED ? gg[u] * gscale : gg[u];
+                float gu = SCALED ? gg[u] * gscale : gg[u];
+                if (L2 && l2) {
+                    const float t = wd * pp[u];
+                    gu = gu + t;
+                }
                 mm[u] = fmaf(beta1, mm[u], omb1 * gu);
                 vv[u] = fmaf(omb2 * gu, gu, beta2 * vv[u]);
                 pp[u] = fmaf(pp[u], decay, -(step_size * mm[u] / fmaf(sqrtf(vv[u]), inv_sqrt_bc2, eps)));
@@ -75,7 +84,11 @@ __device__ __forceinline__ void adamw_chunk(const AdamTensor a, int n, int off, 
             for (int u = 0; u < 4; ++u) {
                 const int j = i + u;
                 if (j >= n) break;
-                const float g = SCALED ? a.g[j] * gscale : a.g[j];
+                float g = SCALED ? a.g[j] * gscale : a.g[j];
+                if (L2 && l2) {
+                    const float t = wd * a.p[j];
+                    g = g + t;
+                }
                 const float m = fmaf(omb1, g, beta1 * a.m[j]);
                 const float v = beta2 * a.v[j] + omb2 * g * g;
                 a.m[j] = m;

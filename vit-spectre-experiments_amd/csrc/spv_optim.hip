@@ -1,9 +1,11 @@
 // spv_optim.hip -- on-device step control of the optimizer (include/spv.h: spv_step_ctl): the gradient's sum of squares (or, under
 // gradient accumulation, the accumulator's, formed while the gradient is added to it), the one-workgroup kernel that turns it and the
 // step counts into this step's learning rate / clip coefficient / apply flag, and the AdamW launch that reads them.  Nothing here is decided on the host, so a captured training step follows the schedule and skips a
-// non-finite gradient on every replay.
+// non-finite gradient on every replay.  At the end of the file: the launches of the two other update rules, torch.optim.Adam and
+// torch.optim.SGD (spv_optim_rules.h), which read the same control block.
 #include "spv_common.h"
 #include "spv_adamw_core.h"
+#include "spv_optim_rules.h"   // torch.optim.Adam and torch.optim.SGD on the same walk and the same control block (end of this file)
 
 #include <math.h>
 
@@ -197,6 +199,74 @@ __global__ __launch_bounds__(256) void adamw_multi_ctl_ema_kernel(const AdamTens
     adamw_chunk<true, true>(a, n, off, lr, beta1, beta2, omb1, omb2, eps, wd, 0.0f, 0.0f, step_dev, ctl->clip_coef, ema_tab[t], ema_w,
                             ema_warmup, 0.0f);
 }
+
+// ---------------------------------------------------------------------------------------------------------
+// The two other update rules of the reference's script on the same walk (spv_optim_rules.h): torch.optim.Adam and torch.optim.SGD,
+// each as a launch that takes the rate by value and as one that reads rate, gradient scale and the apply flag from the control
+// block, with and without the weights' moving average (EMA: ema_tab is read only then).
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_multi_kernel(const AdamTensor* __restrict__ tab, const int* __restrict__ chunk_tensor,
+                                                         const int* __restrict__ chunk_off, const int* __restrict__ sizes, float lr,
+                                                         float beta1, float beta2, float omb1, float omb2, float eps, float wd, float bc1,
+                                                         float bc2, const float* __restrict__ step_dev, float* const* __restrict__ ema_tab,
+                                                         float ema_w, int ema_warmup, float ema_step) {
+    const int t = chunk_tensor[blockIdx.x];
+    const int off = chunk_off[blockIdx.x];
+    const AdamTensor a = tab[t];
+    const int n = sizes[t];
+    adam_chunk<false, EMA>(a, n, off, lr, beta1, beta2, omb1, omb2, eps, wd, bc1, bc2, step_dev, 1.0f, EMA ? ema_tab[t] : nullptr, ema_w,
+                           ema_warmup, ema_step);
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void adam_multi_ctl_kernel(const AdamTensor* __restrict__ tab, const int* __restrict__ chunk_tensor,
+                                                             const int* __restrict__ chunk_off, const int* __restrict__ sizes, double base_lr,
+                                                             float beta1, float beta2, float omb1, float omb2, float eps, float wd,
+                                                             const float* __restrict__ step_dev, const spv_step_ctl* __restrict__ ctl,
+                                                             float* const* __restrict__ ema_tab, float ema_w, int ema_warmup) {
+    if (ctl->apply == 0) return;   // a dropped step writes nothing
+    const float lr = (float)__dadd_rn(__dmul_rn(ctl->a, base_lr), ctl->b);
+    const int t = chunk_tensor[blockIdx.x];
+    const int off = chunk_off[blockIdx.x];
+    const AdamTensor a = tab[t];
+    const int n = sizes[t];
+    adam_chunk<true, EMA>(a, n, off, lr, beta1, beta2, omb1, omb2, eps, wd, 0.0f, 0.0f, step_dev, ctl->clip_coef,
+                          EMA ? ema_tab[t] : nullptr, ema_w, ema_warmup, 0.0f);
+}
+
+// SGD: s = this step's count of the group (already advanced), *step_dev or -- step_dev == NULL -- `step` by value.  s == 1 is the
+// first applied step, where the momentum buffer is assigned and not read.
+template <bool EMA>
+__global__ __launch_bounds__(256) void sgd_multi_kernel(const AdamTensor* __restrict__ tab, const int* __restrict__ chunk_tensor,
+                                                        const int* __restrict__ chunk_off, const int* __restrict__ sizes, float lr,
+                                                        float momentum, float omd, float wd, int nesterov, float step,
+                                                        const float* __restrict__ step_dev, float* const* __restrict__ ema_tab, float ema_w,
+                                                        int ema_warmup) {
+    const float s = step_dev != nullptr ? *step_dev : step;
+    const int t = chunk_tensor[blockIdx.x];
+    const int off = chunk_off[blockIdx.x];
+    const AdamTensor a = tab[t];
+    const int n = sizes[t];
+    const SgdRule r = {lr, momentum, omd, wd, nesterov != 0, s == 1.0f};
+    sgd_chunk<false, EMA>(a, n, off, r, s, 1.0f, EMA ? ema_tab[t] : nullptr, ema_w, ema_warmup);
+}
+
+template <bool EMA>
+__global__ __launch_bounds__(256) void sgd_multi_ctl_kernel(const AdamTensor* __restrict__ tab, const int* __restrict__ chunk_tensor,
+                                                            const int* __restrict__ chunk_off, const int* __restrict__ sizes, double base_lr,
+                                                            float momentum, float omd, float wd, int nesterov,
+                                                            const float* __restrict__ step_dev, const spv_step_ctl* __restrict__ ctl,
+                                                            float* const* __restrict__ ema_tab, float ema_w, int ema_warmup) {
+    if (ctl->apply == 0) return;   // a dropped step writes nothing: no parameter, no buffer, no average
+    const float lr = (float)__dadd_rn(__dmul_rn(ctl->a, base_lr), ctl->b);
+    const float s = *step_dev;
+    const int t = chunk_tensor[blockIdx.x];
+    const int off = chunk_off[blockIdx.x];
+    const AdamTensor a = tab[t];
+    const int n = sizes[t];
+    const SgdRule r = {lr, momentum, omd, wd, nesterov != 0, s == 1.0f};
+    sgd_chunk<true, EMA>(a, n, off, r, s, ctl->clip_coef, EMA ? ema_tab[t] : nullptr, ema_w, ema_warmup);
+}
 }  // namespace
 
 extern "C" int spv_grad_sumsq(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
@@ -293,5 +363,165 @@ extern "C" int spv_adamw_multi_ctl_ema(const void* table, const int* chunk_tenso
                        static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, base_lr, beta1, beta2, one_minus_beta1,
                        one_minus_beta2, eps, weight_decay, step_dev, ctl, ema_table, ema_weight, ema_warmup);
     SPV_LAUNCH_CHECK("spv_adamw_multi_ctl_ema");
+    return 0;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// torch.optim.Adam and torch.optim.SGD: the checks every form of a rule shares, then the eight entry points.
+namespace {
+int adam_args_ok(const char* who, const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
+                 float beta1, float beta2, float eps, float wd) {
+    SPV_CHECK(nchunks >= 0, "%s: nchunks = %d", who, nchunks);
+    SPV_CHECK(table && chunk_tensor && chunk_off && sizes, "%s: null table", who);
+    SPV_CHECK(beta1 >= 0.0f && beta1 < 1.0f && beta2 >= 0.0f && beta2 < 1.0f, "%s: betas (%g, %g) must be in [0, 1)", who, (double)beta1,
+              (double)beta2);
+    SPV_CHECK(eps >= 0.0f && wd >= 0.0f, "%s: eps = %g and weight_decay = %g must be >= 0", who, (double)eps, (double)wd);
+    return 0;
+}
+
+int sgd_args_ok(const char* who, const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
+                float momentum, float omd, float wd, int nesterov) {
+    SPV_CHECK(nchunks >= 0, "%s: nchunks = %d", who, nchunks);
+    SPV_CHECK(table && chunk_tensor && chunk_off && sizes, "%s: null table", who);
+    SPV_CHECK(momentum >= 0.0f && momentum < 1.0f, "%s: momentum = %g must be in [0, 1)", who, (double)momentum);
+    SPV_CHECK(omd > 0.0f && omd <= 1.0f, "%s: one_minus_dampening = %g must be in (0, 1] (dampening in [0, 1))", who, (double)omd);
+    SPV_CHECK(wd >= 0.0f, "%s: weight_decay = %g must be >= 0", who, (double)wd);
+    SPV_CHECK(!nesterov || (momentum > 0.0f && omd == 1.0f), "%s: nesterov needs momentum > 0 and dampening == 0", who);
+    return 0;
+}
+
+int ema_args_ok(const char* who, float* const* ema_table, float ema_weight) {
+    SPV_CHECK(ema_table, "%s: null ema_table (use the form without _ema for a group that is not averaged)", who);
+    SPV_CHECK(ema_weight > 0.0f && ema_weight <= 1.0f, "%s: ema_weight = %g must be in (0, 1]", who, (double)ema_weight);
+    return 0;
+}
+}  // namespace
+
+#define SPV_RULE_TRY(expr) do { if (int rc_ = (expr)) return rc_; } while (0)
+
+extern "C" int spv_adam_multi(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr,
+                              float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                              float bias_correction1, float bias_correction2, const float* step_dev, void* stream) {
+    SPV_RULE_TRY(adam_args_ok("spv_adam_multi", table, chunk_tensor, chunk_off, sizes, nchunks, beta1, beta2, eps, weight_decay));
+    SPV_CHECK(lr >= 0.0f, "spv_adam_multi: lr = %g must be >= 0", (double)lr);
+    SPV_CHECK(step_dev != nullptr || (bias_correction1 > 0.0f && bias_correction2 > 0.0f), "spv_adam_multi: bias corrections must be > 0");
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(adam_multi_kernel<false>, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, lr, beta1, beta2, one_minus_beta1,
+                       one_minus_beta2, eps, weight_decay, bias_correction1, bias_correction2, step_dev,
+                       static_cast<float* const*>(nullptr), 0.0f, 0, 0.0f);
+    SPV_LAUNCH_CHECK("spv_adam_multi");
+    return 0;
+}
+
+extern "C" int spv_adam_multi_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr,
+                                  float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps, float weight_decay,
+                                  float bias_correction1, float bias_correction2, const float* step_dev, float* const* ema_table,
+                                  float ema_weight, int ema_warmup, float ema_step, void* stream) {
+    SPV_RULE_TRY(adam_args_ok("spv_adam_multi_ema", table, chunk_tensor, chunk_off, sizes, nchunks, beta1, beta2, eps, weight_decay));
+    SPV_RULE_TRY(ema_args_ok("spv_adam_multi_ema", ema_table, ema_weight));
+    SPV_CHECK(lr >= 0.0f, "spv_adam_multi_ema: lr = %g must be >= 0", (double)lr);
+    SPV_CHECK(step_dev != nullptr || (bias_correction1 > 0.0f && bias_correction2 > 0.0f), "spv_adam_multi_ema: bias corrections must be > 0");
+    SPV_CHECK(!ema_warmup || step_dev != nullptr || ema_step >= 1.0f, "spv_adam_multi_ema: ema_step = %g must be >= 1 (the step count of this step)",
+              (double)ema_step);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(adam_multi_kernel<true>, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, lr, beta1, beta2, one_minus_beta1,
+                       one_minus_beta2, eps, weight_decay, bias_correction1, bias_correction2, step_dev, ema_table, ema_weight, ema_warmup,
+                       ema_step);
+    SPV_LAUNCH_CHECK("spv_adam_multi_ema");
+    return 0;
+}
+
+extern "C" int spv_adam_multi_ctl(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
+                                  double base_lr, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                                  float weight_decay, const float* step_dev, const spv_step_ctl* ctl, void* stream) {
+    SPV_RULE_TRY(adam_args_ok("spv_adam_multi_ctl", table, chunk_tensor, chunk_off, sizes, nchunks, beta1, beta2, eps, weight_decay));
+    SPV_CHECK(step_dev && ctl, "spv_adam_multi_ctl: null step count / control block");
+    SPV_CHECK(base_lr >= 0.0, "spv_adam_multi_ctl: base_lr = %g must be >= 0", base_lr);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(adam_multi_ctl_kernel<false>, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, base_lr, beta1, beta2, one_minus_beta1,
+                       one_minus_beta2, eps, weight_decay, step_dev, ctl, static_cast<float* const*>(nullptr), 0.0f, 0);
+    SPV_LAUNCH_CHECK("spv_adam_multi_ctl");
+    return 0;
+}
+
+extern "C" int spv_adam_multi_ctl_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
+                                      double base_lr, float beta1, float beta2, float one_minus_beta1, float one_minus_beta2, float eps,
+                                      float weight_decay, const float* step_dev, const spv_step_ctl* ctl, float* const* ema_table,
+                                      float ema_weight, int ema_warmup, void* stream) {
+    SPV_RULE_TRY(adam_args_ok("spv_adam_multi_ctl_ema", table, chunk_tensor, chunk_off, sizes, nchunks, beta1, beta2, eps, weight_decay));
+    SPV_RULE_TRY(ema_args_ok("spv_adam_multi_ctl_ema", ema_table, ema_weight));
+    SPV_CHECK(step_dev && ctl, "spv_adam_multi_ctl_ema: null step count / control block");
+    SPV_CHECK(base_lr >= 0.0, "spv_adam_multi_ctl_ema: base_lr = %g must be >= 0", base_lr);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(adam_multi_ctl_kernel<true>, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, base_lr, beta1, beta2, one_minus_beta1,
+                       one_minus_beta2, eps, weight_decay, step_dev, ctl, ema_table, ema_weight, ema_warmup);
+    SPV_LAUNCH_CHECK("spv_adam_multi_ctl_ema");
+    return 0;
+}
+
+extern "C" int spv_sgd_multi(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr,
+                             float momentum, float one_minus_dampening, float weight_decay, int nesterov, float step, const float* step_dev,
+                             void* stream) {
+    SPV_RULE_TRY(sgd_args_ok("spv_sgd_multi", table, chunk_tensor, chunk_off, sizes, nchunks, momentum, one_minus_dampening, weight_decay,
+                             nesterov));
+    SPV_CHECK(lr >= 0.0f, "spv_sgd_multi: lr = %g must be >= 0", (double)lr);
+    SPV_CHECK(step_dev != nullptr || step >= 1.0f, "spv_sgd_multi: null step count and step = %g (this step's count, >= 1)", (double)step);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(sgd_multi_kernel<false>, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, lr, momentum, one_minus_dampening, weight_decay,
+                       nesterov, step, step_dev, static_cast<float* const*>(nullptr), 0.0f, 0);
+    SPV_LAUNCH_CHECK("spv_sgd_multi");
+    return 0;
+}
+
+extern "C" int spv_sgd_multi_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks, float lr,
+                                 float momentum, float one_minus_dampening, float weight_decay, int nesterov, float step,
+                                 const float* step_dev, float* const* ema_table, float ema_weight, int ema_warmup, void* stream) {
+    SPV_RULE_TRY(sgd_args_ok("spv_sgd_multi_ema", table, chunk_tensor, chunk_off, sizes, nchunks, momentum, one_minus_dampening,
+                             weight_decay, nesterov));
+    SPV_RULE_TRY(ema_args_ok("spv_sgd_multi_ema", ema_table, ema_weight));
+    SPV_CHECK(lr >= 0.0f, "spv_sgd_multi_ema: lr = %g must be >= 0", (double)lr);
+    SPV_CHECK(step_dev != nullptr || step >= 1.0f, "spv_sgd_multi_ema: null step count and step = %g (this step's count, >= 1)", (double)step);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(sgd_multi_kernel<true>, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, lr, momentum, one_minus_dampening, weight_decay,
+                       nesterov, step, step_dev, ema_table, ema_weight, ema_warmup);
+    SPV_LAUNCH_CHECK("spv_sgd_multi_ema");
+    return 0;
+}
+
+extern "C" int spv_sgd_multi_ctl(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
+                                 double base_lr, float momentum, float one_minus_dampening, float weight_decay, int nesterov,
+                                 const float* step_dev, const spv_step_ctl* ctl, void* stream) {
+    SPV_RULE_TRY(sgd_args_ok("spv_sgd_multi_ctl", table, chunk_tensor, chunk_off, sizes, nchunks, momentum, one_minus_dampening,
+                             weight_decay, nesterov));
+    SPV_CHECK(step_dev && ctl, "spv_sgd_multi_ctl: null step count / control block");
+    SPV_CHECK(base_lr >= 0.0, "spv_sgd_multi_ctl: base_lr = %g must be >= 0", base_lr);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(sgd_multi_ctl_kernel<false>, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, base_lr, momentum, one_minus_dampening,
+                       weight_decay, nesterov, step_dev, ctl, static_cast<float* const*>(nullptr), 0.0f, 0);
+    SPV_LAUNCH_CHECK("spv_sgd_multi_ctl");
+    return 0;
+}
+
+extern "C" int spv_sgd_multi_ctl_ema(const void* table, const int* chunk_tensor, const int* chunk_off, const int* sizes, int nchunks,
+                                     double base_lr, float momentum, float one_minus_dampening, float weight_decay, int nesterov,
+                                     const float* step_dev, const spv_step_ctl* ctl, float* const* ema_table, float ema_weight,
+                                     int ema_warmup, void* stream) {
+    SPV_RULE_TRY(sgd_args_ok("spv_sgd_multi_ctl_ema", table, chunk_tensor, chunk_off, sizes, nchunks, momentum, one_minus_dampening,
+                             weight_decay, nesterov));
+    SPV_RULE_TRY(ema_args_ok("spv_sgd_multi_ctl_ema", ema_table, ema_weight));
+    SPV_CHECK(step_dev && ctl, "spv_sgd_multi_ctl_ema: null step count / control block");
+    SPV_CHECK(base_lr >= 0.0, "spv_sgd_multi_ctl_ema: base_lr = %g must be >= 0", base_lr);
+    if (nchunks == 0) return 0;
+    hipLaunchKernelGGL(sgd_multi_ctl_kernel<true>, dim3(nchunks), dim3(256), 0, static_cast<hipStream_t>(stream),
+                       static_cast<const AdamTensor*>(table), chunk_tensor, chunk_off, sizes, base_lr, momentum, one_minus_dampening,
+                       weight_decay, nesterov, step_dev, ctl, ema_table, ema_weight, ema_warmup);
+    SPV_LAUNCH_CHECK("spv_sgd_multi_ctl_ema");
     return 0;
 }

@@ -117,6 +117,14 @@ SIGNATURES = {
     "spv_step_control_accum": [c_vp, c_i, c_vp, c_i, c_vp, c_i, c_i, c_i, c_d, c_f, c_i, c_vp],
     "spv_adamw_multi_ctl": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_vp],
     "spv_adamw_multi_ctl_ema": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_vp, c_f, c_i, c_vp],
+    "spv_adam_multi": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp],
+    "spv_adam_multi_ema": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_f, c_i, c_f, c_vp],
+    "spv_adam_multi_ctl": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_vp],
+    "spv_adam_multi_ctl_ema": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_f, c_f, c_f, c_vp, c_vp, c_vp, c_f, c_i, c_vp],
+    "spv_sgd_multi": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_i, c_f, c_vp, c_vp],
+    "spv_sgd_multi_ema": [c_vp, c_vp, c_vp, c_vp, c_i, c_f, c_f, c_f, c_f, c_i, c_f, c_vp, c_vp, c_f, c_i, c_vp],
+    "spv_sgd_multi_ctl": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_i, c_vp, c_vp, c_vp],
+    "spv_sgd_multi_ctl_ema": [c_vp, c_vp, c_vp, c_vp, c_i, c_d, c_f, c_f, c_f, c_i, c_vp, c_vp, c_vp, c_f, c_i, c_vp],
     "spv_fwht": [c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_i, c_f, c_i, c_vp],
     "spv_hadamard_path": [c_i, c_i, c_i, c_i],
     "spv_hadamard_workspace_floats": [c_i, c_i, c_i],

@@ -137,6 +137,41 @@ def _step_control_record(optimizer):
     return rec
 
 
+def _optimizer_choice(optimizer, momentum, nesterov):
+    """the harness's optimizer arguments -> (name, the rule's keywords).  None = "adamw" left unsaid: the same optimizer, and the epoch
+    record does not name it.  "adam" / "sgd" are the reference script's two other optimizer lines (train.py:197-198, :307):
+    spectre_vit.optim.FusedAdam / FusedSGD on every path (there is no torch.optim fallback for them); momentum / nesterov belong to
+    "sgd", whose defaults are the script's (momentum=0.9, nesterov=True).  Raises before any device is touched."""
+    if optimizer not in (None, "adamw", "adam", "sgd"):
+        raise ValueError(f"optimizer={optimizer!r}: 'adamw', 'adam' or 'sgd'")
+    if isinstance(momentum, bool) or not isinstance(momentum, (int, float)) or not 0.0 <= momentum < 1.0:
+        raise ValueError(f"momentum={momentum!r} must be a float in [0, 1)")
+    if not isinstance(nesterov, bool):
+        raise ValueError(f"nesterov={nesterov!r} must be True or False")
+    if optimizer != "sgd":
+        if momentum != 0.9 or nesterov is not True:
+            raise ValueError("momentum / nesterov belong to optimizer='sgd'")
+        return optimizer, {}
+    if nesterov and momentum == 0.0:
+        raise ValueError("nesterov=True needs momentum > 0 (torch.optim.SGD's rule): pass nesterov=False with momentum=0")
+    return optimizer, dict(momentum=float(momentum), nesterov=nesterov)
+
+
+def _make_optimizer(name, rule, params, c, lr, fused):
+    """the optimizer of a training loop.  fused: the keywords of the one-launch optimizer (capturable, static_grads, control, averaging)
+    or None where the default AdamW may stay torch's own (the reference's eager loop shape)"""
+    if name == "sgd":     # train.py:198
+        from spectre_vit.optim import FusedSGD
+        return FusedSGD(params, lr=lr, weight_decay=c.adam_weight_decay, **rule, **(fused or dict(capturable=True)))
+    if name == "adam":    # train.py:197, :307
+        from spectre_vit.optim import FusedAdam
+        return FusedAdam(params, betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, **(fused or dict(capturable=True)))
+    if fused is not None:
+        from spectre_vit.optim import FusedAdamW
+        return FusedAdamW(params, betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, **fused)
+    return optim.AdamW(params, betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay)  # train.py:199-201, :307-309
+
+
 def _ema_args(ema_decay, ema_warmup):
     """the harness's two averaging arguments -> FusedAdamW keywords; {} when averaging is off.  Raises before any device is touched."""
     if ema_decay is None:
@@ -236,7 +271,8 @@ def _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, uint8):
 def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
           use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
           augment=False, batch_hook=None, graph_eval=False, lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None,
-          skip_nonfinite=False, ema_decay=None, ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None):
+          skip_nonfinite=False, ema_decay=None, ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None,
+          optimizer=None, momentum=0.9, nesterov=True):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
@@ -265,6 +301,10 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     runs on the averaged weights (inside optimizer.ema_weights(); through the same session with graph_eval=True) and the record gains
     "Accuracy/ValidationEMA" and "Loss/ValidationEMA"; model_ema_best.pt holds optimizer.ema_state_dict(model) of the best such epoch.
     Every other entry of the record is what it is without averaging.
+    optimizer="adamw" | "adam" | "sgd" (with momentum, nesterov for "sgd"): the update rule -- the script's three optimizer lines,
+    train.py:197-201.  lr, the betas and weight_decay come from the config for each; "adam" is spectre_vit.optim.FusedAdam and "sgd"
+    FusedSGD(momentum=0.9, nesterov=True by default, the script's values) on every path, with all of the above unchanged in meaning.
+    Left unsaid it is "adamw" as ever; said, the epoch record gains "Optimizer".
     device_meter=True (not with distill): the training criterion carries a spectre_vit.meter.TrainMeter of one log row per step of the
     epoch, so its loss launch -- eager or replayed -- counts the batch's hits and logs the step on the device: the host issues no
     argmax / == / sum / accumulate per step, reads the meter ONCE per epoch and resets it.  "Loss/Train" and "Accuracy/Train" (rank
@@ -289,6 +329,7 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     if augment and (uint8_input or distill):
         raise ValueError("augment=True yields normalised float batches for the plain training step: not with uint8_input or distill")
     ema = _ema_args(ema_decay, ema_warmup)
+    optimizer_name, rule = _optimizer_choice(optimizer, momentum, nesterov)
     c = parse_config(config_path)
     seed = getattr(c, "random_seed", 42)
     lr = getattr(c, "learning_rate", 1e-3)
@@ -321,17 +362,11 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     if meter is not None:   # the training criterion logs every step it computes; validation must not
         criterion = CrossEntropyLoss(meter=meter)
     if graph:
-        from spectre_vit.optim import FusedAdamW
-        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
-                               static_grads=True, **control, **ema)
+        optimizer = _make_optimizer(optimizer_name, rule, model.parameters(), c, lr, dict(capturable=True, static_grads=True, **control, **ema))
         reducer = None   # the graphed step owns its own (fixed-address) gradient buffer
-    elif control or ema:
-        from spectre_vit.optim import FusedAdamW
-        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True, **control,
-                               **ema)
-        reducer = GradReducer(model)
     else:
-        optimizer = optim.AdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay)  # train.py:199-201
+        optimizer = _make_optimizer(optimizer_name, rule, model.parameters(), c, lr,
+                                    dict(capturable=True, **control, **ema) if control or ema else None)
         reducer = GradReducer(model)
     teacher = SyntheticTeacher(c.num_classes, 384, c.in_channels).to(device) if distill else None
     os.makedirs(out_dir, exist_ok=True)
@@ -458,6 +493,8 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
                "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
         if meter is not None:
             rec["Accuracy/TrainTop5"] = metered["accuracy_topk"]
+        if optimizer_name is not None:
+            rec["Optimizer"] = optimizer_name
         if control:
             rec.update(_step_control_record(optimizer))
         if ema:   # the same pass on the averaged weights (a session keeps its own copies: leaving the context does not disturb it)
@@ -511,8 +548,8 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                   use_amp=False, graph=False, augment=True, teacher=None, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75,
                   resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False,
                   lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False, ema_decay=None,
-                  ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None, cache_teacher=False,
-                  teacher_cache_path=None):
+                  ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None, optimizer=None, momentum=0.9,
+                  nesterov=True, cache_teacher=False, teacher_cache_path=None):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -524,7 +561,8 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     sample (train.py:365-383).  The three per-batch losses the reference logs (train.py:355-359) are kept on the device and written
     once per epoch as {"step", "Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE"} lines: no host synchronisation per step.
     batch_hook(kind, step, img, label), kind "train" / "teacher" / "val" (test seam).  graph_eval, lr_schedule, warmup_steps, eta_min,
-    clip_grad_norm, skip_nonfinite, ema_decay, ema_warmup, accumulate_steps: as in train().
+    clip_grad_norm, skip_nonfinite, ema_decay, ema_warmup, accumulate_steps, optimizer, momentum, nesterov: as in train() (the
+    distillation cell's own optimizer line is the Adam one, train.py:307).
     cache_teacher=True: the teacher's view has no random op and the teacher is frozen, so its logits are a function of the sample alone;
     they are computed once before epoch 0 into a resident spectre_vit.distillation.TeacherLogitCache (sharded over the ranks; loaded from
     teacher_cache_path when that file exists and matches, saved there by rank 0 otherwise), a {"TeacherCache": ...} line is logged, and
@@ -547,6 +585,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     _check_device_meter(device_meter)
     _check_device_loader(device_loader)
     ema = _ema_args(ema_decay, ema_warmup)
+    optimizer_name, rule = _optimizer_choice(optimizer, momentum, nesterov)
     c = parse_config(config_path)
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if teacher_cache_path is not None and not cache_teacher:
@@ -588,17 +627,11 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight, **({} if meter is None else {"meter": meter}))
     control = _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite, epoch_steps * epochs, accumulate_steps)
     if graph:
-        from spectre_vit.optim import FusedAdamW
-        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True,
-                               static_grads=True, **control, **ema)
+        optimizer = _make_optimizer(optimizer_name, rule, model.parameters(), c, lr, dict(capturable=True, static_grads=True, **control, **ema))
         reducer = None   # the graphed step owns its own (fixed-address) gradient buffer
-    elif control or ema:
-        from spectre_vit.optim import FusedAdamW
-        optimizer = FusedAdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay, capturable=True, **control,
-                               **ema)
-        reducer = GradReducer(model)
     else:
-        optimizer = optim.AdamW(model.parameters(), betas=c.adam_betas, lr=lr, weight_decay=c.adam_weight_decay)  # train.py:307-309
+        optimizer = _make_optimizer(optimizer_name, rule, model.parameters(), c, lr,
+                                    dict(capturable=True, **control, **ema) if control or ema else None)
         reducer = GradReducer(model)
     os.makedirs(out_dir, exist_ok=True)
     log_f = open(os.path.join(out_dir, "scalars.jsonl"), "a") if rank == 0 else None
@@ -736,6 +769,8 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
         if meter is not None:
             rec["Accuracy/TrainTop5"] = metered["accuracy_topk"]
+        if optimizer_name is not None:
+            rec["Optimizer"] = optimizer_name
         if control:
             rec.update(_step_control_record(optimizer))
         if ema:
@@ -797,6 +832,10 @@ def build_parser():
     ap.add_argument("--accumulate-steps", type=int, default=None, metavar="K",
                     help="accumulate the gradients of K steps on the device and apply the optimizer to their mean on every K-th; "
                          "--steps-per-epoch keeps counting micro-steps and the schedule runs over (epochs * steps) // K optimizer steps")
+    ap.add_argument("--optimizer", default=None, choices=("adamw", "adam", "sgd"),
+                    help="the update rule: the script's three optimizer lines (train.py:197-201); lr, betas and weight decay from the config")
+    ap.add_argument("--momentum", type=float, default=0.9, help="--optimizer sgd: the momentum (the script's 0.9)")
+    ap.add_argument("--no-nesterov", action="store_true", help="--optimizer sgd: plain momentum where the script's line has nesterov=True")
     ap.add_argument("--ema-decay", type=float, default=None,
                     help="keep an exponential moving average of the weights inside the optimizer launch, validate it after every epoch "
                          "and save model_ema_best.pt")
@@ -817,7 +856,8 @@ def build_parser():
 def main(argv=None):
     a = build_parser().parse_args(argv)
     control = dict(lr_schedule=a.lr_schedule, warmup_steps=a.warmup_steps, eta_min=a.eta_min, clip_grad_norm=a.clip_grad_norm,
-                   skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup, accumulate_steps=a.accumulate_steps)
+                   skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup, accumulate_steps=a.accumulate_steps,
+                   optimizer=a.optimizer, momentum=a.momentum, nesterov=not a.no_nesterov)
     if a.distill_paired:
         train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out,
                       graph_eval=a.graph_eval, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache,
