@@ -9,6 +9,9 @@ spectre_vit.augment) instead of PIL on loader workers, scalars to a JSON-lines f
 distillation path (the DINOv3 weights are unavailable offline).  ``train(distill=True)`` is the early form of that path (the teacher
 sees a 64 x 64 interpolation of the student's batch); ``train_distill`` / ``--distill-paired`` is the loop with the reference's two views
 per sample, the teacher's 224 view and the KD loss on HIP kernels, and the step replayed from a graph on request.
+Both entry points check their arguments, build what is their own (criterion, teacher / view / cache, step object) and call the shared
+_setup and _run_epochs (the one loop; _epoch_tail is its validation, record, log and checkpoints).  A step object owes the loop
+batches() -- what the host knows of each next batch -- run(batch, n) -> (loss, y_pred, img, label, *loss terms) and close().
 
     python -m spectre_vit.harness --config spectre_vit/configs/spectre_vit_cifar100.py --epochs 2 --steps-per-epoch 20
 """
@@ -19,6 +22,7 @@ import json
 import os
 import random
 import time
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -268,6 +272,256 @@ def _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, uint8):
                             input="uint8" if uint8 else "float")
 
 
+def _setup(c, mixer, model_name, epochs, steps_per_epoch, batch_size, n_train, n_val, out_dir, graph, device_meter, optimizer_name, rule,
+           ema, control_args):
+    """what every run has before its first batch, from a parsed config and the arguments train() and train_distill() share -> the run's
+    record: rank / world / device, seed, lr, the model (built under the seed, broadcast), the two sets, batch_size, epoch_steps (the
+    loader steps of one epoch), the step control / meter / optimizer / reducer, the open scalars.jsonl (rank 0), the shuffle generator,
+    and the loop's state (global_step, history, the two best accuracies, the lazy evaluation session, the start time)"""
+    rank = int(os.environ.get("RANK", "0"))
+    world = int(os.environ.get("WORLD_SIZE", "1"))
+    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
+    torch.cuda.set_device(local_rank)  # always: kernels launch on the current device's stream (also with a pre-initialised group)
+    if world > 1 and not dist.is_initialized():
+        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
+        dist.init_process_group("nccl")
+    device = torch.device("cuda", local_rank)
+    seed = getattr(c, "random_seed", 42)
+    lr = getattr(c, "learning_rate", 1e-3)
+    seed_everything(seed)
+    model = build_model(c, mixer, device, model_name)
+    broadcast_module(model)
+    batch_size = batch_size or c.batch_size
+    train_set = SyntheticCifar(n_train, c, device, seed=seed)
+    val_set = SyntheticCifar(n_val, c, device, seed=seed + 1)
+    per_pass = (n_train // world) // batch_size
+    epoch_steps = min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass
+    control = _step_control_args(total_steps=epoch_steps * epochs, **control_args)
+    meter = _train_meter(device_meter, epoch_steps, device)
+    optimizer, reducer = _optimizer_and_reducer(optimizer_name, rule, model, c, lr, graph, control, ema)
+    os.makedirs(out_dir, exist_ok=True)
+    log_f = open(os.path.join(out_dir, "scalars.jsonl"), "a") if rank == 0 else None
+    return SimpleNamespace(c=c, rank=rank, world=world, device=device, seed=seed, lr=lr, model=model, train_set=train_set, val_set=val_set,
+                           n_val=n_val, batch_size=batch_size, epoch_steps=epoch_steps, control=control, ema=ema, meter=meter,
+                           optimizer_name=optimizer_name, optimizer=optimizer, reducer=reducer, out_dir=out_dir, log_f=log_f,
+                           gen=torch.Generator().manual_seed(seed), global_step=0, history=[], best_acc=0.0, best_ema_acc=0.0,
+                           session=None, start=time.perf_counter())
+
+
+def _optimizer_and_reducer(name, rule, model, c, lr, graph, control, ema):
+    """graph: the one-launch optimizer on fixed-address gradients and no reducer (the graphed step owns its gradient buffer); eager: the
+    reference's loop shape -- torch's own AdamW unless step control, averaging or the named rule ask for a fused one -- and GradReducer"""
+    if graph:
+        return _make_optimizer(name, rule, model.parameters(), c, lr, dict(capturable=True, static_grads=True, **control, **ema)), None
+    fused = dict(capturable=True, **control, **ema) if control or ema else None
+    return _make_optimizer(name, rule, model.parameters(), c, lr, fused), GradReducer(model)
+
+
+def _resident_loader(run, train_nhwc, aug, uint8_input):
+    """the run's spectre_vit.data.ResidentLoader: its output picked by shape (_loader_output), this loop's steps per epoch, this rank's
+    shard.  With a fused output the loader fetches and augments in ONE call (the table is keyed by the loader's cursor, which equals
+    global_step); with "none" it fetches index and labels only, draw and apply host-issued as without the loader"""
+    from spectre_vit.data import ResidentLoader
+    H, W, C = train_nhwc.shape[1:]
+    output = _loader_output(aug is not None, uint8_input, C, H, W)
+    return ResidentLoader(train_nhwc, run.train_set.labels, run.batch_size, CIFAR_MEAN[:C], CIFAR_STD[:C], seed=loader_seed(run.seed),
+                          rank=run.rank, world=run.world, steps_per_epoch=run.epoch_steps, output=output,
+                          augment=aug if output.startswith("augment") else None)
+
+
+def _eager_update(run, loss):
+    run.reducer.zero_grad()
+    loss.backward()
+    run.reducer.finish()
+    run.optimizer.step()
+
+
+def _step(batches, run_step, gstep):
+    """a step object: batches() yields what the host knows of the next batch, run(batch, n) trains on it, close() closes the graphed
+    step where one was built (gstep: a one-element list, filled on the first batch)"""
+    return SimpleNamespace(batches=batches, run=run_step, close=lambda: gstep[0] is not None and gstep[0].close())
+
+
+class _TrainBooks:
+    """an epoch's training loss and accuracy, kept where the run keeps them: in the criterion's meter, read once; or, without a meter,
+    accumulated on the device -- the loss as a running sum whose mean is taken on the device (train()), or, block=True, as one row of
+    `names` per step read once, the mean taken on the host (train_distill(), which logs every step).  The two means differ in bits."""
+
+    def __init__(self, run, names, block):
+        self.run, self.names, self.block = run, names, block
+
+    def begin(self):
+        if self.run.meter is not None:
+            return
+        device = self.run.device
+        self.correct, self.total = torch.zeros((), device=device, dtype=torch.int64), 0
+        self.loss = torch.zeros((max(self.run.epoch_steps, 1), len(self.names)), device=device) if self.block else torch.zeros((), device=device)
+
+    def add(self, k, y_pred, label, loss, *terms):
+        if self.run.meter is not None:
+            return
+        self.correct += (label == torch.argmax(y_pred, dim=1)).sum()
+        self.total += label.size(0)
+        if self.block:
+            torch.stack((loss.detach(), *terms), out=self.loss[k])
+        else:
+            self.loss += loss.detach()  # accumulated on device: no host sync per step (train.py:243 syncs every step)
+
+    def read(self, steps):
+        """the epoch's one read -> (Loss/Train, Accuracy/Train, Accuracy/TrainTop5 or None, the per-step log lines' entries)"""
+        meter = self.run.meter
+        if meter is not None:
+            metered = meter.read()
+            meter.reset()
+            return metered["loss_mean"], metered["accuracy"], metered["accuracy_topk"], [dict(zip(self.names, row)) for row in metered["rows"]]
+        rows = self.loss[:steps].tolist() if self.block else []
+        train_loss = sum(r[0] for r in rows) / max(steps, 1) if self.block else (self.loss / max(steps, 1)).item()
+        return train_loss, self.correct.item() / max(self.total, 1), None, [dict(zip(self.names, row)) for row in rows]
+
+
+def _validator(run, graph_eval, amp, uint8=False, float_logits=False):
+    """-> validate(hook): one pass over the validation set, every sample of the rank's shard -> (accuracy, loss, samples).  graph_eval:
+    through an InferenceSession built on first use and kept in the run's record; otherwise eagerly with a meter-less criterion"""
+    criterion = CrossEntropyLoss()
+    val_batch = min(getattr(run.c, "val_batch_size", run.batch_size), run.n_val)
+
+    def validate(hook):
+        batches = run.val_set.batches(val_batch, False, None, run.rank, run.world, raw_uint8=uint8, drop_last=False)
+        if not graph_eval:
+            return _eager_validate(run.model, batches, criterion, amp, hook, run.world, run.device, float_logits)
+        if run.session is None:
+            run.session = _eval_session(run.model, run.n_val, val_batch, run.rank, run.world, torch.bfloat16 if amp else None, uint8)
+        return _graph_validate(run.session, batches, hook, run.world)
+    return validate
+
+
+def _epoch_tail(run, epoch, steps, first_step, train, validate, batch_hook, log):
+    """after an epoch's training: validation, the epoch record (with the averaged weights' second pass), rank 0's log lines -- the
+    per-step ones, then the record -- and the two best checkpoints.  train: what _TrainBooks.read returned"""
+    train_loss, train_acc, top5, lines = train
+    val_acc, val_loss, val_samples = validate(batch_hook)
+    rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
+           "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
+    if top5 is not None:
+        rec["Accuracy/TrainTop5"] = top5
+    if run.optimizer_name is not None:
+        rec["Optimizer"] = run.optimizer_name
+    if run.control:
+        rec.update(_step_control_record(run.optimizer))
+    if run.ema:   # the same pass on the averaged weights (a session keeps its own copies: leaving the context does not disturb it)
+        with run.optimizer.ema_weights():
+            rec["Accuracy/ValidationEMA"], rec["Loss/ValidationEMA"], _ = validate(None)
+    run.history.append(rec)
+    if run.rank != 0:
+        return
+    for k, line in enumerate(lines):
+        run.log_f.write(json.dumps({"step": first_step + k, **line}) + "\n")
+    run.log_f.write(json.dumps(rec) + "\n")
+    run.log_f.flush()
+    log(rec)
+    if val_acc > run.best_acc or epoch == 0:  # train.py:288-290; the reference's distillation cell keeps no checkpoint
+        run.best_acc = max(run.best_acc, val_acc)
+        torch.save(run.model.state_dict(), os.path.join(run.out_dir, "model_best.pt"))
+    if run.ema and (rec["Accuracy/ValidationEMA"] > run.best_ema_acc or epoch == 0):
+        run.best_ema_acc = max(run.best_ema_acc, rec["Accuracy/ValidationEMA"])
+        torch.save(run.optimizer.ema_state_dict(run.model), os.path.join(run.out_dir, "model_ema_best.pt"))
+
+
+def _run_epochs(run, step, books, validate, epochs, batch_hook, hook_after, log):
+    """THE training loop.  Per step: the next batch from step.batches(); batch_hook("train", ...) in front of the step when the host
+    knows the batch beforehand, or (hook_after: a resident loader feeds the step) after it with the buffers the step trained on;
+    global_step counted between the two; step.run(batch, n) -> (loss, y_pred, img, label, *further loss terms); the books.  Per epoch
+    _epoch_tail; at the end the step and the session are closed and the "Training time" line is written.  -> (model, history)"""
+    for epoch in range(epochs):
+        run.model.train()
+        books.begin()
+        first_step, steps = run.global_step, 0
+        for batch in step.batches():
+            n = run.global_step
+            if batch_hook is not None and not hook_after:
+                batch_hook("train", n, batch[0], batch[1])
+            run.global_step += 1
+            loss, y_pred, img, label, *terms = step.run(batch, n)
+            books.add(steps, y_pred, label, loss, *terms)
+            if batch_hook is not None and hook_after:
+                batch_hook("train", n, img, label)
+            steps += 1
+            if steps >= run.epoch_steps:
+                break
+        train = books.read(steps)
+        run.model.eval()
+        _epoch_tail(run, epoch, steps, first_step, train, validate, batch_hook, log)
+    step.close()
+    if run.session is not None:
+        run.session.close()
+    if run.rank == 0:
+        run.log_f.write(json.dumps({"Training time": time.perf_counter() - run.start}) + "\n")
+        run.log_f.close()
+    return run.model, run.history
+
+
+def _plain_step(run, criterion, use_amp, graph, uint8_input, aug, loader, train_nhwc):
+    """train()'s step: forward, criterion, backward, optimizer -- eager, or replayed by GraphedTrainStep / GraphedDPStep (built on the
+    first batch, whose training step its warm-up is), with the loader's fetch as the graph's first node where the loader yields images"""
+    host_aug = aug if loader is None or loader.output == "none" else None   # the transform the host still issues per batch
+    loader_in_graph = loader is not None and graph and loader.img is not None   # the step fetches its own batch
+    gstep = [None]
+
+    def batches():
+        if loader is not None:
+            for _ in range(loader.steps_per_epoch):
+                if loader_in_graph:
+                    yield None, None
+                    continue
+                loader.fetch()
+                yield loader.img if host_aug is None else host_aug(train_nhwc, loader.index, step=run.global_step), loader.labels
+            return
+        if aug is None:
+            yield from run.train_set.batches(run.batch_size, True, run.gen, run.rank, run.world, raw_uint8=uint8_input)
+            return
+        for sel in run.train_set.index_batches(run.batch_size, True, run.gen, run.rank, run.world):
+            yield aug(train_nhwc, sel, step=run.global_step), run.train_set.labels[sel]
+
+    def run_step(batch, n):
+        img, label = batch
+        if not graph:
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
+                y_pred = run.model(img)
+            loss = criterion(y_pred, label.long())
+            _eager_update(run, loss)
+            return loss, y_pred, img, label
+        if gstep[0] is None:   # built on the first batch (its shape is the captured one); warm-up steps are real training steps
+            from spectre_vit.graph import GraphedDPStep, GraphedTrainStep
+            cls = GraphedDPStep if run.world > 1 else GraphedTrainStep
+            fed = dict(loader=loader) if loader_in_graph else {}
+            gstep[0] = cls(run.model, run.optimizer, criterion, img, None if loader_in_graph else label.long(),
+                           autocast_dtype=torch.bfloat16 if use_amp else None, warmup=1, **fed)
+            loss, y_pred = gstep[0].warm_loss, gstep[0].warm_out   # the warm-up step WAS this batch's training step
+        else:
+            loss = gstep[0]() if loader_in_graph else gstep[0](img, label.long())   # loader_in_graph: ONE replay, fetch to optimizer
+            y_pred = gstep[0].out
+        if loader_in_graph:
+            img, label = loader.img, loader.labels   # what the step just trained on
+        return loss, y_pred, img, label
+    return _step(batches, run_step, gstep)
+
+
+def _early_distill_step(run, teacher):
+    """train(distill=True)'s step: the teacher sees a 64 x 64 interpolation of the student's batch; eager, fp32 (train.py:299)"""
+    def batches():
+        return run.train_set.batches(run.batch_size, True, run.gen, run.rank, run.world)
+
+    def run_step(batch, n):
+        img, label = batch
+        student_logits, _ = run.model(img, return_features=True)
+        with torch.no_grad():
+            teacher_logits, _ = teacher(nn.functional.interpolate(img, size=64, mode="bicubic"), return_features=True)
+        loss, _, _ = distillation_loss(student_logits, teacher_logits, label.long())
+        _eager_update(run, loss)
+        return loss, student_logits, img, label
+    return _step(batches, run_step, [None])
+
+
 def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
           use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
           augment=False, batch_hook=None, graph_eval=False, lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None,
@@ -331,197 +585,30 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     ema = _ema_args(ema_decay, ema_warmup)
     optimizer_name, rule = _optimizer_choice(optimizer, momentum, nesterov)
     c = parse_config(config_path)
-    seed = getattr(c, "random_seed", 42)
-    lr = getattr(c, "learning_rate", 1e-3)
-    rank = int(os.environ.get("RANK", "0"))
-    world = int(os.environ.get("WORLD_SIZE", "1"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    torch.cuda.set_device(local_rank)  # always: kernels launch on the current device's stream (also with a pre-initialised group)
-    if world > 1 and not dist.is_initialized():
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("nccl")
-    device = torch.device("cuda", local_rank)
-    seed_everything(seed)
-    model_name = model
-    if model_name == "spectre_branch" and uint8_input:
+    if model == "spectre_branch" and uint8_input:
         raise ValueError("the SpectreBranch spectrum takes fp32 images: the uint8 NHWC input path is not built for it")
-    model = build_model(c, mixer, device, model_name)
-    broadcast_module(model)
-    batch_size = batch_size or c.batch_size
-    train_set = SyntheticCifar(n_train, c, device, seed=seed)
-    val_set = SyntheticCifar(n_val, c, device, seed=seed + 1)
-    criterion = CrossEntropyLoss()  # nn.CrossEntropyLoss() of train.py:196 on the HIP path (spectre_vit/loss.py)
-    val_criterion = criterion
     if graph and distill:
         raise ValueError("graph=True replays the plain training step; the distillation step (teacher forward + KD loss) runs eagerly")
-    gstep = session = None
-    per_pass = (n_train // world) // batch_size
-    control = _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite,
-                                 (min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass) * epochs, accumulate_steps)
-    meter = _train_meter(device_meter, min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass, device)
-    if meter is not None:   # the training criterion logs every step it computes; validation must not
-        criterion = CrossEntropyLoss(meter=meter)
-    if graph:
-        optimizer = _make_optimizer(optimizer_name, rule, model.parameters(), c, lr, dict(capturable=True, static_grads=True, **control, **ema))
-        reducer = None   # the graphed step owns its own (fixed-address) gradient buffer
+    run = _setup(c, mixer, model, epochs, steps_per_epoch, batch_size, n_train, n_val, out_dir, graph, device_meter, optimizer_name, rule,
+                 ema, dict(lr_schedule=lr_schedule, warmup_steps=warmup_steps, eta_min=eta_min, clip_grad_norm=clip_grad_norm,
+                           skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps))
+    amp = use_amp and not distill          # distill: use_amp False, train.py:299
+    uint8 = uint8_input and not distill
+    if distill:
+        step = _early_distill_step(run, SyntheticTeacher(c.num_classes, 384, c.in_channels).to(run.device))
     else:
-        optimizer = _make_optimizer(optimizer_name, rule, model.parameters(), c, lr,
-                                    dict(capturable=True, **control, **ema) if control or ema else None)
-        reducer = GradReducer(model)
-    teacher = SyntheticTeacher(c.num_classes, 384, c.in_channels).to(device) if distill else None
-    os.makedirs(out_dir, exist_ok=True)
-    log_f = open(os.path.join(out_dir, "scalars.jsonl"), "a") if rank == 0 else None
-    gen = torch.Generator().manual_seed(seed)
-    best_acc, best_ema_acc, history = 0.0, 0.0, []
-    global_step = 0
-    aug = train_nhwc = loader = None
-    if augment or device_loader:
-        train_nhwc = train_set.images.permute(0, 2, 3, 1).contiguous()
-    if augment:
-        aug = TrainAugment(CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels], seed=augment_seed(seed, rank))
-    if device_loader:
-        from spectre_vit.data import ResidentLoader
-        # augment: fetch and augment in ONE call where a fused kernel takes the image (the table is then keyed by the loader's cursor,
-        # which equals global_step); otherwise index and labels only, draw and apply host-issued as without the loader
-        H, W, C = train_nhwc.shape[1:]
-        output = _loader_output(augment, uint8_input, C, H, W)
-        loader = ResidentLoader(train_nhwc, train_set.labels, batch_size, CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels],
-                                seed=loader_seed(seed), rank=rank, world=world, steps_per_epoch=min(per_pass, steps_per_epoch or per_pass),
-                                output=output, augment=aug if output.startswith("augment") else None)
-    host_aug = aug if loader is None or loader.output == "none" else None   # the transform the host still issues per batch
-    loader_in_graph = loader is not None and graph and loader.img is not None   # the step fetches its own batch
-
-    def train_batches():
-        if loader is not None:
-            for _ in range(loader.steps_per_epoch):
-                if loader_in_graph:
-                    yield None, None
-                    continue
-                loader.fetch()
-                yield loader.img if host_aug is None else host_aug(train_nhwc, loader.index, step=global_step), loader.labels
-            return
-        if aug is None:
-            yield from train_set.batches(batch_size, True, gen, rank, world, raw_uint8=uint8_input and not distill)
-            return
-        for sel in train_set.index_batches(batch_size, True, gen, rank, world):
-            yield aug(train_nhwc, sel, step=global_step), train_set.labels[sel]
-
-    start = time.perf_counter()
-    for epoch in range(epochs):
-        model.train()
-        running = torch.zeros((), device=device)
-        correct = torch.zeros((), device=device, dtype=torch.int64)
-        total, steps = 0, 0
-        first_step = global_step
-        for img, label in train_batches():
-            if batch_hook is not None and loader is None:
-                batch_hook("train", global_step, img, label)
-            global_step += 1
-            if graph:
-                if gstep is None:   # built on the first batch (its shape is the captured one); warm-up steps are real training steps
-                    from spectre_vit.graph import GraphedDPStep, GraphedTrainStep
-                    cls = GraphedDPStep if world > 1 else GraphedTrainStep
-                    fed = dict(loader=loader) if loader_in_graph else {}
-                    gstep = cls(model, optimizer, criterion, img, None if loader_in_graph else label.long(),
-                                autocast_dtype=torch.bfloat16 if use_amp else None, warmup=1, **fed)
-                    loss, y_pred = gstep.warm_loss, gstep.warm_out   # the warm-up step WAS this batch's training step
-                elif loader_in_graph:
-                    loss = gstep()   # ONE replay: fetch, forward, loss, backward, optimizer
-                    y_pred = gstep.out
-                else:
-                    loss = gstep(img, label.long())
-                    y_pred = gstep.out
-                if loader_in_graph:
-                    img, label = loader.img, loader.labels   # what the step just trained on
-                if meter is None:
-                    correct += (label == torch.argmax(y_pred, dim=1)).sum()
-                    total += label.size(0)
-                    running += loss.detach()
-                if batch_hook is not None and loader is not None:
-                    batch_hook("train", global_step - 1, img, label)
-                steps += 1
-                if steps_per_epoch and steps >= steps_per_epoch:
-                    break
-                continue
-            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp and not distill):  # distill: use_amp False, train.py:299
-                if distill:
-                    student_logits, _ = model(img, return_features=True)
-                    with torch.no_grad():
-                        teacher_logits, _ = teacher(nn.functional.interpolate(img, size=64, mode="bicubic"), return_features=True)
-                    loss, _, _ = distillation_loss(student_logits, teacher_logits, label.long())
-                    y_pred = student_logits
-                else:
-                    y_pred = model(img)
-            if meter is None:
-                correct += (label == torch.argmax(y_pred, dim=1)).sum()
-                total += label.size(0)
-            if not distill:
-                loss = criterion(y_pred, label.long())
-            reducer.zero_grad()
-            loss.backward()
-            reducer.finish()
-            optimizer.step()
-            if meter is None:
-                running += loss.detach()  # accumulated on device: no host sync per step (train.py:243 syncs every step)
-            if batch_hook is not None and loader is not None:
-                batch_hook("train", global_step - 1, img, label)
-            steps += 1
-            if steps_per_epoch and steps >= steps_per_epoch:
-                break
-        if meter is None:
-            train_loss = (running / max(steps, 1)).item()
-            train_acc = correct.item() / max(total, 1)
-        else:
-            metered = meter.read()   # the epoch's one read of the training scalars
-            meter.reset()
-            train_loss, train_acc = metered["loss_mean"], metered["accuracy"]
-
-        model.eval()
-        val_batch = min(getattr(c, "val_batch_size", batch_size), n_val)
-        val_uint8 = uint8_input and not distill
-
-        def validate(hook):
-            batches = val_set.batches(val_batch, False, None, rank, world, raw_uint8=val_uint8, drop_last=False)
-            if graph_eval:
-                return _graph_validate(session, batches, hook, world)
-            return _eager_validate(model, batches, val_criterion, use_amp and not distill, hook, world, device)
-
-        if graph_eval and session is None:
-            session = _eval_session(model, n_val, val_batch, rank, world, torch.bfloat16 if use_amp and not distill else None, val_uint8)
-        val_acc, val_loss, val_samples = validate(batch_hook)
-        rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
-               "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
-        if meter is not None:
-            rec["Accuracy/TrainTop5"] = metered["accuracy_topk"]
-        if optimizer_name is not None:
-            rec["Optimizer"] = optimizer_name
-        if control:
-            rec.update(_step_control_record(optimizer))
-        if ema:   # the same pass on the averaged weights (a session keeps its own copies: leaving the context does not disturb it)
-            with optimizer.ema_weights():
-                rec["Accuracy/ValidationEMA"], rec["Loss/ValidationEMA"], _ = validate(None)
-        history.append(rec)
-        if rank == 0:
-            if meter is not None:
-                for k, row in enumerate(metered["rows"]):
-                    log_f.write(json.dumps({"step": first_step + k, "Batch Loss/Train": row[0]}) + "\n")
-            log_f.write(json.dumps(rec) + "\n")
-            log_f.flush()
-            log(rec)
-            if val_acc > best_acc or epoch == 0:  # train.py:288-290
-                best_acc = max(best_acc, val_acc)
-                torch.save(model.state_dict(), os.path.join(out_dir, "model_best.pt"))
-            if ema and (rec["Accuracy/ValidationEMA"] > best_ema_acc or epoch == 0):
-                best_ema_acc = max(best_ema_acc, rec["Accuracy/ValidationEMA"])
-                torch.save(optimizer.ema_state_dict(model), os.path.join(out_dir, "model_ema_best.pt"))
-    if gstep is not None:
-        gstep.close()
-    if session is not None:
-        session.close()
-    if rank == 0:
-        log_f.write(json.dumps({"Training time": time.perf_counter() - start}) + "\n")
-        log_f.close()
-    return model, history
+        # nn.CrossEntropyLoss() of train.py:196 on the HIP path (spectre_vit/loss.py); with a meter it logs every step it computes
+        criterion = CrossEntropyLoss(**({} if run.meter is None else {"meter": run.meter}))
+        aug = train_nhwc = loader = None
+        if augment or device_loader:
+            train_nhwc = run.train_set.images.permute(0, 2, 3, 1).contiguous()
+        if augment:
+            aug = TrainAugment(CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels], seed=augment_seed(run.seed, run.rank))
+        if device_loader:
+            loader = _resident_loader(run, train_nhwc, aug, uint8)
+        step = _plain_step(run, criterion, amp, graph, uint8, aug, loader, train_nhwc)
+    return _run_epochs(run, step, _TrainBooks(run, ("Batch Loss/Train",), block=False), _validator(run, graph_eval, amp, uint8), epochs,
+                       batch_hook, device_loader, log)
 
 
 def _teacher_cache(teacher, view, train_nhwc, classes, device, path, resize, crop, rank, world, batch_hook, batch_size):
@@ -542,6 +629,87 @@ def _teacher_cache(teacher, view, train_nhwc, classes, device, path, resize, cro
     if path is not None and not loaded and rank == 0:
         cache.save(path, resize=int(resize), crop=int(crop), tag=tag)
     return cache, {"rows": n, "teacher_batches": calls, "seconds": 0.0, "loaded": loaded}
+
+
+def _paired_distill_step(run, criterion, use_amp, graph, aug, view, teacher, cache, loader, train_nhwc, batch_hook):
+    """train_distill()'s step: ONE index seen twice -- the student's view and, uncached, the teacher's view and forward (the "teacher"
+    hook in front of it) -- then the fused DistillationLoss, eager or replayed by GraphedDistillStep (built on the first batch, whose
+    training step its warm-up is).  -> (loss, y_pred, img, label, soft, ce)"""
+    loader_step = loader is not None and graph and loader.img is not None       # the graphed step reads the loader's buffers
+    loader_in_graph = loader_step and cache is not None                         # ... and fetches them itself: a step is one replay
+    autocast_dtype = torch.bfloat16 if use_amp else None
+    train_set = run.train_set
+    gstep = [None]
+
+    def index_batches():
+        if loader is None:
+            yield from train_set.index_batches(run.batch_size, True, run.gen, run.rank, run.world)
+            return
+        for _ in range(loader.steps_per_epoch):
+            if loader_in_graph:
+                yield None
+                continue
+            loader.fetch()
+            yield loader.index
+
+    def batches():
+        for sel in index_batches():
+            if loader_in_graph:
+                img = label = None   # the replay fetches them
+            elif loader is not None:
+                label = loader.labels
+                img = loader.img if loader.img is not None else aug(train_nhwc, sel, step=run.global_step)
+            else:
+                label = train_set.labels[sel]
+                if aug is not None:
+                    img = aug(train_nhwc, sel, step=run.global_step)
+                else:
+                    img = (train_set.images[sel].float() / 255.0 - train_set.mean) / train_set.std
+            yield img, label, sel, view(train_nhwc, sel) if cache is None else None
+
+    def run_step(batch, n):
+        img, label, sel, img_teacher = batch
+        if cache is None:
+            if batch_hook is not None:
+                batch_hook("teacher", n, img_teacher, label)
+            with torch.no_grad():   # train.py:326-327
+                teacher_logits, _ = teacher(img_teacher, return_features=True)
+            teacher_logits = teacher_logits.float()
+        if not graph:
+            with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
+                y_pred = run.model(img)
+            if cache is None:
+                loss = criterion(y_pred.float(), teacher_logits, label.long())
+            else:
+                loss = criterion(y_pred.float(), cache, label.long(), index=sel)
+            soft, ce = criterion.soft, criterion.ce
+            _eager_update(run, loss)
+            return loss, y_pred, img, label, soft, ce
+        if gstep[0] is None:   # built on the first batch; its warm-up step WAS this batch's training step
+            from spectre_vit.graph import GraphedDistillStep
+            if loader_step:   # the batch (and, cached, its index) are the loader's buffers
+                teacher_args = dict(example_teacher_logits=teacher_logits) if cache is None else dict(teacher_cache=cache)
+                g = GraphedDistillStep(run.model, run.optimizer, criterion, None, None, autocast_dtype=autocast_dtype, warmup=1,
+                                       loader=loader, **teacher_args)
+            else:
+                teacher_args = dict(example_teacher_logits=teacher_logits) if cache is None else dict(teacher_cache=cache, example_index=sel)
+                g = GraphedDistillStep(run.model, run.optimizer, criterion, img, label.long(), autocast_dtype=autocast_dtype, warmup=1,
+                                       **teacher_args)
+            gstep[0] = g
+            loss, soft, ce, y_pred = g.warm_loss, g.warm_soft, g.warm_ce, g.warm_out
+        else:
+            g = gstep[0]
+            if loader_in_graph:
+                loss = g()   # ONE replay: fetch, forward, cached loss, backward, optimizer
+            elif loader_step:
+                loss = g(teacher_logits=teacher_logits)
+            else:
+                loss = g(img, label.long(), teacher_logits) if cache is None else g(img, label.long(), index=sel)
+            soft, ce, y_pred = g.soft, g.ce, g.out
+        if loader_in_graph:
+            img, label = loader.img, loader.labels   # what the step just trained on
+        return loss, y_pred, img, label, soft, ce
+    return _step(batches, run_step, gstep)
 
 
 def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
@@ -587,216 +755,39 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     ema = _ema_args(ema_decay, ema_warmup)
     optimizer_name, rule = _optimizer_choice(optimizer, momentum, nesterov)
     c = parse_config(config_path)
-    world = int(os.environ.get("WORLD_SIZE", "1"))
     if teacher_cache_path is not None and not cache_teacher:
         raise ValueError("teacher_cache_path names the file of the cached teacher's logits: it needs cache_teacher=True")
-    if graph and world > 1:
+    if graph and int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise ValueError("graph=True replays the single-process distillation step (GraphedDistillStep); a data-parallel rank runs it eagerly")
     if not _native.call("spv_teacher_view_supported", int(c.in_channels), int(c.img_size), int(resize), int(crop)):
         raise ValueError(f"the teacher view kernel does not take {c.in_channels} x {c.img_size} x {c.img_size} images at resize={resize}, "
                          f"crop={crop} (1 or 3 channels, img_size <= resize, 0 < crop <= resize, four taps inside the image)")
     if not (T > 0):
         raise ValueError(f"temperature T={T} must be positive")
-    seed = getattr(c, "random_seed", 42)
-    lr = getattr(c, "learning_rate", 1e-3)
-    rank = int(os.environ.get("RANK", "0"))
-    local_rank = int(os.environ.get("LOCAL_RANK", "0"))
-    torch.cuda.set_device(local_rank)
-    if world > 1 and not dist.is_initialized():
-        os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
-        dist.init_process_group("nccl")
-    device = torch.device("cuda", local_rank)
-    seed_everything(seed)
-    model = build_model(c, mixer, device)
-    broadcast_module(model)
-    batch_size = batch_size or c.batch_size
-    train_set = SyntheticCifar(n_train, c, device, seed=seed)
-    val_set = SyntheticCifar(n_val, c, device, seed=seed + 1)
-    train_nhwc = train_set.images.permute(0, 2, 3, 1).contiguous()
+    run = _setup(c, mixer, "spectre", epochs, steps_per_epoch, batch_size, n_train, n_val, out_dir, graph, device_meter, optimizer_name, rule,
+                 ema, dict(lr_schedule=lr_schedule, warmup_steps=warmup_steps, eta_min=eta_min, clip_grad_norm=clip_grad_norm,
+                           skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps))
+    train_nhwc = run.train_set.images.permute(0, 2, 3, 1).contiguous()
     mean, std = CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels]
-    aug = TrainAugment(mean, std, seed=augment_seed(seed, rank)) if augment else None
+    aug = TrainAugment(mean, std, seed=augment_seed(run.seed, run.rank)) if augment else None
     view = TeacherView(mean, std, resize=resize, crop=crop)
     if teacher is None:
-        teacher = SyntheticTeacher(c.num_classes, 384, c.in_channels).to(device)
+        teacher = SyntheticTeacher(c.num_classes, 384, c.in_channels).to(run.device)
     teacher.eval()
-    val_criterion = CrossEntropyLoss()
-    gstep = session = None
-    per_pass = (n_train // world) // batch_size
-    epoch_steps = min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass
-    meter = _train_meter(device_meter, epoch_steps, device)
-    criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight, **({} if meter is None else {"meter": meter}))
-    control = _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite, epoch_steps * epochs, accumulate_steps)
-    if graph:
-        optimizer = _make_optimizer(optimizer_name, rule, model.parameters(), c, lr, dict(capturable=True, static_grads=True, **control, **ema))
-        reducer = None   # the graphed step owns its own (fixed-address) gradient buffer
-    else:
-        optimizer = _make_optimizer(optimizer_name, rule, model.parameters(), c, lr,
-                                    dict(capturable=True, **control, **ema) if control or ema else None)
-        reducer = GradReducer(model)
-    os.makedirs(out_dir, exist_ok=True)
-    log_f = open(os.path.join(out_dir, "scalars.jsonl"), "a") if rank == 0 else None
-    gen = torch.Generator().manual_seed(seed)
-    best_acc, best_ema_acc, history = 0.0, 0.0, []
-    global_step = 0
-    autocast_dtype = torch.bfloat16 if use_amp else None
-    start = time.perf_counter()
+    criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight, **({} if run.meter is None else {"meter": run.meter}))
     cache = None
     if cache_teacher:
         # filled in blocks of the training batch: the teacher then sees the batch shape it would see inside the epochs
-        cache, cache_rec = _teacher_cache(teacher, view, train_nhwc, c.num_classes, device, teacher_cache_path, resize, crop, rank, world,
-                                          batch_hook, batch_size)
-        cache_rec["seconds"] = time.perf_counter() - start
-        if rank == 0:
-            log_f.write(json.dumps({"TeacherCache": cache_rec}) + "\n")
-            log_f.flush()
-    loader = None
-    if device_loader:
-        from spectre_vit.data import ResidentLoader
-        H, W, C = train_nhwc.shape[1:]
-        output = _loader_output(augment, False, C, H, W)
-        loader = ResidentLoader(train_nhwc, train_set.labels, batch_size, mean, std, seed=loader_seed(seed), rank=rank, world=world,
-                                steps_per_epoch=epoch_steps, output=output, augment=aug if output.startswith("augment") else None)
-    loader_step = loader is not None and graph and loader.img is not None       # the graphed step reads the loader's buffers
-    loader_in_graph = loader_step and cache is not None                         # ... and fetches them itself: a step is one replay
-
-    def index_batches():
-        if loader is None:
-            yield from train_set.index_batches(batch_size, True, gen, rank, world)
-            return
-        for _ in range(loader.steps_per_epoch):
-            if loader_in_graph:
-                yield None
-                continue
-            loader.fetch()
-            yield loader.index
-
-    for epoch in range(epochs):
-        model.train()
-        correct = torch.zeros((), device=device, dtype=torch.int64)
-        batch_losses = torch.zeros((max(epoch_steps, 1), 3), device=device)   # (Train, Dist, CE) per step, read once per epoch
-        first_step = global_step
-        total, steps = 0, 0
-        for sel in index_batches():
-            if loader_in_graph:
-                img = label = None   # the replay fetches them
-            elif loader is not None:
-                label = loader.labels
-                img = loader.img if loader.img is not None else aug(train_nhwc, sel, step=global_step)
-            else:
-                label = train_set.labels[sel]
-                if aug is not None:
-                    img = aug(train_nhwc, sel, step=global_step)
-                else:
-                    img = (train_set.images[sel].float() / 255.0 - train_set.mean) / train_set.std
-            if cache is None:
-                img_teacher = view(train_nhwc, sel)
-            if batch_hook is not None:
-                if loader is None:
-                    batch_hook("train", global_step, img, label)
-                if cache is None:
-                    batch_hook("teacher", global_step, img_teacher, label)
-            global_step += 1
-            if cache is None:
-                with torch.no_grad():   # train.py:326-327
-                    teacher_logits, _ = teacher(img_teacher, return_features=True)
-                teacher_logits = teacher_logits.float()
-            if graph:
-                if gstep is None:   # built on the first batch; its warm-up step WAS this batch's training step
-                    from spectre_vit.graph import GraphedDistillStep
-                    if loader_step:   # the batch (and, cached, its index) are the loader's buffers
-                        teacher_args = dict(example_teacher_logits=teacher_logits) if cache is None else dict(teacher_cache=cache)
-                        gstep = GraphedDistillStep(model, optimizer, criterion, None, None, autocast_dtype=autocast_dtype, warmup=1,
-                                                   loader=loader, **teacher_args)
-                    else:
-                        teacher_args = dict(example_teacher_logits=teacher_logits) if cache is None else dict(teacher_cache=cache, example_index=sel)
-                        gstep = GraphedDistillStep(model, optimizer, criterion, img, label.long(), autocast_dtype=autocast_dtype, warmup=1,
-                                                   **teacher_args)
-                    loss, soft, ce, y_pred = gstep.warm_loss, gstep.warm_soft, gstep.warm_ce, gstep.warm_out
-                else:
-                    if loader_in_graph:
-                        loss = gstep()   # ONE replay: fetch, forward, cached loss, backward, optimizer
-                    elif loader_step:
-                        loss = gstep(teacher_logits=teacher_logits)
-                    else:
-                        loss = gstep(img, label.long(), teacher_logits) if cache is None else gstep(img, label.long(), index=sel)
-                    soft, ce, y_pred = gstep.soft, gstep.ce, gstep.out
-                if loader_in_graph:
-                    img, label = loader.img, loader.labels   # what the step just trained on
-            else:
-                with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
-                    y_pred = model(img)
-                if cache is None:
-                    loss = criterion(y_pred.float(), teacher_logits, label.long())
-                else:
-                    loss = criterion(y_pred.float(), cache, label.long(), index=sel)
-                soft, ce = criterion.soft, criterion.ce
-                reducer.zero_grad()
-                loss.backward()
-                reducer.finish()
-                optimizer.step()
-            if meter is None:
-                torch.stack((loss.detach(), soft, ce), out=batch_losses[steps])
-                correct += (label == torch.argmax(y_pred, dim=1)).sum()
-                total += label.size(0)
-            if batch_hook is not None and loader is not None:
-                batch_hook("train", global_step - 1, img, label)
-            steps += 1
-            if steps >= epoch_steps:
-                break
-        if meter is None:
-            per_batch = batch_losses[:steps].tolist()   # the epoch's one read of the per-batch scalars
-            train_loss = sum(r[0] for r in per_batch) / max(steps, 1)
-            train_acc = correct.item() / max(total, 1)
-        else:
-            metered = meter.read()   # the epoch's one read: every step's (loss, soft, ce) row and the hit totals
-            meter.reset()
-            per_batch = [row[:3] for row in metered["rows"]]
-            train_loss, train_acc = metered["loss_mean"], metered["accuracy"]
-
-        model.eval()
-        val_batch = min(getattr(c, "val_batch_size", batch_size), n_val)
-
-        def validate(hook):
-            batches = val_set.batches(val_batch, False, None, rank, world, drop_last=False)
-            if graph_eval:
-                return _graph_validate(session, batches, hook, world)
-            return _eager_validate(model, batches, val_criterion, use_amp, hook, world, device, float_logits=True)
-
-        if graph_eval and session is None:
-            session = _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, False)
-        val_acc, val_loss, val_samples = validate(batch_hook)
-        rec = {"epoch": epoch + 1, "Loss/Train": train_loss, "Loss/Validation": val_loss, "Accuracy/Train": train_acc,
-               "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
-        if meter is not None:
-            rec["Accuracy/TrainTop5"] = metered["accuracy_topk"]
-        if optimizer_name is not None:
-            rec["Optimizer"] = optimizer_name
-        if control:
-            rec.update(_step_control_record(optimizer))
-        if ema:
-            with optimizer.ema_weights():
-                rec["Accuracy/ValidationEMA"], rec["Loss/ValidationEMA"], _ = validate(None)
-        history.append(rec)
-        if rank == 0:
-            for k, (lt, ld, lc) in enumerate(per_batch):
-                log_f.write(json.dumps({"step": first_step + k, "Batch Loss/Train": lt, "Batch Loss/Dist": ld, "Batch Loss/CE": lc}) + "\n")
-            log_f.write(json.dumps(rec) + "\n")
-            log_f.flush()
-            log(rec)
-            if val_acc > best_acc or epoch == 0:  # as train (train.py:288-290); the reference's distillation cell keeps no checkpoint
-                best_acc = max(best_acc, val_acc)
-                torch.save(model.state_dict(), os.path.join(out_dir, "model_best.pt"))
-            if ema and (rec["Accuracy/ValidationEMA"] > best_ema_acc or epoch == 0):
-                best_ema_acc = max(best_ema_acc, rec["Accuracy/ValidationEMA"])
-                torch.save(optimizer.ema_state_dict(model), os.path.join(out_dir, "model_ema_best.pt"))
-    if gstep is not None:
-        gstep.close()
-    if session is not None:
-        session.close()
-    if rank == 0:
-        log_f.write(json.dumps({"Training time": time.perf_counter() - start}) + "\n")
-        log_f.close()
-    return model, history
+        cache, cache_rec = _teacher_cache(teacher, view, train_nhwc, c.num_classes, run.device, teacher_cache_path, resize, crop, run.rank,
+                                          run.world, batch_hook, run.batch_size)
+        cache_rec["seconds"] = time.perf_counter() - run.start
+        if run.rank == 0:
+            run.log_f.write(json.dumps({"TeacherCache": cache_rec}) + "\n")
+            run.log_f.flush()
+    loader = _resident_loader(run, train_nhwc, aug, False) if device_loader else None
+    step = _paired_distill_step(run, criterion, use_amp, graph, aug, view, teacher, cache, loader, train_nhwc, batch_hook)
+    return _run_epochs(run, step, _TrainBooks(run, ("Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE"), block=True),
+                       _validator(run, graph_eval, use_amp, float_logits=True), epochs, batch_hook, device_loader, log)
 
 
 def build_parser():
@@ -855,17 +846,15 @@ def build_parser():
 
 def main(argv=None):
     a = build_parser().parse_args(argv)
-    control = dict(lr_schedule=a.lr_schedule, warmup_steps=a.warmup_steps, eta_min=a.eta_min, clip_grad_norm=a.clip_grad_norm,
-                   skip_nonfinite=a.skip_nonfinite, ema_decay=a.ema_decay, ema_warmup=a.ema_warmup, accumulate_steps=a.accumulate_steps,
-                   optimizer=a.optimizer, momentum=a.momentum, nesterov=not a.no_nesterov)
+    common = dict(mixer=a.mixer, epochs=a.epochs, steps_per_epoch=a.steps_per_epoch, batch_size=a.batch_size, out_dir=a.out, graph=a.graph,
+                  graph_eval=a.graph_eval, device_meter=a.device_meter, device_loader=a.device_loader, lr_schedule=a.lr_schedule,
+                  warmup_steps=a.warmup_steps, eta_min=a.eta_min, clip_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite,
+                  ema_decay=a.ema_decay, ema_warmup=a.ema_warmup, accumulate_steps=a.accumulate_steps, optimizer=a.optimizer,
+                  momentum=a.momentum, nesterov=not a.no_nesterov)
     if a.distill_paired:
-        train_distill(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, graph=a.graph, augment=not a.no_augment, out_dir=a.out,
-                      graph_eval=a.graph_eval, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache,
-                      device_meter=a.device_meter, device_loader=a.device_loader, **control)
+        train_distill(a.config, augment=not a.no_augment, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache, **common)
         return
-    train(a.config, a.mixer, a.epochs, a.steps_per_epoch, a.batch_size, distill=a.distill, out_dir=a.out, graph=a.graph,
-          model=a.model, augment=a.augment, graph_eval=a.graph_eval, device_meter=a.device_meter, device_loader=a.device_loader,
-          **control)
+    train(a.config, distill=a.distill, model=a.model, augment=a.augment, **common)
 
 
 if __name__ == "__main__":
