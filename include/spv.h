@@ -878,6 +878,34 @@ int spv_distill_loss_idx_fwd(const float* student, const float* cache, const int
 int spv_distill_loss_idx_bwd(const float* student, const float* cache, const int64_t* index, const int64_t* labels, const float* lse3,
                              const float* grad_out, float* dlogits, int rows, int n_cache, int classes, float T, float w_soft, float w_ce,
                              void* stream);
+/* The feature-matching term of the distillation cell (spectre_vit/repl/train.py:306, 343-346), one launch each way:
+ *   out[0] = 1 - mean_r cos_r,   cos_r = s_r . t_r / (|s_r| |t_r|)
+ * student [rows][width] in s_dtype, teacher [rows][width] in t_dtype (SPV_F32 or SPV_BF16 each), dense rows.  A wave per row: the three
+ * dot products s.s, t.t, s.t are accumulated in fp32 -- lane l takes the 8-element chunks l, l + 64, ... of the row in order, then the
+ * lanes 0 .. width % 8 - 1 one element each of what is left -- and joined by the wave reduction; |s| = sqrt(s.s), |t| = sqrt(t.t),
+ * cos = (s.t / |s|) / |t|.  The chunks are read as 16-byte loads when both bases and both row pitches are multiples of 16 bytes and as
+ * element loads otherwise: the same additions in the same order, the same bits.  stat3 [3][rows] (fp32) receives |s|, |t|, cos: the
+ * backward's input.  The one deviation from F.normalize + nn.CosineSimilarity: a row with |s| < 1e-12 or |t| < 1e-12 has cos_r = 0 and
+ * a zero gradient row (the reference's clamp_min gives a gradient of order 1e12 there).  A NaN in a row (an unfilled cache row) makes
+ * cos_r and out[0] NaN.  Rows are joined in a fixed order (spv_distill_loss_fwd's scheme): `workspace` holds
+ * spv_feature_cosine_workspace_floats() floats, zeroed once by the caller; two calls give the same bits.
+ *   dstudent_r = -grad_out[0] * w / rows * (t_r / |t_r| - cos_r * s_r / |s_r|) / |s_r|      in s_dtype; elementwise, 4 elements per
+ * thread when width % 4 == 0 and the three bases are 16-byte aligned.  `w` is the term's weight in the total loss.
+ * spv_feature_cosine_idx_fwd / _idx_bwd: the teacher row of sample r is cache + index[r] * width (cache: fp32 [n_cache][width], index:
+ * int64 [rows] on the device).  One device row body, the same grid, workspace and join: the result is, bit for bit, the dense call on
+ * cache[index].  An index outside [0, n_cache) cannot be seen by the host: the kernel forms no cache address for that row; its three
+ * stat3 entries and out[0] are NaN and the backward writes NaN to that row of dstudent (spv_distill_loss_idx_*'s convention).
+ * Refused on the host, before any launch: a missing pointer, rows / width / n_cache <= 0, rows > 2^24, a dtype other than the two, a
+ * weight not finite.  No census slot. */
+int64_t spv_feature_cosine_workspace_floats(void);
+int spv_feature_cosine_fwd(const void* student, const void* teacher, float* stat3, float* out, float* workspace, int rows, int width,
+                           int s_dtype, int t_dtype, void* stream);
+int spv_feature_cosine_bwd(const void* student, const void* teacher, const float* stat3, const float* grad_out, void* dstudent, int rows,
+                           int width, int s_dtype, int t_dtype, float w, void* stream);
+int spv_feature_cosine_idx_fwd(const void* student, const float* cache, const int64_t* index, float* stat3, float* out, float* workspace,
+                               int rows, int n_cache, int width, int s_dtype, void* stream);
+int spv_feature_cosine_idx_bwd(const void* student, const float* cache, const int64_t* index, const float* stat3, const float* grad_out,
+                               void* dstudent, int rows, int n_cache, int width, int s_dtype, float w, void* stream);
 
 /* The end of an inference / validation batch, one launch (csrc/spv_infer.hip): logits [rows][classes] (dtype: SPV_F32 or SPV_BF16),
  * labels int64 [rows], *n_valid an int32 DEVICE word (read by the kernel, so a captured launch follows it), 1 <= k <= 8.

@@ -397,6 +397,153 @@ __global__ __launch_bounds__(DL_THREADS) void distill_bwd_kernel(const float* __
     }
 }
 
+// ================================================================ feature cosine (the hint term, include/spv.h)
+constexpr int FC_CHUNK = 8;          // elements a lane takes at a time: 16 bytes of bf16, two 16-byte loads of fp32
+constexpr float FC_TINY = 1e-12f;    // F.normalize's eps: below it a norm is "zero" and the row contributes cos = 0, gradient 0
+
+// eight consecutive elements as floats; VEC: 16-byte loads (p 16-byte aligned), else element loads -- the same values either way
+template <typename T, bool VEC>
+__device__ __forceinline__ void fc_ld8(const T* p, float (&v)[FC_CHUNK]) {
+    if constexpr (!VEC) {
+#pragma unroll
+        for (int u = 0; u < FC_CHUNK; ++u) v[u] = io<T>::ld(p + u);
+    } else if constexpr (sizeof(T) == 4) {
+        const float4 a = *reinterpret_cast<const float4*>(p), b = *(reinterpret_cast<const float4*>(p) + 1);
+        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w;
+        v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
+    } else {
+        const uint4 q = *reinterpret_cast<const uint4*>(p);
+        v[0] = __uint_as_float(q.x << 16); v[1] = __uint_as_float(q.x & 0xffff0000u);
+        v[2] = __uint_as_float(q.y << 16); v[3] = __uint_as_float(q.y & 0xffff0000u);
+        v[4] = __uint_as_float(q.z << 16); v[5] = __uint_as_float(q.z & 0xffff0000u);
+        v[6] = __uint_as_float(q.w << 16); v[7] = __uint_as_float(q.w & 0xffff0000u);
+    }
+}
+
+// Wave per row, one pass: lane l accumulates s.s, t.t, s.t over the chunks l, l + 64, ... and then (l < W % 8) over one element of the
+// rest, with explicit fmas -- the order does not depend on VEC, so the aligned and the unaligned launch return the same bits -- and
+// the wave reduction joins the lanes.  Rows are joined as in distill_fwd_body: per-workgroup partials, the last workgroup to arrive
+// adds them by the same tree every time and re-arms the counter (one exit path).
+// INDEXED: t is the resident fp32 feature cache [n_cache][W] and row r's teacher row is t + index[r] * W.  A row whose index lies
+// outside [0, n_cache) forms no cache address and reads nothing: its three stats and the loss are NaN.
+template <typename TS, typename TT, bool INDEXED, bool VEC>
+__global__ __launch_bounds__(DL_THREADS) void feature_cosine_fwd_kernel(const TS* __restrict__ s, const TT* __restrict__ t,
+                                                                        const int64_t* __restrict__ index, float* __restrict__ stat3,
+                                                                        float* __restrict__ out, float* __restrict__ partial,
+                                                                        unsigned* __restrict__ counter, int rows, int n_cache, int W) {
+    __shared__ float ws[DL_WAVES];
+    __shared__ bool last;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int nch = W / FC_CHUNK, rest = W - nch * FC_CHUNK;
+    float acc = 0.0f;   // the same in every lane
+    for (int r = blockIdx.x * DL_WAVES + wave; r < rows; r += gridDim.x * DL_WAVES) {
+        const TS* sr = s + (size_t)r * W;
+        const TT* tr = t + (size_t)r * W;
+        if constexpr (INDEXED) {
+            const int64_t row = index[r];
+            if (row < 0 || row >= (int64_t)n_cache) {   // wave uniform
+                if (lane == 0) stat3[r] = stat3[rows + r] = stat3[2 * rows + r] = __builtin_nanf("");
+                acc += __builtin_nanf("");
+                continue;
+            }
+            tr = t + (size_t)row * W;
+        }
+        float ss = 0.0f, tt = 0.0f, st = 0.0f;
+        for (int j = lane; j < nch; j += 64) {
+            float a[FC_CHUNK], b[FC_CHUNK];
+            fc_ld8<TS, VEC>(sr + (size_t)j * FC_CHUNK, a);
+            fc_ld8<TT, VEC>(tr + (size_t)j * FC_CHUNK, b);
+#pragma unroll
+            for (int u = 0; u < FC_CHUNK; ++u) {
+                ss = fmaf(a[u], a[u], ss);
+                tt = fmaf(b[u], b[u], tt);
+                st = fmaf(a[u], b[u], st);
+            }
+        }
+        if (lane < rest) {
+            const float a = io<TS>::ld(sr + nch * FC_CHUNK + lane), b = io<TT>::ld(tr + nch * FC_CHUNK + lane);
+            ss = fmaf(a, a, ss);
+            tt = fmaf(b, b, tt);
+            st = fmaf(a, b, st);
+        }
+        ss = wave_sum(ss);
+        tt = wave_sum(tt);
+        st = wave_sum(st);
+        const float ns = sqrtf(ss), nt = sqrtf(tt);
+        const float c = (ns < FC_TINY || nt < FC_TINY) ? 0.0f : (st / ns) / nt;   // a NaN norm is not "tiny": it stays NaN
+        if (lane == 0) {
+            stat3[r] = ns;
+            stat3[rows + r] = nt;
+            stat3[2 * rows + r] = c;
+        }
+        acc += c;
+    }
+    if (lane == 0) ws[wave] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        float a = 0.0f;
+        for (int w = 0; w < DL_WAVES; ++w) a += ws[w];
+        partial[blockIdx.x] = a;
+        __threadfence();
+        last = atomicAdd(counter, 1u) == gridDim.x - 1;
+    }
+    __syncthreads();
+    if (last) {
+        __threadfence();
+        if (wave == 0) {   // one partial per lane (gridDim.x <= 64)
+            const float a = wave_sum(lane < (int)gridDim.x ? __builtin_nontemporal_load(partial + lane) : 0.0f);
+            if (lane == 0) {
+                out[0] = 1.0f - a / (float)rows;
+                *counter = 0u;
+            }
+        }
+    }
+}
+
+// ds = -go w / rows * (t / |t| - cos s / |s|) / |s|, V elements per thread (V = 4: W % 4 == 0 and 16-byte aligned bases).  A row with
+// a norm below FC_TINY gets zeros; INDEXED: a row whose index lies outside [0, n_cache) reads nothing of t and is NaN.
+template <typename TS, typename TT, bool INDEXED, int V>
+__global__ __launch_bounds__(DL_THREADS) void feature_cosine_bwd_kernel(const TS* __restrict__ s, const TT* __restrict__ t,
+                                                                        const int64_t* __restrict__ index, const float* __restrict__ stat3,
+                                                                        const float* __restrict__ go, TS* __restrict__ ds, int rows,
+                                                                        int n_cache, int W, float w) {
+    const float k = -go[0] * w / (float)rows;
+    const int per_row = W / V;
+    const int64_t total = (int64_t)rows * per_row;
+    for (int64_t e = (int64_t)blockIdx.x * DL_THREADS + threadIdx.x; e < total; e += (int64_t)gridDim.x * DL_THREADS) {
+        const int r = (int)(e / per_row), c = (int)(e - (int64_t)r * per_row) * V;
+        const size_t at = (size_t)r * W + c;
+        float a[V], b[V], o[V];
+        size_t tat = at;
+        bool held = true;
+        if constexpr (INDEXED) {
+            const int64_t row = index[r];
+            held = row >= 0 && row < (int64_t)n_cache;
+            tat = (size_t)row * W + c;   // an offset, not an address: nothing is formed from it unless held
+        }
+        const float ns = stat3[r], nt = stat3[rows + r], cs = stat3[2 * rows + r];
+        if (!held) {
+#pragma unroll
+            for (int u = 0; u < V; ++u) o[u] = __builtin_nanf("");
+        } else if (ns < FC_TINY || nt < FC_TINY) {
+#pragma unroll
+            for (int u = 0; u < V; ++u) o[u] = 0.0f;
+        } else {
+            if constexpr (V == 4) {
+                io<TS>::ld4(s + at, a);
+                io<TT>::ld4(t + tat, b);
+            } else {
+                a[0] = io<TS>::ld(s + at);
+                b[0] = io<TT>::ld(t + tat);
+            }
+#pragma unroll
+            for (int u = 0; u < V; ++u) o[u] = k * ((b[u] / nt - cs * (a[u] / ns)) / ns);
+        }
+        if constexpr (V == 4) io<TS>::st4(ds + at, o);
+        else io<TS>::st(ds + at, o[0]);
+    }
+}
+
 // ================================================================ resident teacher logits
 constexpr int LC_THREADS = 256;
 
@@ -525,6 +672,123 @@ extern "C" int spv_distill_loss_idx_bwd(const float* student, const float* cache
                        dim3(DL_THREADS), 0, static_cast<hipStream_t>(stream), student, cache, index, labels, lse3, grad_out, dlogits, rows,
                        n_cache, classes, T, w_soft, w_ce);
     SPV_LAUNCH_CHECK("spv_distill_loss_idx_bwd");
+    return 0;
+}
+
+// ---- the feature cosine term, dense and through the resident feature cache
+extern "C" int64_t spv_feature_cosine_workspace_floats() { return DL_MAX_WG + 1; }   // a partial sum per workgroup + the arrival counter
+
+static inline size_t fc_es(int dtype) { return dtype == SPV_BF16 ? 2 : 4; }
+
+static int feature_check(const char* name, const void* a, const void* b, const void* c, const void* d, const void* e, int rows, int width,
+                         int s_dtype, int t_dtype, float w) {
+    SPV_CHECK(rows > 0 && width > 0, "%s: empty (rows=%d width=%d)", name, rows, width);
+    SPV_CHECK(rows <= (1 << 24), "%s: rows=%d above 2^24 (the mean's divisor is an exact fp32 integer)", name, rows);
+    SPV_CHECK((s_dtype == SPV_F32 || s_dtype == SPV_BF16) && (t_dtype == SPV_F32 || t_dtype == SPV_BF16),
+              "%s: bad dtype (student %d, teacher %d): SPV_F32 or SPV_BF16", name, s_dtype, t_dtype);
+    SPV_CHECK(std::isfinite(w), "%s: the weight is not finite", name);
+    SPV_CHECK(a != nullptr && b != nullptr, "%s: student / teacher missing", name);
+    SPV_CHECK(c != nullptr && d != nullptr && e != nullptr, "%s: an output, stat3, grad_out or workspace pointer is missing", name);
+    SPV_CHECK((uintptr_t)a % fc_es(s_dtype) == 0 && (uintptr_t)b % fc_es(t_dtype) == 0, "%s: student / teacher not aligned to their elements",
+              name);
+    return 0;
+}
+
+// both operands readable as 16-byte chunks: both bases and both row pitches multiples of 16 bytes
+static inline bool fc_vec(const void* s, const void* t, int width, int s_dtype, int t_dtype) {
+    return (((uintptr_t)s | (uintptr_t)t) & 15) == 0 && (width * fc_es(s_dtype)) % 16 == 0 && (width * fc_es(t_dtype)) % 16 == 0;
+}
+
+template <bool INDEXED>
+static void feature_fwd_launch(const void* s, const void* t, const int64_t* index, float* stat3, float* out, float* workspace, int rows,
+                               int n_cache, int width, int s_dtype, int t_dtype, hipStream_t st) {
+    const dim3 grid(std::min(cdiv(rows, DL_WAVES), DL_MAX_WG)), block(DL_THREADS);
+    unsigned* counter = reinterpret_cast<unsigned*>(workspace + DL_MAX_WG);
+    const bool vec = fc_vec(s, t, width, s_dtype, t_dtype);
+#define SPV_FC_FWD(TS, TT)                                                                                                               \
+    do {                                                                                                                                 \
+        if (vec)                                                                                                                         \
+            hipLaunchKernelGGL((feature_cosine_fwd_kernel<TS, TT, INDEXED, true>), grid, block, 0, st, static_cast<const TS*>(s),         \
+                               static_cast<const TT*>(t), index, stat3, out, workspace, counter, rows, n_cache, width);                  \
+        else                                                                                                                             \
+            hipLaunchKernelGGL((feature_cosine_fwd_kernel<TS, TT, INDEXED, false>), grid, block, 0, st, static_cast<const TS*>(s),        \
+                               static_cast<const TT*>(t), index, stat3, out, workspace, counter, rows, n_cache, width);                  \
+    } while (0)
+    if constexpr (INDEXED) {   // the cache is fp32
+        if (s_dtype == SPV_BF16) SPV_FC_FWD(bf16_t, float);
+        else SPV_FC_FWD(float, float);
+    } else {
+        if (s_dtype == SPV_BF16 && t_dtype == SPV_BF16) SPV_FC_FWD(bf16_t, bf16_t);
+        else if (s_dtype == SPV_BF16) SPV_FC_FWD(bf16_t, float);
+        else if (t_dtype == SPV_BF16) SPV_FC_FWD(float, bf16_t);
+        else SPV_FC_FWD(float, float);
+    }
+#undef SPV_FC_FWD
+}
+
+template <bool INDEXED>
+static void feature_bwd_launch(const void* s, const void* t, const int64_t* index, const float* stat3, const float* go, void* ds, int rows,
+                               int n_cache, int width, int s_dtype, int t_dtype, float w, hipStream_t st) {
+    const bool vec = width % 4 == 0 && (((uintptr_t)s | (uintptr_t)t | (uintptr_t)ds) & 15) == 0;
+    const int64_t total = (int64_t)rows * (vec ? width / 4 : width);
+    const dim3 grid((unsigned)std::min<int64_t>((total + DL_THREADS - 1) / DL_THREADS, 1024)), block(DL_THREADS);
+#define SPV_FC_BWD(TS, TT)                                                                                                               \
+    do {                                                                                                                                 \
+        if (vec)                                                                                                                         \
+            hipLaunchKernelGGL((feature_cosine_bwd_kernel<TS, TT, INDEXED, 4>), grid, block, 0, st, static_cast<const TS*>(s),            \
+                               static_cast<const TT*>(t), index, stat3, go, static_cast<TS*>(ds), rows, n_cache, width, w);              \
+        else                                                                                                                             \
+            hipLaunchKernelGGL((feature_cosine_bwd_kernel<TS, TT, INDEXED, 1>), grid, block, 0, st, static_cast<const TS*>(s),            \
+                               static_cast<const TT*>(t), index, stat3, go, static_cast<TS*>(ds), rows, n_cache, width, w);              \
+    } while (0)
+    if constexpr (INDEXED) {
+        if (s_dtype == SPV_BF16) SPV_FC_BWD(bf16_t, float);
+        else SPV_FC_BWD(float, float);
+    } else {
+        if (s_dtype == SPV_BF16 && t_dtype == SPV_BF16) SPV_FC_BWD(bf16_t, bf16_t);
+        else if (s_dtype == SPV_BF16) SPV_FC_BWD(bf16_t, float);
+        else if (t_dtype == SPV_BF16) SPV_FC_BWD(float, bf16_t);
+        else SPV_FC_BWD(float, float);
+    }
+#undef SPV_FC_BWD
+}
+
+extern "C" int spv_feature_cosine_fwd(const void* student, const void* teacher, float* stat3, float* out, float* workspace, int rows,
+                                      int width, int s_dtype, int t_dtype, void* stream) {
+    if (int rc = feature_check("spv_feature_cosine_fwd", student, teacher, stat3, out, workspace, rows, width, s_dtype, t_dtype, 0.0f)) return rc;
+    feature_fwd_launch<false>(student, teacher, nullptr, stat3, out, workspace, rows, 0, width, s_dtype, t_dtype, static_cast<hipStream_t>(stream));
+    SPV_LAUNCH_CHECK("spv_feature_cosine_fwd");
+    return 0;
+}
+
+extern "C" int spv_feature_cosine_bwd(const void* student, const void* teacher, const float* stat3, const float* grad_out, void* dstudent,
+                                      int rows, int width, int s_dtype, int t_dtype, float w, void* stream) {
+    if (int rc = feature_check("spv_feature_cosine_bwd", student, teacher, stat3, grad_out, dstudent, rows, width, s_dtype, t_dtype, w)) return rc;
+    SPV_CHECK((uintptr_t)dstudent % fc_es(s_dtype) == 0, "spv_feature_cosine_bwd: dstudent not aligned to its elements");
+    feature_bwd_launch<false>(student, teacher, nullptr, stat3, grad_out, dstudent, rows, 0, width, s_dtype, t_dtype, w,
+                              static_cast<hipStream_t>(stream));
+    SPV_LAUNCH_CHECK("spv_feature_cosine_bwd");
+    return 0;
+}
+
+extern "C" int spv_feature_cosine_idx_fwd(const void* student, const float* cache, const int64_t* index, float* stat3, float* out,
+                                          float* workspace, int rows, int n_cache, int width, int s_dtype, void* stream) {
+    if (int rc = feature_check("spv_feature_cosine_idx_fwd", student, cache, stat3, out, workspace, rows, width, s_dtype, SPV_F32, 0.0f)) return rc;
+    if (int rc = distill_idx_check("spv_feature_cosine_idx_fwd", index, n_cache)) return rc;
+    feature_fwd_launch<true>(student, cache, index, stat3, out, workspace, rows, n_cache, width, s_dtype, SPV_F32, static_cast<hipStream_t>(stream));
+    SPV_LAUNCH_CHECK("spv_feature_cosine_idx_fwd");
+    return 0;
+}
+
+extern "C" int spv_feature_cosine_idx_bwd(const void* student, const float* cache, const int64_t* index, const float* stat3,
+                                          const float* grad_out, void* dstudent, int rows, int n_cache, int width, int s_dtype, float w,
+                                          void* stream) {
+    if (int rc = feature_check("spv_feature_cosine_idx_bwd", student, cache, stat3, grad_out, dstudent, rows, width, s_dtype, SPV_F32, w)) return rc;
+    if (int rc = distill_idx_check("spv_feature_cosine_idx_bwd", index, n_cache)) return rc;
+    SPV_CHECK((uintptr_t)dstudent % fc_es(s_dtype) == 0, "spv_feature_cosine_idx_bwd: dstudent not aligned to its elements");
+    feature_bwd_launch<true>(student, cache, index, stat3, grad_out, dstudent, rows, n_cache, width, s_dtype, SPV_F32, w,
+                             static_cast<hipStream_t>(stream));
+    SPV_LAUNCH_CHECK("spv_feature_cosine_idx_bwd");
     return 0;
 }
 

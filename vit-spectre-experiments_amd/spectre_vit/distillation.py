@@ -12,6 +12,8 @@ sample (train.py:92-100), Pillow's integer resampling bit for bit -- read from t
 ``DistillationLoss`` is the soft-target + cross-entropy loss as one launch each way (``hip_ops.distill_loss``).
 ``TeacherLogitCache`` keeps the frozen teacher's logits of every sample resident on the GPU (the teacher's view has no random op and
 the teacher is frozen, so they are a function of the sample index alone): filled once, read by ``DistillationLoss(..., index=...)``.
+``DistillationLoss(feature_loss_weight=...)`` adds the cell's feature-matching term (train.py:306, 343-346: 1 - mean cosine of the two
+models' CLS features) as one more launch each way; ``TeacherLogitCache(feature_dim=...)`` keeps the teacher's features beside its logits.
 """
 import math
 
@@ -209,14 +211,24 @@ class TeacherView:
 class DistillationLoss(nn.Module):
     """The loss of reference train.py:300-302, 334-348 on the HIP path (GPU only, like spectre_vit.loss.CrossEntropyLoss): returns the
     weighted loss; ``.soft`` and ``.ce`` hold the unweighted soft-target and cross-entropy terms of the last call (device scalars,
-    detached), the reference's "Batch Loss/Dist" and "Batch Loss/CE"."""
+    detached), the reference's "Batch Loss/Dist" and "Batch Loss/CE".
+    feature_loss_weight (0.0: off, and then not one launch differs): the feature-matching term of train.py:306, 343-346,
+    feat = 1 - mean_r cos(student_feat[r], teacher_feat[r]), one more launch each way (``hip_ops.feature_cosine``); the loss is then
+    w_soft * soft + w_ce * ce + w_feat * feat and ``.feat`` holds the unweighted term of the last call.  The two feature matrices must
+    have one width: a teacher of another width projects inside its own module (no learned projector here, as in the reference)."""
 
-    def __init__(self, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75, meter=None):
+    def __init__(self, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75, meter=None, feature_loss_weight=0.0):
         super().__init__()
         if not (T > 0 and math.isfinite(T)):
             raise ValueError(f"temperature T={T} must be positive and finite")
         self.T, self.soft_target_loss_weight, self.ce_loss_weight = float(T), float(soft_target_loss_weight), float(ce_loss_weight)
-        self.soft = self.ce = None
+        self.feature_loss_weight = float(feature_loss_weight)
+        if not math.isfinite(self.feature_loss_weight):
+            raise ValueError(f"feature_loss_weight={feature_loss_weight!r} must be finite")
+        if self.feature_loss_weight != 0.0 and meter is not None:
+            raise ValueError(f"feature_loss_weight={self.feature_loss_weight} with a meter ({type(meter).__name__}): the meter's log row "
+                             "holds loss, soft and CE and has no slot for a fourth term, so its logged loss would lack the feature term")
+        self.soft = self.ce = self.feat = None
         if meter is not None:
             from .meter import TrainMeter
             if not isinstance(meter, TrainMeter):
@@ -225,18 +237,45 @@ class DistillationLoss(nn.Module):
         # logged into the meter's device block; None: the un-metered launch, exactly
         self.meter = meter
 
-    def forward(self, student_logits, teacher_logits, labels, index=None):
+    def _features(self, student_feat, teacher_feat, teacher_logits, index):
+        """the two feature matrices of a call with the term on, checked (ValueErrors name the values) -> (student, teacher)"""
+        w = self.feature_loss_weight
+        if teacher_feat is None and index is not None and isinstance(teacher_logits, TeacherLogitCache):
+            teacher_feat = teacher_logits.features
+        if isinstance(teacher_feat, TeacherLogitCache):
+            teacher_feat = teacher_feat.features
+        if student_feat is None or teacher_feat is None:
+            raise ValueError(f"feature_loss_weight={w}: the feature term needs student_feat and teacher_feat, got student_feat="
+                             f"{None if student_feat is None else tuple(student_feat.shape)}, teacher_feat="
+                             f"{None if teacher_feat is None else tuple(teacher_feat.shape)} (with index=: the cache's feature matrix, "
+                             "TeacherLogitCache(feature_dim=...).features)")
+        if student_feat.dim() != 2 or teacher_feat.dim() != 2 or student_feat.shape[1] != teacher_feat.shape[1]:
+            raise ValueError(f"feature_loss_weight={w}: student features {tuple(student_feat.shape)} and teacher features "
+                             f"{tuple(teacher_feat.shape)} differ in width; project inside the teacher module (there is no learned "
+                             "projector in this loss)")
+        return student_feat, teacher_feat
+
+    def forward(self, student_logits, teacher_logits, labels, index=None, student_feat=None, teacher_feat=None):
         """index (int64 [rows], on the device): ``teacher_logits`` is then the resident cache -- a TeacherLogitCache or its [n, classes]
-        matrix -- and row r's teacher logits are cache[index[r]], read inside the kernel (``hip_ops.distill_loss_cached``)."""
+        matrix -- and row r's teacher logits are cache[index[r]], read inside the kernel (``hip_ops.distill_loss_cached``).
+        student_feat, teacher_feat ([rows, width]; with index= teacher_feat is the cache's feature matrix [n, width]): read only with a
+        non-zero feature_loss_weight; with 0.0 they are allowed and ignored."""
         from . import hip_ops
         metered = {} if self.meter is None else {"meter": self.meter}
+        featured = self.feature_loss_weight != 0.0
+        if featured:   # refused before the logit loss launches
+            student_feat, teacher_feat = self._features(student_feat, teacher_feat, teacher_logits, index)
         if index is not None:
             cache = teacher_logits.logits if isinstance(teacher_logits, TeacherLogitCache) else teacher_logits
             loss, self.soft, self.ce = hip_ops.distill_loss_cached(student_logits, cache, index, labels, self.T,
                                                                    self.soft_target_loss_weight, self.ce_loss_weight, **metered)
+            if featured:
+                loss, self.feat = hip_ops.feature_cosine_cached(student_feat, teacher_feat, index, self.feature_loss_weight, loss)
             return loss
         loss, self.soft, self.ce = hip_ops.distill_loss(student_logits, teacher_logits, labels, self.T, self.soft_target_loss_weight,
                                                         self.ce_loss_weight, **metered)
+        if featured:
+            loss, self.feat = hip_ops.feature_cosine(student_feat, teacher_feat, self.feature_loss_weight, loss)
         return loss
 
 
@@ -258,35 +297,56 @@ class TeacherLogitCache:
 
         cache = TeacherLogitCache(n_train, num_classes, device)
         cache.fill(teacher, view, train_u8_nhwc)                  # ceil(n / 512) teacher calls, once
-        loss = criterion(student_logits, cache, labels, index=sel)"""
+        loss = criterion(student_logits, cache, labels, index=sel)
+
+    feature_dim (None: no features, and every byte of the behaviour and the file format is that of a cache without the argument): a
+    second fixed-address fp32 matrix ``.features`` [n, feature_dim], NaN until filled, holds the teacher's CLS features for
+    ``DistillationLoss(feature_loss_weight=...)``; ``store`` / ``fill`` / ``complete`` / ``save`` / ``load`` cover both matrices."""
 
     META = ("n", "classes", "resize", "crop", "tag")
 
-    def __init__(self, n, classes, device):
+    def __init__(self, n, classes, device, feature_dim=None):
         n, classes = int(n), int(classes)
         if n <= 0 or classes <= 0:
             raise ValueError(f"TeacherLogitCache: n={n}, classes={classes}")
+        if feature_dim is not None and int(feature_dim) <= 0:
+            raise ValueError(f"TeacherLogitCache: feature_dim={feature_dim}")
         self.n, self.classes = n, classes
+        self.feature_dim = None if feature_dim is None else int(feature_dim)
         self.logits = torch.full((n, classes), float("nan"), dtype=torch.float32, device=device)
+        self.features = None if feature_dim is None else torch.full((n, self.feature_dim), float("nan"), dtype=torch.float32, device=device)
 
-    def store(self, index, logits):
+    def store(self, index, logits, features=None):
         """logits fp32 [rows, classes] -> rows ``index`` (int64 [rows]; None: rows 0..rows-1) of the cache: one launch.  A row whose
-        index lies outside the cache is skipped by the kernel."""
+        index lies outside the cache is skipped by the kernel.  features fp32 [rows, feature_dim] (a cache built with feature_dim): the
+        same rows of ``.features``, by a second launch of the same kernel."""
         from spectre_vit import _native
         from spectre_vit.hip_ops import _p, _require_gpu, _stream
         if logits.dim() != 2 or logits.dtype != torch.float32 or logits.shape[1] != self.classes:
             raise ValueError(f"TeacherLogitCache.store: fp32 logits [rows, {self.classes}] expected, got {logits.dtype} {tuple(logits.shape)}")
         if index is not None and (index.dtype != torch.int64 or index.shape != logits.shape[:1]):
             raise ValueError(f"TeacherLogitCache.store: index is an int64 vector of {logits.shape[0]} rows, got {index.dtype} {tuple(index.shape)}")
-        _require_gpu(self.logits, logits, index)
+        if (features is None) != (self.features is None):
+            raise ValueError(f"TeacherLogitCache.store: a cache with feature_dim={self.feature_dim} "
+                             f"{'takes no features' if self.features is None else 'needs features with every store'}")
+        if features is not None and (features.dim() != 2 or features.dtype != torch.float32
+                                     or tuple(features.shape) != (logits.shape[0], self.feature_dim)):
+            raise ValueError(f"TeacherLogitCache.store: fp32 features [{logits.shape[0]}, {self.feature_dim}] expected, got "
+                             f"{features.dtype} {tuple(features.shape)}")
+        _require_gpu(self.logits, logits, index, features)
         logits = logits.detach().contiguous()
         index = None if index is None else index.contiguous()
         _native.call("spv_logit_cache_store", _p(self.logits), _p(index), _p(logits), logits.shape[0], self.n, self.classes, _stream())
+        if features is not None:
+            features = features.detach().contiguous()
+            _native.call("spv_logit_cache_store", _p(self.features), _p(index), _p(features), features.shape[0], self.n, self.feature_dim,
+                         _stream())
 
     def fill(self, teacher, view, images_u8_nhwc, batch_size=512, rank=0, world=1, process_group=None, batch_hook=None):
         """Every row of the cache: ``view(images, idx)`` -> ``teacher(img, return_features=True)[0].float()`` under no_grad -> ``store``,
-        over the row blocks of ``fill_plan``.  Draws from no torch generator.  world > 1: a rank computes its own blocks only, and round
-        by round the ranks exchange them with an all-gather (a copy: every rank ends with every row, bits unchanged).
+        over the row blocks of ``fill_plan`` (a cache with feature_dim stores the same call's features too).  Draws from no torch
+        generator.  world > 1: a rank computes its own blocks only, and round by round the ranks exchange them with an all-gather (a
+        copy: every rank ends with every row, bits unchanged).
         batch_hook("teacher_fill", k, img_teacher, idx), k the block's number (test seam).  -> the teacher calls of this rank."""
         if getattr(teacher, "training", False):
             raise ValueError("TeacherLogitCache.fill: the teacher is in train mode -- its output is then not a function of the sample "
@@ -298,7 +358,7 @@ class TeacherLogitCache:
         rounds = ((self.n + batch_size - 1) // batch_size + world - 1) // world
         calls = 0
         for j in range(rounds):
-            out = None
+            out = feats = None
             if j < len(mine):
                 start, stop = mine[j]
                 idx = torch.arange(start, stop, dtype=torch.int64, device=dev)
@@ -306,50 +366,74 @@ class TeacherLogitCache:
                     img = view(images_u8_nhwc, idx)
                     if batch_hook is not None:
                         batch_hook("teacher_fill", j * world + rank, img, idx)
-                    out = teacher(img, return_features=True)[0].float()
+                    out, feats = teacher(img, return_features=True)
+                    out = out.float()
                 if out.shape != (stop - start, self.classes):
                     raise ValueError(f"TeacherLogitCache.fill: the teacher returned {tuple(out.shape)} for {stop - start} samples of "
                                      f"{self.classes} classes")
-                self.store(idx, out)
+                if self.features is None:
+                    feats = None
+                    self.store(idx, out)
+                else:
+                    feats = feats.float()
+                    if feats.shape != (stop - start, self.feature_dim):
+                        raise ValueError(f"TeacherLogitCache.fill: the teacher returned features {tuple(feats.shape)} for {stop - start} "
+                                         f"samples of feature_dim={self.feature_dim}; project inside the teacher module")
+                    self.store(idx, out, feats)
                 calls += 1
             if world > 1:
-                self._exchange(j, out, batch_size, rank, world, process_group)
+                self._exchange(j, out, feats, batch_size, rank, world, process_group)
         return calls
 
-    def _exchange(self, j, out, batch_size, rank, world, process_group):
+    def _exchange(self, j, out, feats, batch_size, rank, world, process_group):
         """round j: every rank hands in its block (padded to batch_size rows) and stores the others' at their rows"""
         import torch.distributed as dist
         dev = self.logits.device
         # gloo gathers host tensors; RCCL device tensors.  Either way the rows are copied, never summed.
         where = torch.device("cpu") if dist.get_backend(process_group) == "gloo" else dev
-        send = torch.full((batch_size, self.classes), float("nan"), dtype=torch.float32, device=where)
-        if out is not None:
-            send[:out.shape[0]].copy_(out)
-        recv = [torch.empty_like(send) for _ in range(world)]
-        dist.all_gather(recv, send, group=process_group)
+
+        def gather(block, width):
+            send = torch.full((batch_size, width), float("nan"), dtype=torch.float32, device=where)
+            if block is not None:
+                send[:block.shape[0]].copy_(block)
+            recv = [torch.empty_like(send) for _ in range(world)]
+            dist.all_gather(recv, send, group=process_group)
+            return recv
+
+        recv = gather(out, self.classes)
+        frecv = None if self.features is None else gather(feats, self.feature_dim)
         for r in range(world):
             start = (j * world + r) * batch_size
             stop = min(start + batch_size, self.n)
             if r != rank and start < stop:
-                self.store(torch.arange(start, stop, dtype=torch.int64, device=dev), recv[r][:stop - start].to(dev))
+                self.store(torch.arange(start, stop, dtype=torch.int64, device=dev), recv[r][:stop - start].to(dev),
+                           None if frecv is None else frecv[r][:stop - start].to(dev))
 
     def complete(self):
         """no NaN left: one host read"""
-        return not bool(torch.isnan(self.logits).any().item())
+        if self.features is None:
+            return not bool(torch.isnan(self.logits).any().item())
+        return not bool((torch.isnan(self.logits).any() | torch.isnan(self.features).any()).item())
 
     def save(self, path, **meta):
-        """torch.save of {"logits", "meta"}; meta: resize, crop, tag (what the rows were computed from), n and classes are the cache's"""
+        """torch.save of {"logits", "meta"}; meta: resize, crop, tag (what the rows were computed from), n and classes are the cache's.
+        A cache with feature_dim: {"logits", "features", "meta"}, the meta with a "feature_dim" field."""
         unknown = set(meta) - set(self.META[2:])
         if unknown:
             raise ValueError(f"TeacherLogitCache.save: unknown meta field(s) {sorted(unknown)} (resize, crop, tag)")
         m = {"n": self.n, "classes": self.classes, "resize": None, "crop": None, "tag": None}
         m.update(meta)
-        torch.save({"logits": self.logits.detach().cpu(), "meta": m}, path)
+        blob = {"logits": self.logits.detach().cpu(), "meta": m}
+        if self.features is not None:
+            m["feature_dim"] = self.feature_dim
+            blob["features"] = self.features.detach().cpu()
+        torch.save(blob, path)
 
     @classmethod
-    def load(cls, path, device, **expect):
+    def load(cls, path, device, feature_dim=None, **expect):
         """The cache saved at ``path`` on ``device``.  Every field of ``expect`` (n, classes, resize, crop, tag) must equal the file's;
-        a file with NaN rows is refused."""
+        a file with NaN rows is refused.  feature_dim: the features are asked for -- a file without them, or with another width, is
+        refused; None: a file's features, if it has any, are left out."""
         blob = torch.load(path, map_location="cpu", weights_only=True)
         logits, meta = blob["logits"], blob["meta"]
         for k, v in expect.items():
@@ -362,6 +446,23 @@ class TeacherLogitCache:
                              f"[{meta['n']}, {meta['classes']}]")
         if bool(torch.isnan(logits).any()):
             raise ValueError(f"TeacherLogitCache.load: {path} is incomplete ({int(torch.isnan(logits).any(dim=1).sum())} rows hold NaN)")
-        cache = cls(meta["n"], meta["classes"], device)
+        features = None
+        if feature_dim is not None:
+            features = blob.get("features")
+            if features is None or meta.get("feature_dim") is None:
+                raise ValueError(f"TeacherLogitCache.load: {path} holds no features (it was saved from a cache without feature_dim), "
+                                 f"feature_dim={feature_dim} was asked for")
+            if meta["feature_dim"] != int(feature_dim):
+                raise ValueError(f"TeacherLogitCache.load: {path} was saved with feature_dim={meta['feature_dim']!r}, expected "
+                                 f"feature_dim={int(feature_dim)!r}")
+            if features.dtype != torch.float32 or tuple(features.shape) != (meta["n"], meta["feature_dim"]):
+                raise ValueError(f"TeacherLogitCache.load: {path} holds features {features.dtype} {tuple(features.shape)}, its meta says "
+                                 f"fp32 [{meta['n']}, {meta['feature_dim']}]")
+            if bool(torch.isnan(features).any()):
+                raise ValueError(f"TeacherLogitCache.load: {path} is incomplete ({int(torch.isnan(features).any(dim=1).sum())} feature "
+                                 "rows hold NaN)")
+        cache = cls(meta["n"], meta["classes"], device, feature_dim=feature_dim)
         cache.logits.copy_(logits)
+        if features is not None:
+            cache.features.copy_(features)
         return cache

@@ -281,10 +281,16 @@ class GraphedDistillStep(GraphedTrainStep):
         step = GraphedDistillStep(model, optimizer, DistillationLoss(), None, None, teacher_logits_of(loader.index), loader=loader)
         loader.fetch(); loss = step(teacher_logits=teacher_logits_of(loader.index))
 
+    A criterion with a non-zero ``feature_loss_weight`` (the feature-matching term): the student's forward returns its features too and
+    the feature launch is captured with the rest.  Uncached, the step owns a second fixed-address buffer ``teacher_feat`` beside
+    ``teacher_logits`` -- pass ``example_teacher_feat`` and, per step, ``teacher_feat=`` -- filled in front of the replay; cached, the
+    term reads ``teacher_cache.features`` (a ``TeacherLogitCache(feature_dim=...)``) through the same index, so the loader-fed cached
+    step stays one replay.  ``step.feat`` is the captured unweighted term.
+
     Single process only: a graph-replayed data-parallel distillation rank is not built."""
 
     def __init__(self, model, optimizer, criterion, example_img, example_labels, example_teacher_logits=None, autocast_dtype=None, warmup=3,
-                 process_group=None, *, teacher_cache=None, example_index=None, loader=None):
+                 process_group=None, *, teacher_cache=None, example_index=None, loader=None, example_teacher_feat=None):
         import torch.distributed as dist
         if loader is not None:
             _check_loader("GraphedDistillStep", loader, example_img, example_labels)
@@ -298,6 +304,14 @@ class GraphedDistillStep(GraphedTrainStep):
         if dist.is_available() and dist.is_initialized() and dist.get_world_size(process_group) > 1:
             raise RuntimeError("GraphedDistillStep is the single-process step: GraphedDPStep is not built for distillation "
                                "(run the ranks of a torch.distributed job with the eager step)")
+        self.featured = getattr(criterion, "feature_loss_weight", 0.0) != 0.0
+        if self.featured and teacher_cache is None and example_teacher_feat is None:
+            raise ValueError(f"GraphedDistillStep: the criterion's feature_loss_weight={criterion.feature_loss_weight} needs "
+                             "example_teacher_feat beside example_teacher_logits")
+        if self.featured and teacher_cache is not None and getattr(teacher_cache, "features", None) is None:
+            raise ValueError(f"GraphedDistillStep: the criterion's feature_loss_weight={criterion.feature_loss_weight} needs a teacher "
+                             "cache with features (TeacherLogitCache(feature_dim=...))")
+        self.teacher_feat = example_teacher_feat.detach().clone() if self.featured and teacher_cache is None else None
         self.teacher_cache = teacher_cache
         if teacher_cache is None:
             self.teacher_logits, self.index = example_teacher_logits.detach().clone(), None
@@ -322,24 +336,35 @@ class GraphedDistillStep(GraphedTrainStep):
         _native.call("spv_seed_advance", self.seed_word.data_ptr(), torch.cuda.current_stream().cuda_stream)
         self.reducer.zero_grad()
         with torch.autocast("cuda", dtype=self.autocast_dtype, enabled=self.autocast_dtype is not None):
-            out = self.model(self.img)
+            out = self.model(self.img, return_features=True) if self.featured else self.model(self.img)
+        feats = {}
+        if self.featured:
+            out, student_feat = out
+            feats = dict(student_feat=student_feat, teacher_feat=self.teacher_feat if self.index is None else self.teacher_cache.features)
         if self.index is None:
-            loss = self.criterion(out, self.teacher_logits, self.labels)   # on the fp32 logits, outside autocast
+            loss = self.criterion(out, self.teacher_logits, self.labels, **feats)   # on the fp32 logits, outside autocast
         else:
-            loss = self.criterion(out, self.teacher_cache, self.labels, index=self.index)
+            loss = self.criterion(out, self.teacher_cache, self.labels, index=self.index, **feats)
         loss.backward(self._one)
         return loss, out
 
     def _warm(self, warmup):
         super()._warm(warmup)
         self.warm_soft, self.warm_ce = self.criterion.soft, self.criterion.ce
+        self.warm_feat = self.criterion.feat if self.featured else None
 
     def _build(self, warmup):
         super()._build(warmup)
         self.soft, self.ce = self.criterion.soft, self.criterion.ce
+        self.feat = self.criterion.feat if self.featured else None
 
-    def __call__(self, img=None, labels=None, teacher_logits=None, *, index=None):
+    def __call__(self, img=None, labels=None, teacher_logits=None, *, index=None, teacher_feat=None):
         if not self._closed:
+            if teacher_feat is not None:
+                if self.teacher_feat is None:
+                    raise ValueError("this step has no teacher feature buffer: its criterion's feature_loss_weight is 0, or it reads the "
+                                     "teacher cache's features through the index")
+                self.teacher_feat.copy_(teacher_feat, non_blocking=True)
             if teacher_logits is not None:
                 if self.teacher_logits is None:
                     raise ValueError("this step reads the teacher cache: pass index=, not teacher logits")

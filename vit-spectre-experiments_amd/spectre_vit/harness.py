@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import math
 import os
 import random
 import time
@@ -404,6 +405,8 @@ def _epoch_tail(run, epoch, steps, first_step, train, validate, batch_hook, log)
            "Accuracy/Validation": val_acc, "steps": steps, "val_samples": val_samples}
     if top5 is not None:
         rec["Accuracy/TrainTop5"] = top5
+    if lines and "Batch Loss/Feat" in lines[0]:   # the feature term's epoch mean, from the rows the other losses come from
+        rec["Loss/Feat"] = sum(line["Batch Loss/Feat"] for line in lines) / len(lines)
     if run.optimizer_name is not None:
         rec["Optimizer"] = run.optimizer_name
     if run.control:
@@ -611,17 +614,18 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
                        batch_hook, device_loader, log)
 
 
-def _teacher_cache(teacher, view, train_nhwc, classes, device, path, resize, crop, rank, world, batch_hook, batch_size):
+def _teacher_cache(teacher, view, train_nhwc, classes, device, path, resize, crop, rank, world, batch_hook, batch_size, feature_dim=None):
     """train_distill's cached teacher: loaded from `path` when that file exists and was saved for this set size, class count and view;
     filled otherwise (every rank its share of the rows, then exchanged) and saved by rank 0.  -> (cache, the "TeacherCache" record)"""
     from spectre_vit.distillation import TeacherLogitCache
     n = train_nhwc.shape[0]
     tag = type(teacher).__name__
     if path is not None and os.path.exists(path):
-        cache = TeacherLogitCache.load(path, device, n=n, classes=int(classes), resize=int(resize), crop=int(crop), tag=tag)
+        wanted = {} if feature_dim is None else {"feature_dim": feature_dim}   # a file without features is refused by name then
+        cache = TeacherLogitCache.load(path, device, n=n, classes=int(classes), resize=int(resize), crop=int(crop), tag=tag, **wanted)
         calls, loaded = 0, True
     else:
-        cache = TeacherLogitCache(n, classes, device)
+        cache = TeacherLogitCache(n, classes, device, **({} if feature_dim is None else {"feature_dim": feature_dim}))
         calls = cache.fill(teacher, view, train_nhwc, batch_size=batch_size, rank=rank, world=world, batch_hook=batch_hook)
         loaded = False
     if not cache.complete():
@@ -634,7 +638,9 @@ def _teacher_cache(teacher, view, train_nhwc, classes, device, path, resize, cro
 def _paired_distill_step(run, criterion, use_amp, graph, aug, view, teacher, cache, loader, train_nhwc, batch_hook):
     """train_distill()'s step: ONE index seen twice -- the student's view and, uncached, the teacher's view and forward (the "teacher"
     hook in front of it) -- then the fused DistillationLoss, eager or replayed by GraphedDistillStep (built on the first batch, whose
-    training step its warm-up is).  -> (loss, y_pred, img, label, soft, ce)"""
+    training step its warm-up is).  A criterion with a non-zero feature_loss_weight also gets both models' features (the cache's, when
+    cached).  -> (loss, y_pred, img, label, soft, ce[, feat])"""
+    featured = criterion.feature_loss_weight != 0.0
     loader_step = loader is not None and graph and loader.img is not None       # the graphed step reads the loader's buffers
     loader_in_graph = loader_step and cache is not None                         # ... and fetches them itself: a step is one replay
     autocast_dtype = torch.bfloat16 if use_amp else None
@@ -673,42 +679,49 @@ def _paired_distill_step(run, criterion, use_amp, graph, aug, view, teacher, cac
             if batch_hook is not None:
                 batch_hook("teacher", n, img_teacher, label)
             with torch.no_grad():   # train.py:326-327
-                teacher_logits, _ = teacher(img_teacher, return_features=True)
+                teacher_logits, teacher_feat = teacher(img_teacher, return_features=True)
             teacher_logits = teacher_logits.float()
         if not graph:
+            feats = {}
             with torch.autocast("cuda", dtype=torch.bfloat16, enabled=use_amp):
-                y_pred = run.model(img)
+                if featured:   # train.py:325
+                    y_pred, student_feat = run.model(img, return_features=True)
+                    feats = dict(student_feat=student_feat, teacher_feat=teacher_feat if cache is None else cache.features)
+                else:
+                    y_pred = run.model(img)
             if cache is None:
-                loss = criterion(y_pred.float(), teacher_logits, label.long())
+                loss = criterion(y_pred.float(), teacher_logits, label.long(), **feats)
             else:
-                loss = criterion(y_pred.float(), cache, label.long(), index=sel)
-            soft, ce = criterion.soft, criterion.ce
+                loss = criterion(y_pred.float(), cache, label.long(), index=sel, **feats)
+            terms = (criterion.soft, criterion.ce) + ((criterion.feat,) if featured else ())
             _eager_update(run, loss)
-            return loss, y_pred, img, label, soft, ce
+            return (loss, y_pred, img, label) + terms
         if gstep[0] is None:   # built on the first batch; its warm-up step WAS this batch's training step
             from spectre_vit.graph import GraphedDistillStep
+            fed = dict(example_teacher_feat=teacher_feat) if featured and cache is None else {}
             if loader_step:   # the batch (and, cached, its index) are the loader's buffers
-                teacher_args = dict(example_teacher_logits=teacher_logits) if cache is None else dict(teacher_cache=cache)
+                teacher_args = dict(example_teacher_logits=teacher_logits, **fed) if cache is None else dict(teacher_cache=cache)
                 g = GraphedDistillStep(run.model, run.optimizer, criterion, None, None, autocast_dtype=autocast_dtype, warmup=1,
                                        loader=loader, **teacher_args)
             else:
-                teacher_args = dict(example_teacher_logits=teacher_logits) if cache is None else dict(teacher_cache=cache, example_index=sel)
+                teacher_args = dict(example_teacher_logits=teacher_logits, **fed) if cache is None else dict(teacher_cache=cache, example_index=sel)
                 g = GraphedDistillStep(run.model, run.optimizer, criterion, img, label.long(), autocast_dtype=autocast_dtype, warmup=1,
                                        **teacher_args)
             gstep[0] = g
-            loss, soft, ce, y_pred = g.warm_loss, g.warm_soft, g.warm_ce, g.warm_out
+            loss, soft, ce, feat, y_pred = g.warm_loss, g.warm_soft, g.warm_ce, g.warm_feat, g.warm_out
         else:
             g = gstep[0]
+            fed = dict(teacher_feat=teacher_feat) if featured and cache is None else {}
             if loader_in_graph:
                 loss = g()   # ONE replay: fetch, forward, cached loss, backward, optimizer
             elif loader_step:
-                loss = g(teacher_logits=teacher_logits)
+                loss = g(teacher_logits=teacher_logits, **fed)
             else:
-                loss = g(img, label.long(), teacher_logits) if cache is None else g(img, label.long(), index=sel)
-            soft, ce, y_pred = g.soft, g.ce, g.out
+                loss = g(img, label.long(), teacher_logits, **fed) if cache is None else g(img, label.long(), index=sel)
+            soft, ce, feat, y_pred = g.soft, g.ce, g.feat, g.out
         if loader_in_graph:
             img, label = loader.img, loader.labels   # what the step just trained on
-        return loss, y_pred, img, label, soft, ce
+        return (loss, y_pred, img, label, soft, ce) + ((feat,) if featured else ())
     return _step(batches, run_step, gstep)
 
 
@@ -717,7 +730,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                   resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False,
                   lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False, ema_decay=None,
                   ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None, optimizer=None, momentum=0.9,
-                  nesterov=True, cache_teacher=False, teacher_cache_path=None):
+                  nesterov=True, feature_loss_weight=0.0, cache_teacher=False, teacher_cache_path=None):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -748,7 +761,16 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     host fetches, runs the view and the teacher, and replays a graph that reads the loader's buffers.  The global step, the
     augmentation's step and the loader's cursor stay equal.  batch_hook("train", step, img, label) is called AFTER the step with the
     step's buffers (valid until the next fetch); the "teacher" hook keeps its place in front of the teacher.  The sample order is the
-    loader's, not the host randperm's."""
+    loader's, not the host randperm's.
+    feature_loss_weight=W (0.0: off, and the record and the launches are those of a run without the argument): the feature-matching
+    term of train.py:306, 343-346 -- W * (1 - mean cos(student CLS features, teacher CLS features)) -- joins the loss
+    (DistillationLoss(feature_loss_weight=W): one more launch each way).  Both models are asked for their features (train.py:325-327);
+    teacher=None builds the SyntheticTeacher with the student's embed_dim as its feature width, a teacher of another width is refused
+    before the first step (project inside the teacher module).  With cache_teacher=True the cache keeps the teacher's features too
+    (TeacherLogitCache(feature_dim=...)) and the term reads them through the batch's index, so the graphed, cached, loader-fed step
+    stays one replay.  The epoch record gains "Loss/Feat" and the per-step lines "Batch Loss/Feat", from the same per-epoch device
+    buffer as the other three.  Not with device_meter=True (the meter's log row has no slot for a fourth term).  Eager, graph=True,
+    cache_teacher, device_loader, and as an eager data-parallel rank."""
     from spectre_vit import _native
     _check_device_meter(device_meter)
     _check_device_loader(device_loader)
@@ -764,6 +786,13 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                          f"crop={crop} (1 or 3 channels, img_size <= resize, 0 < crop <= resize, four taps inside the image)")
     if not (T > 0):
         raise ValueError(f"temperature T={T} must be positive")
+    if isinstance(feature_loss_weight, bool) or not isinstance(feature_loss_weight, (int, float)) \
+            or not math.isfinite(feature_loss_weight) or feature_loss_weight < 0:
+        raise ValueError(f"feature_loss_weight={feature_loss_weight!r} must be a finite number >= 0")
+    featured = feature_loss_weight != 0
+    if featured and device_meter:
+        raise ValueError(f"feature_loss_weight={feature_loss_weight} with device_meter=True: the meter's log row holds loss, soft and CE "
+                         "and has no slot for the feature term")
     run = _setup(c, mixer, "spectre", epochs, steps_per_epoch, batch_size, n_train, n_val, out_dir, graph, device_meter, optimizer_name, rule,
                  ema, dict(lr_schedule=lr_schedule, warmup_steps=warmup_steps, eta_min=eta_min, clip_grad_norm=clip_grad_norm,
                            skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps))
@@ -771,22 +800,31 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     mean, std = CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels]
     aug = TrainAugment(mean, std, seed=augment_seed(run.seed, run.rank)) if augment else None
     view = TeacherView(mean, std, resize=resize, crop=crop)
-    if teacher is None:
-        teacher = SyntheticTeacher(c.num_classes, 384, c.in_channels).to(run.device)
+    if teacher is None:   # with the feature term the stand-in's features have the student's width
+        teacher = SyntheticTeacher(c.num_classes, int(c.embed_dim) if featured else 384, c.in_channels).to(run.device)
     teacher.eval()
-    criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight, **({} if run.meter is None else {"meter": run.meter}))
+    criterion = DistillationLoss(T, soft_target_loss_weight, ce_loss_weight, **({} if run.meter is None else {"meter": run.meter}),
+                                 **({"feature_loss_weight": float(feature_loss_weight)} if featured else {}))
+    if featured:   # a teacher of another feature width is refused here, before the first step and before the cache's fill
+        with torch.no_grad():
+            probe = teacher(view(train_nhwc, torch.zeros(1, dtype=torch.int64, device=run.device)), return_features=True)[1]
+        if probe.dim() != 2 or probe.shape[1] != int(c.embed_dim):
+            raise ValueError(f"feature_loss_weight={feature_loss_weight}: the teacher's features {tuple(probe.shape)} and the student's "
+                             f"(width embed_dim={c.embed_dim}) differ in width; project inside the teacher module (there is no learned "
+                             "projector in this loss)")
     cache = None
     if cache_teacher:
         # filled in blocks of the training batch: the teacher then sees the batch shape it would see inside the epochs
         cache, cache_rec = _teacher_cache(teacher, view, train_nhwc, c.num_classes, run.device, teacher_cache_path, resize, crop, run.rank,
-                                          run.world, batch_hook, run.batch_size)
+                                          run.world, batch_hook, run.batch_size, int(c.embed_dim) if featured else None)
         cache_rec["seconds"] = time.perf_counter() - run.start
         if run.rank == 0:
             run.log_f.write(json.dumps({"TeacherCache": cache_rec}) + "\n")
             run.log_f.flush()
     loader = _resident_loader(run, train_nhwc, aug, False) if device_loader else None
     step = _paired_distill_step(run, criterion, use_amp, graph, aug, view, teacher, cache, loader, train_nhwc, batch_hook)
-    return _run_epochs(run, step, _TrainBooks(run, ("Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE"), block=True),
+    names = ("Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE") + (("Batch Loss/Feat",) if featured else ())
+    return _run_epochs(run, step, _TrainBooks(run, names, block=True),
                        _validator(run, graph_eval, use_amp, float_logits=True), epochs, batch_hook, device_loader, log)
 
 
@@ -812,6 +850,10 @@ def build_parser():
                          "by index (no teacher view and no teacher forward inside the epochs)")
     ap.add_argument("--teacher-cache", default=None, metavar="PATH",
                     help="--cache-teacher: load the logits from PATH when it exists and matches, save them there otherwise")
+    ap.add_argument("--feature-loss-weight", type=float, default=0.0, metavar="W",
+                    help="--distill-paired: add W * (1 - mean cosine of the student's and the teacher's CLS features), the reference's "
+                         "feature-matching term (train.py:343-346); with --cache-teacher the features are cached too; not with "
+                         "--device-meter")
     ap.add_argument("--graph-eval", action="store_true",
                     help="validate through a graph-replayed InferenceSession with on-device metrics (spectre_vit.inference)")
     ap.add_argument("--lr-schedule", default=None, choices=("cosine",),
@@ -852,7 +894,8 @@ def main(argv=None):
                   ema_decay=a.ema_decay, ema_warmup=a.ema_warmup, accumulate_steps=a.accumulate_steps, optimizer=a.optimizer,
                   momentum=a.momentum, nesterov=not a.no_nesterov)
     if a.distill_paired:
-        train_distill(a.config, augment=not a.no_augment, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache, **common)
+        train_distill(a.config, augment=not a.no_augment, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache,
+                      feature_loss_weight=a.feature_loss_weight, **common)
         return
     train(a.config, distill=a.distill, model=a.model, augment=a.augment, **common)
 

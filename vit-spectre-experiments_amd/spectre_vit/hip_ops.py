@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import collections
 import ctypes
+import math
 import os
 import warnings
 import weakref
@@ -1549,6 +1550,116 @@ def distill_loss_cached(student_logits, cache, index, labels, T=2.0, w_soft=0.25
     if meter is not None:
         return DistillLossIdxMeterFn.apply(student_logits, cache, index, labels, T, w_soft, w_ce, meter)
     return DistillLossIdxFn.apply(student_logits, cache, index, labels, T, w_soft, w_ce)
+
+
+_feature_workspaces = {}
+
+
+def _add_weighted(base, feat, w):
+    """base + w * feat as one launch (base None: w * feat)"""
+    if base is None:
+        return feat * w
+    if base.dim() != 0 or base.dtype != torch.float32 or base.device != feat.device:
+        raise ValueError(f"feature_cosine: base is an fp32 scalar tensor on the features' device, got {base.dtype} {tuple(base.shape)}")
+    return torch.add(base, feat, alpha=w)
+
+
+def _check_feature_weight(w):
+    w = float(w)
+    if not math.isfinite(w):
+        raise ValueError(f"feature_cosine: the weight w={w!r} is not finite")
+    return w
+
+
+class FeatureCosineFn(torch.autograd.Function):
+    """w * (1 - mean_r cos(s_r, t_r)) and the unweighted term (reference repl/train.py:306, 343-346: two F.normalize, nn.CosineSimilarity,
+    mean, 1 -): one launch forward, one backward.  Student features fp32 or bf16 [rows, width], teacher features fp32 or bf16 of the same
+    shape; gradient to the student only, in its dtype.  Returns (base + w * feat, feat) as fp32 device scalars, feat detached; base
+    (the loss the term is added to, a scalar tensor or None for 0) passes its gradient through untouched, so adding the term to a loss
+    costs one small launch forward and none backward."""
+
+    @staticmethod
+    def forward(ctx, student_feat, teacher_feat, w, base=None):
+        _require_gpu(student_feat, teacher_feat)
+        s, t = student_feat, teacher_feat
+        if (s.dim() != 2 or t.shape != s.shape or s.dtype not in (torch.float32, torch.bfloat16)
+                or t.dtype not in (torch.float32, torch.bfloat16) or s.shape[0] < 1 or s.shape[1] < 1):
+            raise ValueError("feature_cosine: fp32 or bf16 student and teacher features of one shape [rows, width] expected, got "
+                             f"{s.dtype} {tuple(s.shape)} and {t.dtype} {tuple(t.shape)}")
+        w = _check_feature_weight(w)
+        s, t = s.contiguous(), t.detach().contiguous()
+        rows, width = s.shape
+        stat = torch.empty((3, rows), dtype=torch.float32, device=s.device)
+        out = torch.empty((1,), dtype=torch.float32, device=s.device)
+        _native.call("spv_feature_cosine_fwd", _p(s), _p(t), _p(stat), _p(out),
+                     _p(_zero_workspace(_feature_workspaces, s.device, "spv_feature_cosine_workspace_floats")), rows, width, _dt(s), _dt(t),
+                     _stream())
+        ctx.save_for_backward(s, t, stat)
+        ctx.w = w
+        feat = out[0]
+        ctx.mark_non_differentiable(feat)
+        return _add_weighted(base, feat, w), feat
+
+    @staticmethod
+    def backward(ctx, go, _gfeat):
+        s, t, stat = ctx.saved_tensors
+        go = go.reshape(1).float().contiguous()
+        ds = torch.empty_like(s)
+        _native.call("spv_feature_cosine_bwd", _p(s), _p(t), _p(stat), _p(go), _p(ds), s.shape[0], s.shape[1], _dt(s), _dt(t), ctx.w, _stream())
+        return ds, None, None, go.reshape(()) if ctx.needs_input_grad[3] else None
+
+
+class FeatureCosineIdxFn(torch.autograd.Function):
+    """FeatureCosineFn with the teacher's rows read from the resident fp32 feature cache [n_cache, width] through the batch's index (int64
+    [rows]): the bits of FeatureCosineFn on cache[index], without the gather.  Cache and index are read by address -- a captured launch
+    follows whatever they hold at replay.  A row whose index lies outside the cache, or whose cache row was never filled (NaN), poisons
+    the term and gets a NaN gradient row."""
+
+    @staticmethod
+    def forward(ctx, student_feat, cache, index, w, base=None):
+        _require_gpu(student_feat, cache, index)
+        s = student_feat
+        if (s.dim() != 2 or s.dtype not in (torch.float32, torch.bfloat16) or cache.dim() != 2 or cache.dtype != torch.float32
+                or cache.shape[1] != s.shape[1] or cache.shape[0] < 1 or not cache.is_contiguous() or s.shape[0] < 1 or s.shape[1] < 1
+                or index.dtype != torch.int64 or index.shape != s.shape[:1]):
+            raise ValueError("feature_cosine_cached: fp32 or bf16 student features [rows, width], a contiguous fp32 cache [n, width] and an "
+                             f"int64 index [rows] expected, got {s.dtype} {tuple(s.shape)}, {cache.dtype} {tuple(cache.shape)}, "
+                             f"{index.dtype} {tuple(index.shape)}")
+        w = _check_feature_weight(w)
+        s, t, idx = s.contiguous(), cache.detach(), index.contiguous()
+        rows, width = s.shape
+        stat = torch.empty((3, rows), dtype=torch.float32, device=s.device)
+        out = torch.empty((1,), dtype=torch.float32, device=s.device)
+        _native.call("spv_feature_cosine_idx_fwd", _p(s), _p(t), _p(idx), _p(stat), _p(out),
+                     _p(_zero_workspace(_feature_workspaces, s.device, "spv_feature_cosine_workspace_floats")), rows, t.shape[0], width,
+                     _dt(s), _stream())
+        ctx.save_for_backward(s, stat)
+        ctx.resident = (t, idx)   # read by address again in the backward (see DistillLossIdxFn)
+        ctx.w = w
+        feat = out[0]
+        ctx.mark_non_differentiable(feat)
+        return _add_weighted(base, feat, w), feat
+
+    @staticmethod
+    def backward(ctx, go, _gfeat):
+        s, stat = ctx.saved_tensors
+        t, idx = ctx.resident
+        go = go.reshape(1).float().contiguous()
+        ds = torch.empty_like(s)
+        _native.call("spv_feature_cosine_idx_bwd", _p(s), _p(t), _p(idx), _p(stat), _p(go), _p(ds), s.shape[0], t.shape[0], s.shape[1], _dt(s),
+                     ctx.w, _stream())
+        return ds, None, None, None, go.reshape(()) if ctx.needs_input_grad[4] else None
+
+
+def feature_cosine(student_feat, teacher_feat, w=1.0, base=None):
+    """(base + w * feat, feat): feat = 1 - mean_r cos(student_feat[r], teacher_feat[r]); the first is differentiable in the student
+    features (and in base, a scalar loss tensor; None: 0)"""
+    return FeatureCosineFn.apply(student_feat, teacher_feat, w, base)
+
+
+def feature_cosine_cached(student_feat, cache, index, w=1.0, base=None):
+    """feature_cosine(student_feat, cache[index], w, base) without materialising cache[index]"""
+    return FeatureCosineIdxFn.apply(student_feat, cache, index, w, base)
 
 
 # ------------------------------------------------------------------------------------------------

@@ -36,6 +36,12 @@ _WORK_MODELS = {
     "spv_cross_entropy_meter_fwd": lambda i: ("cross_entropy_meter_fwd", i[0:2], F32, "hbm", i[0] * i[1] * 4.0),
     "spv_distill_loss_meter_fwd": lambda i: ("distill_loss_meter_fwd", i[0:2], F32, "hbm", i[0] * i[1] * 8.0),
     "spv_distill_loss_idx_meter_fwd": lambda i: ("distill_loss_idx_meter_fwd", (i[0], i[2]), F32, "hbm", i[0] * (i[2] * 8.0 + 8.0)),
+    # (rows, width, s_dtype, t_dtype) / (rows, n_cache, width, s_dtype): both feature matrices read once (forward), read again and the
+    # student's gradient written (backward); the cache is fp32, the three per-row stats and the index are a few words a row
+    "spv_feature_cosine_fwd": lambda i: ("feature_cosine_fwd", i[0:2], F32, "hbm", 1.0 * i[0] * i[1] * (_es(i[2]) + _es(i[3]))),
+    "spv_feature_cosine_bwd": lambda i: ("feature_cosine_bwd", i[0:2], F32, "hbm", 1.0 * i[0] * i[1] * (2 * _es(i[2]) + _es(i[3]))),
+    "spv_feature_cosine_idx_fwd": lambda i: ("feature_cosine_idx_fwd", (i[0], i[2]), F32, "hbm", 1.0 * i[0] * i[2] * (_es(i[3]) + 4)),
+    "spv_feature_cosine_idx_bwd": lambda i: ("feature_cosine_idx_bwd", (i[0], i[2]), F32, "hbm", 1.0 * i[0] * i[2] * (2 * _es(i[3]) + 4)),
     "spv_logit_cache_store": lambda i: ("logit_cache_store", (i[0], i[2]), F32, "hbm", i[0] * (i[2] * 8.0 + 8.0)),
     # (batch, n_src, chans, n, resize, crop, dtype): the uint8 images read, the cropped view written once
     "spv_teacher_view_u8": lambda i: ("teacher_view", (i[0], i[2], i[3], i[5]), i[6], "hbm",
