@@ -1055,6 +1055,32 @@ int spv_loader_fetch_augment_tiled(const unsigned char* src_nhwc, const void* la
                                    uint64_t loader_seed, int shuffle, int label_dtype, uint64_t augment_seed, void* workspace,
                                    size_t workspace_bytes, void* stream);
 
+/* ---- state snapshot: a run's device-resident state into one flat staging buffer, by ONE launch ----
+ * spv_snapshot_multi copies `bytes` bytes from src to dst for every job, bit for bit, walking a chunk table as spv_adamw_multi does:
+ * chunk c is bytes [chunk_off[c], min(chunk_off[c] + chunk_bytes, bytes)) of job chunk_job[c]; one 256-thread workgroup per chunk
+ * (grid = nchunks); a job of 0 bytes has no chunk.  jobs / chunk_job / chunk_off / chunk_sum / chunk_nonfinite are device pointers.
+ * Any byte count and any source alignment are taken: a chunk whose src and dst are both 16-byte aligned moves 16 bytes per lane and
+ * access, one whose two addresses are 4-byte aligned moves 4, any other moves single bytes; a job's last partial 16 bytes (or word) go
+ * bytewise.  Nothing outside [dst, dst + bytes) is written.  chunk_off entries and chunk_bytes are multiples of 16 (the host lays the
+ * slots out on 256-byte boundaries, so dst never lowers the access width).
+ *   chunk_sum[c]        the sum, mod 2^64, of the chunk's bytes read as little-endian 32-bit words counted from the JOB's start, the
+ *                       job's last partial word zero-padded.  A job's checksum is the sum of its chunks' sums mod 2^64: integer
+ *                       addition makes it independent of chunk_bytes and of any order.  The host folds; no atomics, a fixed layout.
+ *   chunk_nonfinite[c]  kind == 1: the whole fp32 words of the chunk whose exponent is all ones (inf, NaN); any other kind: 0.
+ * Refused on the host, before any launch: nchunks < 0, chunk_bytes not a positive multiple of 16, and with nchunks > 0 a null table or
+ * a null output.  nchunks == 0 launches nothing.  Allocates nothing and synchronises nothing: the call may be captured. */
+#define SPV_SNAPSHOT_RAW 0
+#define SPV_SNAPSHOT_FP32 1
+typedef struct spv_copy_job {
+    const void* src;
+    void* dst;
+    long long bytes;
+    int kind;       /* SPV_SNAPSHOT_RAW: raw bytes; SPV_SNAPSHOT_FP32: fp32 values, counted */
+    int reserved;
+} spv_copy_job;
+int spv_snapshot_multi(const spv_copy_job* jobs, const int* chunk_job, const long long* chunk_off, int nchunks, int chunk_bytes,
+                       unsigned long long* chunk_sum, int* chunk_nonfinite, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

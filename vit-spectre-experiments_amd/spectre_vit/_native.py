@@ -176,6 +176,7 @@ SIGNATURES = {
     "spv_loader_fetch_augment": [c_vp] * 10 + [c_i] * 8 + [c_u64, c_i, c_i, c_u64, c_vp],
     "spv_loader_augment_tiled_supported": [c_i, c_i, c_i],
     "spv_loader_fetch_augment_tiled": [c_vp] * 10 + [c_i] * 8 + [c_u64, c_i, c_i, c_u64, c_vp, ctypes.c_size_t, c_vp],
+    "spv_snapshot_multi": [c_vp, c_vp, c_vp, c_i, c_i, c_vp, c_vp, c_vp],
 }
 _RESTYPES = {"spv_last_error": ctypes.c_char_p, "spv_path_count": ctypes.c_longlong, "spv_rowop_partial_floats": c_i64, "spv_fnet_workspace_floats": c_i64,
              "spv_fnet_twiddle_floats": c_i64, "spv_tail_ln_partial_floats": c_i64, "spv_permut_table_words": c_i64, "spv_small_sl_partial_floats": c_i64,

@@ -90,7 +90,12 @@ class GraphedTrainStep:
     _dp = False
 
     def __init__(self, model, optimizer, criterion, example_img, example_labels, autocast_dtype=torch.bfloat16, warmup=3,
-                 return_features=False, process_group=None, force_collective=False, loader=None):
+                 return_features=False, process_group=None, force_collective=False, loader=None, seed_word=0, capture_rng_state=None):
+        """seed_word: the dropout seed word's initial value (a resumed run passes the saved word, so that its warm-up step draws the
+        masks the uninterrupted run's next replay draws).  capture_rng_state: torch's CPU generator state an earlier step object of
+        the same run was captured under (its ``capture_rng_state`` attribute): the by-value dropout seeds are drawn from that
+        generator and frozen in the graph, so a resumed run sets it in front of its warm-up step AND in front of its capture --
+        both then draw the seeds the interrupted run's graph holds (exact with warmup=1, the harness's value)."""
         if loader is not None:
             _check_loader(type(self).__name__, loader, example_img, example_labels)
         elif not example_img.is_cuda:
@@ -114,7 +119,12 @@ class GraphedTrainStep:
         self.reducer = GradReducer(model, always=True, process_group=process_group, overlap=not self._dp)
         if not self._dp and self.reducer.world > 1:
             raise RuntimeError("GraphedTrainStep is the single-process step; a rank of a torch.distributed job uses GraphedDPStep")
+        seed_word = int(seed_word) & (2 ** 64 - 1)
         self.seed_word = torch.zeros(1, dtype=torch.int64, device=dev)
+        if seed_word:   # (0: the launches of a step built without the keyword)
+            self.seed_word.copy_(torch.tensor([seed_word if seed_word < 2 ** 63 else seed_word - 2 ** 64], dtype=torch.int64))
+        self._resume_rng = capture_rng_state
+        self.capture_rng_state = None
         _claim_seed_word(self)
         self._closed = False
         self._one = torch.ones((), dtype=torch.float32, device=dev)
@@ -161,8 +171,14 @@ class GraphedTrainStep:
         finally:
             hip_ops.HOLD_UNDER_DP = prev
 
+    def _set_capture_rng(self):
+        """in front of the capture (and, resumed, of the warm-up): the generator state the graph's by-value seeds are drawn under"""
+        if self._resume_rng is not None:
+            torch.set_rng_state(self._resume_rng)
+
     def _warm(self, warmup):
         # warm-up on a side stream (allocator pools, lazily built tables, optimizer state), then capture
+        self._set_capture_rng()
         side = torch.cuda.Stream(device=self.img.device)
         side.wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(side), self._hold():
@@ -173,6 +189,8 @@ class GraphedTrainStep:
         # takes the last one's results from here instead of replaying that batch a second time
         self.warm_loss, self.warm_out = loss.detach(), out.detach()
         shadows.reset_shadow_cache()  # the weight casts must be recorded in the graph, not served from a cache
+        self._set_capture_rng()
+        self.capture_rng_state = torch.get_rng_state()   # what a checkpoint keeps of this capture (a host read of a host generator)
 
     def _build(self, warmup):
         self._warm(warmup)
@@ -290,7 +308,8 @@ class GraphedDistillStep(GraphedTrainStep):
     Single process only: a graph-replayed data-parallel distillation rank is not built."""
 
     def __init__(self, model, optimizer, criterion, example_img, example_labels, example_teacher_logits=None, autocast_dtype=None, warmup=3,
-                 process_group=None, *, teacher_cache=None, example_index=None, loader=None, example_teacher_feat=None):
+                 process_group=None, *, teacher_cache=None, example_index=None, loader=None, example_teacher_feat=None, seed_word=0,
+                 capture_rng_state=None):
         import torch.distributed as dist
         if loader is not None:
             _check_loader("GraphedDistillStep", loader, example_img, example_labels)
@@ -323,7 +342,7 @@ class GraphedDistillStep(GraphedTrainStep):
                                  f"{example_index.dtype} {tuple(example_index.shape)}")
             self.teacher_logits, self.index = None, example_index.detach().clone()
         super().__init__(model, optimizer, criterion, example_img, example_labels, autocast_dtype=autocast_dtype, warmup=warmup,
-                         process_group=process_group, loader=loader)
+                         process_group=process_group, loader=loader, seed_word=seed_word, capture_rng_state=capture_rng_state)
 
     @property
     def fetch_in_graph(self):

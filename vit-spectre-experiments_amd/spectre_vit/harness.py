@@ -306,7 +306,8 @@ def _setup(c, mixer, model_name, epochs, steps_per_epoch, batch_size, n_train, n
                            n_val=n_val, batch_size=batch_size, epoch_steps=epoch_steps, control=control, ema=ema, meter=meter,
                            optimizer_name=optimizer_name, optimizer=optimizer, reducer=reducer, out_dir=out_dir, log_f=log_f,
                            gen=torch.Generator().manual_seed(seed), global_step=0, history=[], best_acc=0.0, best_ema_acc=0.0,
-                           session=None, start=time.perf_counter())
+                           session=None, start=time.perf_counter(), start_epoch=0, elapsed=0.0, checkpoint_every=None, resume=None,
+                           fingerprint=None, snapshot=None, loader=None, step_resume={})
 
 
 def _optimizer_and_reducer(name, rule, model, c, lr, graph, control, ema):
@@ -340,7 +341,7 @@ def _eager_update(run, loss):
 def _step(batches, run_step, gstep):
     """a step object: batches() yields what the host knows of the next batch, run(batch, n) trains on it, close() closes the graphed
     step where one was built (gstep: a one-element list, filled on the first batch)"""
-    return SimpleNamespace(batches=batches, run=run_step, close=lambda: gstep[0] is not None and gstep[0].close())
+    return SimpleNamespace(batches=batches, run=run_step, close=lambda: gstep[0] is not None and gstep[0].close(), gstep=gstep)
 
 
 class _TrainBooks:
@@ -396,6 +397,110 @@ def _validator(run, graph_eval, amp, uint8=False, float_logits=False):
     return validate
 
 
+def _checkpoint_args(checkpoint_every, resume, out_dir, fingerprint):
+    """the harness's two checkpoint arguments -> (checkpoint_every, the loaded state to resume from or None).  Raises before any device
+    is touched: a bad argument, a data-parallel rank, a missing file, and whatever spectre_vit.checkpoint.load_train_state refuses --
+    a damaged file by its job's name, another run's file by the first differing key of the fingerprint."""
+    if checkpoint_every is not None:
+        if isinstance(checkpoint_every, float):
+            raise ValueError(f"checkpoint_every={checkpoint_every!r}: mid-epoch checkpoints are not built -- it counts whole epochs (an int >= 1)")
+        if isinstance(checkpoint_every, bool) or not isinstance(checkpoint_every, int) or checkpoint_every < 1:
+            raise ValueError(f"checkpoint_every={checkpoint_every!r} must be None or an int >= 1 (epochs)")
+    if resume is not None and resume is not True and not isinstance(resume, (str, os.PathLike)):
+        raise ValueError(f"resume={resume!r}: None, True (out_dir/train_state.pt) or a path")
+    if checkpoint_every is None and resume is None:
+        return None, None
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise ValueError("checkpoint_every / resume with world > 1 are not built: every rank's seed word and RNG states need a file of "
+                         "their own")
+    if resume is None:
+        return checkpoint_every, None
+    from spectre_vit import checkpoint
+    path = os.path.join(out_dir, checkpoint.FILE_NAME) if resume is True else os.fspath(resume)
+    if not os.path.exists(path):
+        raise ValueError(f"resume: no such file: {path}")
+    return checkpoint_every, checkpoint.load_train_state(path, fingerprint)
+
+
+def _fingerprint(entry, c, **args):
+    """what shapes a run's trajectory: the parsed config's fields and the arguments of train() / train_distill() that do (graph_eval,
+    device_meter, log, batch_hook and out_dir do not enter).  A resume is held to it key by key."""
+    fp = {"entry": entry, "world": int(os.environ.get("WORLD_SIZE", "1"))}
+    fp.update({f"config/{k}": v for k, v in sorted(vars(c).items())})
+    fp.update(args)
+    return fp
+
+
+def _state_blocks(run, step):
+    """the run's device-resident state as the named tensors of ONE snapshot launch -> (blocks, the names the non-finite gate watches):
+    every entry of model.state_dict() (the parameters gated), the optimizer's per-parameter state (the averages gated), control
+    block and accumulators, the loader's cursor block, the graphed step's seed word"""
+    from spectre_vit import checkpoint
+    blocks = [("model/" + k, v) for k, v in run.model.state_dict().items()]
+    gated = {"model/" + k for k, _ in run.model.named_parameters()}
+    opt = run.optimizer
+    optim_blocks = (opt.state_blocks() if hasattr(opt, "state_blocks") else checkpoint.optimizer_blocks(opt))[0]
+    blocks += optim_blocks
+    gated |= {name for name, _ in optim_blocks if name.endswith("/ema")}
+    if run.loader is not None:
+        blocks.append(("loader/cursor", run.loader._cursor))
+    gstep = getattr(step, "gstep", [None])[0]
+    if gstep is not None:
+        blocks.append(("step/seed_word", gstep.seed_word))
+    return blocks, gated
+
+
+def _take_checkpoint(run, step, epoch):
+    """after an epoch's tail: ONE launch takes the device's state in stream order (the snapshot is built at the first call, when every
+    block exists), the host's part is put together here, and the file is written behind the training's back"""
+    from spectre_vit import checkpoint
+    if run.snapshot is None:
+        def report(rec):   # a finished write, told at the next take() or at close()
+            run.log_f.write(json.dumps(rec) + "\n")
+            run.log_f.flush()
+        blocks, gated = _state_blocks(run, step)
+        run.snapshot = checkpoint.StateSnapshot(blocks, run.out_dir, gated=gated, report=report)
+    opt = run.optimizer
+    _, optim_host, aliases = opt.state_blocks() if hasattr(opt, "state_blocks") else checkpoint.optimizer_blocks(opt)
+    gstep = getattr(step, "gstep", [None])[0]
+    host = dict(fingerprint=run.fingerprint, epoch=epoch, global_step=run.global_step, history=[dict(r) for r in run.history],
+                best_acc=run.best_acc, best_ema_acc=run.best_ema_acc, elapsed=run.elapsed + time.perf_counter() - run.start,
+                param_groups=checkpoint.packed_param_groups(opt), optim_host=optim_host, optim_aliases=aliases,
+                loader=None if run.loader is None else run.loader.state_dict(),
+                capture_rng_state=None if gstep is None else gstep.capture_rng_state, rng=checkpoint.host_rng_state(run.gen))
+    run.snapshot.take(host, epoch)
+
+
+def _restore(run):
+    """a loaded train state into the run _setup built: model, optimizer (with the open window: control block and accumulators) and
+    loader; the loop's counters, history and best accuracies; the seed word and the capture's generator state for the step object the
+    first batch builds; the RNG states LAST, because set-up drew from them"""
+    from spectre_vit import checkpoint, shadows
+    host, tensors = run.resume["host"], run.resume["tensors"]
+    run.model.load_state_dict({k[len("model/"):]: v for k, v in tensors.items() if k.startswith("model/")})
+    shadows.invalidate_weight_shadows()
+    opt = run.optimizer
+    optim_sd = checkpoint.optimizer_state_dict(tensors, host)
+    if hasattr(opt, "load_train_state"):
+        accs = None
+        if opt.accumulate_steps is not None:
+            accs = [tensors[f"optim/accumulators/{gi}"] for gi in range(len(opt.param_groups))]
+        opt.load_train_state(optim_sd, tensors.get("optim/control_block"), accs)
+    else:
+        opt.load_state_dict(optim_sd)
+    if getattr(run, "loader", None) is not None:
+        cursor = int(tensors["loader/cursor"][0]) & (2 ** 64 - 1)
+        if cursor != host["loader"]["step"]:
+            raise ValueError(f"resume: the loader's saved cursor block is at step {cursor}, its host mirror at {host['loader']['step']}")
+        run.loader.load_state_dict(host["loader"])
+    if "step/seed_word" in tensors:
+        run.step_resume = dict(seed_word=int(tensors["step/seed_word"][0]) & (2 ** 64 - 1), capture_rng_state=host["capture_rng_state"])
+    run.global_step, run.start_epoch, run.elapsed = host["global_step"], host["epoch"], host["elapsed"]
+    run.history[:] = host["history"]
+    run.best_acc, run.best_ema_acc = host["best_acc"], host["best_ema_acc"]
+    checkpoint.set_host_rng_state(host["rng"], getattr(run, "gen", None))
+
+
 def _epoch_tail(run, epoch, steps, first_step, train, validate, batch_hook, log):
     """after an epoch's training: validation, the epoch record (with the averaged weights' second pass), rank 0's log lines -- the
     per-step ones, then the record -- and the two best checkpoints.  train: what _TrainBooks.read returned"""
@@ -434,32 +539,50 @@ def _run_epochs(run, step, books, validate, epochs, batch_hook, hook_after, log)
     """THE training loop.  Per step: the next batch from step.batches(); batch_hook("train", ...) in front of the step when the host
     knows the batch beforehand, or (hook_after: a resident loader feeds the step) after it with the buffers the step trained on;
     global_step counted between the two; step.run(batch, n) -> (loss, y_pred, img, label, *further loss terms); the books.  Per epoch
-    _epoch_tail; at the end the step and the session are closed and the "Training time" line is written.  -> (model, history)"""
-    for epoch in range(epochs):
-        run.model.train()
-        books.begin()
-        first_step, steps = run.global_step, 0
-        for batch in step.batches():
-            n = run.global_step
-            if batch_hook is not None and not hook_after:
-                batch_hook("train", n, batch[0], batch[1])
-            run.global_step += 1
-            loss, y_pred, img, label, *terms = step.run(batch, n)
-            books.add(steps, y_pred, label, loss, *terms)
-            if batch_hook is not None and hook_after:
-                batch_hook("train", n, img, label)
-            steps += 1
-            if steps >= run.epoch_steps:
-                break
-        train = books.read(steps)
-        run.model.eval()
-        _epoch_tail(run, epoch, steps, first_step, train, validate, batch_hook, log)
-    step.close()
-    if run.session is not None:
-        run.session.close()
-    if run.rank == 0:
-        run.log_f.write(json.dumps({"Training time": time.perf_counter() - run.start}) + "\n")
-        run.log_f.close()
+    _epoch_tail, then (checkpoint_every) the state's snapshot; at the end -- in a finally: a run that ends in an exception releases the
+    seed word and finishes a pending write too -- the step, the session, the snapshot's writer and the log are closed, the "Training
+    time" line written in front of that when the loop came through.  A run with a loaded state (resume) takes it in first and starts
+    at the saved epoch.  -> (model, history)"""
+    every = getattr(run, "checkpoint_every", None)
+    done = False
+    try:
+        if getattr(run, "resume", None) is not None:
+            _restore(run)
+        for epoch in range(getattr(run, "start_epoch", 0), epochs):
+            run.model.train()
+            books.begin()
+            first_step, steps = run.global_step, 0
+            for batch in step.batches():
+                n = run.global_step
+                if batch_hook is not None and not hook_after:
+                    batch_hook("train", n, batch[0], batch[1])
+                run.global_step += 1
+                loss, y_pred, img, label, *terms = step.run(batch, n)
+                books.add(steps, y_pred, label, loss, *terms)
+                if batch_hook is not None and hook_after:
+                    batch_hook("train", n, img, label)
+                steps += 1
+                if steps >= run.epoch_steps:
+                    break
+            train = books.read(steps)
+            run.model.eval()
+            _epoch_tail(run, epoch, steps, first_step, train, validate, batch_hook, log)
+            if every is not None and (epoch + 1) % every == 0 and run.rank == 0:
+                _take_checkpoint(run, step, epoch + 1)
+        done = True
+    finally:
+        try:
+            step.close()
+            if run.session is not None:
+                run.session.close()
+            if getattr(run, "snapshot", None) is not None:
+                run.snapshot.close()   # a pending write is finished, and logged, first
+        finally:
+            if run.rank == 0:
+                if done:
+                    elapsed = getattr(run, "elapsed", 0.0) + time.perf_counter() - run.start
+                    run.log_f.write(json.dumps({"Training time": elapsed}) + "\n")
+                run.log_f.close()
     return run.model, run.history
 
 
@@ -498,7 +621,7 @@ def _plain_step(run, criterion, use_amp, graph, uint8_input, aug, loader, train_
             cls = GraphedDPStep if run.world > 1 else GraphedTrainStep
             fed = dict(loader=loader) if loader_in_graph else {}
             gstep[0] = cls(run.model, run.optimizer, criterion, img, None if loader_in_graph else label.long(),
-                           autocast_dtype=torch.bfloat16 if use_amp else None, warmup=1, **fed)
+                           autocast_dtype=torch.bfloat16 if use_amp else None, warmup=1, **fed, **run.step_resume)
             loss, y_pred = gstep[0].warm_loss, gstep[0].warm_out   # the warm-up step WAS this batch's training step
         else:
             loss = gstep[0]() if loader_in_graph else gstep[0](img, label.long())   # loader_in_graph: ONE replay, fetch to optimizer
@@ -529,7 +652,7 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
           use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
           augment=False, batch_hook=None, graph_eval=False, lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None,
           skip_nonfinite=False, ema_decay=None, ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None,
-          optimizer=None, momentum=0.9, nesterov=True):
+          optimizer=None, momentum=0.9, nesterov=True, checkpoint_every=None, resume=None):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
@@ -580,7 +703,15 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     a by-value argument).
     The host then no longer knows a batch beforehand: batch_hook("train", step, img, label) is called AFTER the step, with the step's
     buffers (the loader's, or the augmented batch) -- valid until the next step overwrites them.  Validation is untouched.  The sample
-    ORDER differs from the host randperm's (same distribution, another stream): hence a flag and not the default."""
+    ORDER differs from the host randperm's (same distribution, another stream): hence a flag and not the default.
+    checkpoint_every=E: after every E-th epoch's tail the run's whole state -- model.state_dict(), the optimizer's moments, step count,
+    averages, control block and accumulators (an accumulation window may be open across the boundary), the loader's cursor, the graphed
+    step's seed word -- is taken on the device by ONE launch (spectre_vit.checkpoint.StateSnapshot) and written to
+    out_dir/train_state.pt behind the training's back, with the host's part: counters, history, best accuracies, RNG states.  A finished
+    write is logged as a {"Checkpoint": ...} line; a non-finite weight or average keeps the old file ({"CheckpointSkipped": ...}).
+    resume=True (out_dir/train_state.pt) or a path: the run is built as ever from the SAME arguments (the file's fingerprint is held
+    against them, a ValueError names the first differing key), then continues the saved one bit for bit from its saved epoch.
+    Single process only; model_best.pt / model_ema_best.pt stay what they are.  Left unsaid, nothing of a run changes."""
     _check_device_meter(device_meter, distill)
     _check_device_loader(device_loader, distill)
     if augment and (uint8_input or distill):
@@ -592,9 +723,17 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         raise ValueError("the SpectreBranch spectrum takes fp32 images: the uint8 NHWC input path is not built for it")
     if graph and distill:
         raise ValueError("graph=True replays the plain training step; the distillation step (teacher forward + KD loss) runs eagerly")
+    fingerprint = _fingerprint("train", c, mixer=mixer, model=model, batch_size=batch_size, n_train=n_train, n_val=n_val,
+                               steps_per_epoch=steps_per_epoch, epochs=epochs, use_amp=use_amp, graph=graph, augment=augment,
+                               uint8_input=uint8_input, device_loader=device_loader, optimizer=optimizer, momentum=momentum,
+                               nesterov=nesterov, lr_schedule=lr_schedule, warmup_steps=warmup_steps, eta_min=eta_min,
+                               clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps,
+                               ema_decay=ema_decay, ema_warmup=ema_warmup, distill=distill)
+    checkpoint_every, resume = _checkpoint_args(checkpoint_every, resume, out_dir, fingerprint)
     run = _setup(c, mixer, model, epochs, steps_per_epoch, batch_size, n_train, n_val, out_dir, graph, device_meter, optimizer_name, rule,
                  ema, dict(lr_schedule=lr_schedule, warmup_steps=warmup_steps, eta_min=eta_min, clip_grad_norm=clip_grad_norm,
                            skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps))
+    run.checkpoint_every, run.resume, run.fingerprint = checkpoint_every, resume, fingerprint
     amp = use_amp and not distill          # distill: use_amp False, train.py:299
     uint8 = uint8_input and not distill
     if distill:
@@ -608,7 +747,7 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         if augment:
             aug = TrainAugment(CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels], seed=augment_seed(run.seed, run.rank))
         if device_loader:
-            loader = _resident_loader(run, train_nhwc, aug, uint8)
+            run.loader = loader = _resident_loader(run, train_nhwc, aug, uint8)
         step = _plain_step(run, criterion, amp, graph, uint8, aug, loader, train_nhwc)
     return _run_epochs(run, step, _TrainBooks(run, ("Batch Loss/Train",), block=False), _validator(run, graph_eval, amp, uint8), epochs,
                        batch_hook, device_loader, log)
@@ -702,11 +841,11 @@ def _paired_distill_step(run, criterion, use_amp, graph, aug, view, teacher, cac
             if loader_step:   # the batch (and, cached, its index) are the loader's buffers
                 teacher_args = dict(example_teacher_logits=teacher_logits, **fed) if cache is None else dict(teacher_cache=cache)
                 g = GraphedDistillStep(run.model, run.optimizer, criterion, None, None, autocast_dtype=autocast_dtype, warmup=1,
-                                       loader=loader, **teacher_args)
+                                       loader=loader, **teacher_args, **run.step_resume)
             else:
                 teacher_args = dict(example_teacher_logits=teacher_logits, **fed) if cache is None else dict(teacher_cache=cache, example_index=sel)
                 g = GraphedDistillStep(run.model, run.optimizer, criterion, img, label.long(), autocast_dtype=autocast_dtype, warmup=1,
-                                       **teacher_args)
+                                       **teacher_args, **run.step_resume)
             gstep[0] = g
             loss, soft, ce, feat, y_pred = g.warm_loss, g.warm_soft, g.warm_ce, g.warm_feat, g.warm_out
         else:
@@ -730,7 +869,8 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                   resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False,
                   lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False, ema_decay=None,
                   ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None, optimizer=None, momentum=0.9,
-                  nesterov=True, feature_loss_weight=0.0, cache_teacher=False, teacher_cache_path=None):
+                  nesterov=True, feature_loss_weight=0.0, checkpoint_every=None, resume=None, cache_teacher=False,
+                  teacher_cache_path=None):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -770,7 +910,9 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     (TeacherLogitCache(feature_dim=...)) and the term reads them through the batch's index, so the graphed, cached, loader-fed step
     stays one replay.  The epoch record gains "Loss/Feat" and the per-step lines "Batch Loss/Feat", from the same per-epoch device
     buffer as the other three.  Not with device_meter=True (the meter's log row has no slot for a fourth term).  Eager, graph=True,
-    cache_teacher, device_loader, and as an eager data-parallel rank."""
+    cache_teacher, device_loader, and as an eager data-parallel rank.
+    checkpoint_every, resume: as in train().  The teacher, its view and its cache are no part of the state: a resumed run builds (or
+    loads) them as ever, before the saved state is taken in."""
     from spectre_vit import _native
     _check_device_meter(device_meter)
     _check_device_loader(device_loader)
@@ -793,9 +935,19 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     if featured and device_meter:
         raise ValueError(f"feature_loss_weight={feature_loss_weight} with device_meter=True: the meter's log row holds loss, soft and CE "
                          "and has no slot for the feature term")
+    fingerprint = _fingerprint("train_distill", c, mixer=mixer, batch_size=batch_size, n_train=n_train, n_val=n_val,
+                               steps_per_epoch=steps_per_epoch, epochs=epochs, use_amp=use_amp, graph=graph, augment=augment,
+                               device_loader=device_loader, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
+                               lr_schedule=lr_schedule, warmup_steps=warmup_steps, eta_min=eta_min, clip_grad_norm=clip_grad_norm,
+                               skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps, ema_decay=ema_decay,
+                               ema_warmup=ema_warmup, teacher=None if teacher is None else type(teacher).__name__, T=T,
+                               soft_target_loss_weight=soft_target_loss_weight, ce_loss_weight=ce_loss_weight, resize=resize, crop=crop,
+                               feature_loss_weight=feature_loss_weight, cache_teacher=cache_teacher)
+    checkpoint_every, resume = _checkpoint_args(checkpoint_every, resume, out_dir, fingerprint)
     run = _setup(c, mixer, "spectre", epochs, steps_per_epoch, batch_size, n_train, n_val, out_dir, graph, device_meter, optimizer_name, rule,
                  ema, dict(lr_schedule=lr_schedule, warmup_steps=warmup_steps, eta_min=eta_min, clip_grad_norm=clip_grad_norm,
                            skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps))
+    run.checkpoint_every, run.resume, run.fingerprint = checkpoint_every, resume, fingerprint
     train_nhwc = run.train_set.images.permute(0, 2, 3, 1).contiguous()
     mean, std = CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels]
     aug = TrainAugment(mean, std, seed=augment_seed(run.seed, run.rank)) if augment else None
@@ -821,7 +973,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
         if run.rank == 0:
             run.log_f.write(json.dumps({"TeacherCache": cache_rec}) + "\n")
             run.log_f.flush()
-    loader = _resident_loader(run, train_nhwc, aug, False) if device_loader else None
+    run.loader = loader = _resident_loader(run, train_nhwc, aug, False) if device_loader else None
     step = _paired_distill_step(run, criterion, use_amp, graph, aug, view, teacher, cache, loader, train_nhwc, batch_hook)
     names = ("Batch Loss/Train", "Batch Loss/Dist", "Batch Loss/CE") + (("Batch Loss/Feat",) if featured else ())
     return _run_epochs(run, step, _TrainBooks(run, names, block=True),
@@ -882,6 +1034,12 @@ def build_parser():
                          "host-issued work in front of it; also with --distill-paired (there one replay with --graph --cache-teacher; "
                          "uncached the teacher runs between the fetch and the replay); the sample order differs from the host "
                          "randperm's")
+    ap.add_argument("--checkpoint-every", type=int, default=None, metavar="E",
+                    help="after every E-th epoch take the run's whole state on the GPU in one launch and write OUT/train_state.pt behind "
+                         "the training's back (spectre_vit.checkpoint); single process")
+    ap.add_argument("--resume", nargs="?", const=True, default=None, metavar="PATH",
+                    help="continue the run saved in PATH (left out: OUT/train_state.pt) bit for bit; every other argument as in the "
+                         "saved run")
     ap.add_argument("--out", default="runs/spectre_vit")
     return ap
 
@@ -892,7 +1050,7 @@ def main(argv=None):
                   graph_eval=a.graph_eval, device_meter=a.device_meter, device_loader=a.device_loader, lr_schedule=a.lr_schedule,
                   warmup_steps=a.warmup_steps, eta_min=a.eta_min, clip_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite,
                   ema_decay=a.ema_decay, ema_warmup=a.ema_warmup, accumulate_steps=a.accumulate_steps, optimizer=a.optimizer,
-                  momentum=a.momentum, nesterov=not a.no_nesterov)
+                  momentum=a.momentum, nesterov=not a.no_nesterov, checkpoint_every=a.checkpoint_every, resume=a.resume)
     if a.distill_paired:
         train_distill(a.config, augment=not a.no_augment, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache,
                       feature_loss_weight=a.feature_loss_weight, **common)

@@ -165,6 +165,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
         self._ctl = None
         self._ctl_ws = None
         self._ctl_counts = (0, 0)   # (schedule step, skipped steps) a freshly built block starts from
+        self._ctl_raw = None        # ... or the 64 raw bytes of a saved block (load_train_state), micro-step included
         self._acc = {}  # gradient accumulation: group index -> dict(sizes, flat, views), one allocation per group, made once
 
     def _table(self, gi, ps):
@@ -285,10 +286,55 @@ class _FusedOptimizer(torch.optim.Optimizer):
         if self.step_control:   # the control block is rebuilt by the next step(), from the loaded counters
             sc = state_dict.get("step_control") or {}
             self._ctl_counts = (int(sc.get("schedule_step", 0)), int(sc.get("skipped_steps", 0)))
-            self._ctl = self._ctl_ws = None
+            self._ctl = self._ctl_ws = self._ctl_raw = None
             if self.accumulate_steps is not None and int(sc.get("micro_step", 0)) != 0:
                 warnings.warn(f"{self._who}.load_state_dict: the state was saved {int(sc['micro_step'])} micro-step(s) into an accumulation "
                               "window; the accumulators are not checkpointed, so the window restarts at micro-step 0", stacklevel=2)
+
+    def state_blocks(self):
+        """the optimizer's device-resident state as named tensors -- the tensors themselves, at the addresses the launches use --
+        for a spectre_vit.checkpoint.StateSnapshot: every per-parameter entry as "optim/<index>/<key>" in state_dict()'s numbering
+        (moments, ``ema``, the step count: one tensor per group, named once), with step control the raw 64-byte control block as
+        "optim/control_block", with accumulate_steps every group's accumulators as "optim/accumulators/<group>" (the flat allocation,
+        slot padding included).  Reads nothing from the device.  After the first step(): the moments, the step count and the
+        control block are made there.  -> (blocks, host_state, aliases) as spectre_vit.checkpoint.optimizer_blocks"""
+        from spectre_vit.checkpoint import optimizer_blocks
+        blocks, host_state, aliases = optimizer_blocks(self)
+        if self.step_control:
+            if self._ctl is None:
+                raise RuntimeError(f"{self._who}.state_blocks(): the control block is built by the first step()")
+            blocks.append(("optim/control_block", self._ctl))
+        if self.accumulate_steps is not None:
+            for gi in range(len(self.param_groups)):
+                self._accumulators(gi)
+                blocks.append((f"optim/accumulators/{gi}", self._acc[gi]["flat"]))
+        return blocks, host_state, aliases
+
+    def load_train_state(self, state_dict, control_block=None, accumulators=None):
+        """load_state_dict(state_dict) plus what a checkpoint of a RUNNING window needs (spectre_vit.checkpoint): control_block, the 64
+        raw bytes state_blocks() saved -- the schedule count, the skipped count and the micro-step of the open window, with the last
+        boundary's rate and norm -- and accumulators, one flat fp32 tensor per parameter group, copied bit for bit into this
+        optimizer's.  The window then continues where it was saved: no warning, nothing lost."""
+        with warnings.catch_warnings():
+            warnings.simplefilter("ignore")   # (the open window is restored below)
+            self.load_state_dict(state_dict)
+        if self.step_control and control_block is not None:
+            raw = bytes(control_block.cpu().contiguous().view(torch.uint8).numpy().tobytes()) if isinstance(control_block, torch.Tensor) \
+                else bytes(control_block)
+            if len(raw) != struct.calcsize(_CTL_FMT):
+                raise ValueError(f"{self._who}.load_train_state: the control block is {struct.calcsize(_CTL_FMT)} bytes, got {len(raw)}")
+            c = dict(zip(_CTL_FIELDS, struct.unpack(_CTL_FMT, raw)))
+            self._ctl_counts, self._ctl_raw = (c["sched_step"], c["skipped"]), raw
+        if self.accumulate_steps is not None and accumulators is not None:
+            if len(accumulators) != len(self.param_groups):
+                raise ValueError(f"{self._who}.load_train_state: {len(accumulators)} accumulator blocks for {len(self.param_groups)} groups")
+            for gi, saved in enumerate(accumulators):
+                self._accumulators(gi)
+                flat = self._acc[gi]["flat"]
+                if saved.numel() != flat.numel() or saved.dtype != flat.dtype:
+                    raise ValueError(f"{self._who}.load_train_state: group {gi}'s accumulators hold {flat.numel()} fp32 values here, "
+                                     f"{saved.numel()} {saved.dtype} in the saved state")
+                flat.copy_(saved.reshape(-1))
 
     def state_dict(self):
         """torch's layout; with step control on, one more top-level entry carries the schedule count and the skipped count, so that a
@@ -405,7 +451,7 @@ class _FusedOptimizer(torch.optim.Optimizer):
     def control_block_bytes(self):
         """the 64 raw bytes of the control block: the device's, or (before the first step) the ones it will start from"""
         if self._ctl is None:
-            return struct.pack(_CTL_FMT, 1.0, 0.0, 1.0, 1, 0.0, *self._ctl_counts, 0)
+            return self._ctl_raw or struct.pack(_CTL_FMT, 1.0, 0.0, 1.0, 1, 0.0, *self._ctl_counts, 0)
         return self._ctl.cpu().numpy().tobytes()
 
     def _control_workspace(self, active):
