@@ -1081,6 +1081,27 @@ typedef struct spv_copy_job {
 int spv_snapshot_multi(const spv_copy_job* jobs, const int* chunk_job, const long long* chunk_off, int nchunks, int chunk_bytes,
                        unsigned long long* chunk_sum, int* chunk_nonfinite, void* stream);
 
+/* ---- dataset ingest: a dataset file's pixel payload into the resident set, by ONE launch per uploaded chunk ----
+ * src [n][c][h][w] (SPV_DATASET_PLANAR, the CIFAR / MNIST files) or [n][h][w][c] (SPV_DATASET_INTERLEAVED); dst = the other layout,
+ * NULL: statistics only.  labels (SPV_LOADER_LABEL_U8 or SPV_LOADER_LABEL_I64 by label_dtype, nullable) feed the histogram.  stats
+ * (uint64, spv_dataset_stats_words(c, classes) words, 8-byte aligned, ADDED to: the caller zeroes it once and may call per chunk):
+ *   [0, c) sum of x per channel, [c, 2c) sum of x^2, [2c] pixels counted per channel, [2c+1] labels outside [0, classes),
+ *   [2c+2, 2c+2+classes) label histogram.  All integer, so the result does not depend on the order of the adds.
+ * c in {1, 3}, h, w in 1..512, 0 <= n < 2^31, 0 <= classes <= 2^24; n == 0 launches nothing.  Every byte offset is 64-bit.  src, dst
+ * and labels may have ANY alignment: a workgroup stages its unit (a group of whole images of together <= 8192 pixels, or a tile of 8192
+ * pixels of a larger image) in LDS at offsets congruent to the global addresses mod 16, moves 16 bytes per lane and access where a
+ * run's addresses allow and single bytes at its head and tail, and int64 labels are read bytewise.  Nothing outside
+ * [dst, dst + n c h w) is written.  A unit's sums are 32-bit (8192 x 255^2 < 2^32); a workgroup (1024 at the most, each walking
+ * every 1024th unit) keeps 64-bit totals over its units and, for classes <= 1024, its label histogram in LDS, and adds them to
+ * `stats` once at its end: one 64-bit atomic add per statistic and per class it met (above 1024 classes: one per label).  With c == 1 the two layouts are the same bytes and the call copies.
+ * Refused on the host, before any launch: a shape, n, src_layout, label_dtype or classes outside the above, a null or misaligned
+ * stats, with n > 0 a null src, and a dst whose bytes overlap src's.  Allocates nothing and synchronises nothing. */
+#define SPV_DATASET_PLANAR 0
+#define SPV_DATASET_INTERLEAVED 1
+int     spv_dataset_ingest(const uint8_t* src, uint8_t* dst, const void* labels, int label_dtype, uint64_t* stats, int64_t n, int c,
+                           int h, int w, int src_layout, int classes, void* stream);
+int64_t spv_dataset_stats_words(int c, int classes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -177,13 +177,16 @@ SIGNATURES = {
     "spv_loader_augment_tiled_supported": [c_i, c_i, c_i],
     "spv_loader_fetch_augment_tiled": [c_vp] * 10 + [c_i] * 8 + [c_u64, c_i, c_i, c_u64, c_vp, ctypes.c_size_t, c_vp],
     "spv_snapshot_multi": [c_vp, c_vp, c_vp, c_i, c_i, c_vp, c_vp, c_vp],
+    "spv_dataset_ingest": [c_vp, c_vp, c_vp, c_i, c_vp, c_i64, c_i, c_i, c_i, c_i, c_i, c_vp],
+    "spv_dataset_stats_words": [c_i, c_i],
 }
 _RESTYPES = {"spv_last_error": ctypes.c_char_p, "spv_path_count": ctypes.c_longlong, "spv_rowop_partial_floats": c_i64, "spv_fnet_workspace_floats": c_i64,
              "spv_fnet_twiddle_floats": c_i64, "spv_tail_ln_partial_floats": c_i64, "spv_permut_table_words": c_i64, "spv_small_sl_partial_floats": c_i64,
              "spv_cross_entropy_workspace_floats": c_i64, "spv_distill_loss_workspace_floats": c_i64,
              "spv_eval_head_stats_words": c_i64, "spv_augment_tiled_ws_bytes": ctypes.c_size_t, "spv_train_meter_words": c_i64,
              "spv_cross_entropy_meter_workspace_floats": c_i64, "spv_distill_loss_meter_workspace_floats": c_i64,
-             "spv_loader_cursor_bytes": c_i64, "spv_hadamard_workspace_floats": c_i64, "spv_feature_cosine_workspace_floats": c_i64}
+             "spv_loader_cursor_bytes": c_i64, "spv_hadamard_workspace_floats": c_i64, "spv_feature_cosine_workspace_floats": c_i64,
+             "spv_dataset_stats_words": c_i64}
 _NO_STATUS = set(_RESTYPES) | {"spv_hadamard_path", "spv_hadamard_ln_supported", "spv_hadamard_cls_supported", "spv_version", "spv_fnet_ln_supported", "spv_fnet_cls_supported", "spv_tail_ln_supported", "spv_tail_up_supported", "spv_small_sl_supported", "spv_tail_bwd_parts", "spv_embed_bwd_groups", "spv_haar_ln_supported", "spv_permut_pool_supported", "spv_spectrum_floats", "spv_augment_supported", "spv_loader_augment_supported", "spv_loader_augment_tiled_supported", "spv_augment_plan", "spv_teacher_view_supported", "spv_token_embed_supported"}
 
 class FoldJob(ctypes.Structure):

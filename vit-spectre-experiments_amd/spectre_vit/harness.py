@@ -2,7 +2,8 @@
 
 Same loop structure (train.py:207-295 classification, :298-361 distillation): seeds, model from a parsed config,
 AdamW(betas, lr, weight_decay), autocast, per-epoch eval, accuracy bookkeeping on device, best-validation
-``state_dict`` checkpoint.  What differs: synthetic CIFAR-shaped data resident on the GPU (no torchvision / network),
+``state_dict`` checkpoint.  What differs: the data resident on the GPU -- synthetic CIFAR-shaped sets by default, or, ``data_root=`` /
+``--data-root``, the dataset files the reference's ``./data`` holds, read by spectre_vit.datasets (no torchvision / network) --,
 bf16 autocast (no GradScaler needed), the training transform chain of train.py:100-115 as an on-GPU kernel pair (``--augment``,
 spectre_vit.augment) instead of PIL on loader workers, scalars to a JSON-lines file instead of TensorBoard, optional data parallelism
 (one process per GPU, RCCL all-reduce through spectre_vit.dp.GradReducer), and a synthetic frozen teacher for the
@@ -32,6 +33,7 @@ from torch import nn, optim
 
 from spectre_vit.augment import TrainAugment
 from spectre_vit.configs.parser import parse_config
+from spectre_vit.datasets import ResidentSet
 from spectre_vit.distillation import DistillationLoss, SyntheticTeacher, TeacherView, distillation_loss
 from spectre_vit.dp import GradReducer, broadcast_module
 from spectre_vit.loss import CrossEntropyLoss
@@ -75,7 +77,7 @@ def build_model(c, mixer="permut", device="cuda", model="spectre"):
                       dropout=c.dropout, activation=c.activation, mixer=mixer).to(device)
 
 
-class SyntheticCifar:
+class SyntheticCifar(ResidentSet):
     """class-conditional uint8 images resident in HBM: a fixed random template per class plus noise, so a model can
     actually learn something; normalised like train.py:109-112 when a batch is drawn."""
 
@@ -88,26 +90,7 @@ class SyntheticCifar:
         self.labels = self.labels.to(torch.uint8 if c.num_classes <= 256 else torch.int64).to(device)  # uint8 as train.py:218
         self.mean = torch.tensor(CIFAR_MEAN[:c.in_channels], device=device).view(1, -1, 1, 1)
         self.std = torch.tensor(CIFAR_STD[:c.in_channels], device=device).view(1, -1, 1, 1)
-
-    def index_batches(self, batch_size, shuffle, generator=None, rank=0, world=1, drop_last=True):
-        """the row indices (int64, on the set's device) of every batch of one pass, in the order `batches` draws them"""
-        n = self.images.shape[0]
-        idx = torch.randperm(n, generator=generator) if shuffle else torch.arange(n)
-        idx = idx[rank::world].to(self.images.device)
-        stop = idx.numel() - batch_size + 1 if drop_last else idx.numel()
-        for i in range(0, stop, batch_size):
-            yield idx[i:i + batch_size]
-
-    def batches(self, batch_size, shuffle, generator=None, rank=0, world=1, raw_uint8=False, drop_last=True):
-        """raw_uint8: yield the uint8 NHWC batch itself; the model's patch gather normalises it.
-        drop_last=False (validation): the short tail batch is yielded too, so every sample of the rank's shard is seen
-        (the reference's DataLoader default, train.py:151-155)."""
-        for sel in self.index_batches(batch_size, shuffle, generator, rank, world, drop_last):
-            if raw_uint8:
-                yield self.images[sel].permute(0, 2, 3, 1).contiguous(), self.labels[sel]
-                continue
-            img = (self.images[sel].float() / 255.0 - self.mean) / self.std
-            yield img, self.labels[sel]
+        self.mean_values, self.std_values = CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels]
 
 
 def _step_control_args(lr_schedule, warmup_steps, eta_min, clip_grad_norm, skip_nonfinite, total_steps, accumulate_steps=None):
@@ -273,8 +256,52 @@ def _eval_session(model, n_val, val_batch, rank, world, autocast_dtype, uint8):
                             input="uint8" if uint8 else "float")
 
 
+class _Unsaid(int):
+    """n_train / n_val left unsaid: the synthetic sets' sizes as ever (it IS that int), the whole split with data_root"""
+
+
+_UNSAID_TRAIN, _UNSAID_VAL = _Unsaid(4096), _Unsaid(1024)
+
+
+def _data_args(c, config_path, data_root, dataset, normalize, n_train, n_val):
+    """the harness's data arguments -> (the two host-side FileDatasets' record or None, n_train, n_val, the fingerprint's further
+    keys).  Without data_root: the synthetic sets of 4096 / 1024 samples unless a number is said, and nothing more.  With it the files
+    are read and checked here, on the host: n_train / n_val left unsaid (or None) are the whole split, a number is the limit.  Raises
+    before any device is touched."""
+    if data_root is None:
+        if dataset is not None or normalize is not None:
+            raise ValueError("dataset / normalize describe the files under data_root: they need data_root")
+        n_train, n_val = (4096 if n_train is None else n_train), (1024 if n_val is None else n_val)
+        return None, int(n_train) if isinstance(n_train, _Unsaid) else n_train, int(n_val) if isinstance(n_val, _Unsaid) else n_val, {}
+    n_train, n_val = (None if isinstance(n, _Unsaid) else n for n in (n_train, n_val))
+    from spectre_vit import datasets
+    if dataset is None:
+        dataset = datasets.dataset_of_config(config_path)
+    norm = datasets.resolve_normalize(dataset, normalize)
+    sets = []
+    for split, limit, what in (("train", n_train, "n_train"), ("test", n_val, "n_val")):
+        if limit is not None and (isinstance(limit, bool) or not isinstance(limit, int) or limit < 1):
+            raise ValueError(f"{what}={limit!r} must be None (the whole {split} split) or an int >= 1")
+        try:
+            ds = datasets.FileDataset(data_root, dataset, split, None, norm, limit)
+        except ValueError as e:
+            raise ValueError(f"{what}: {e}") if limit is not None and "is above the" in str(e) else e
+        if (ds.channels, ds.height, ds.width) != (c.in_channels, c.img_size, c.img_size):
+            raise ValueError(f"{ds.root} ({dataset}, {split}) holds {ds.channels} x {ds.height} x {ds.width} images, the config "
+                             f"in_channels={c.in_channels}, img_size={c.img_size}")
+        if ds.num_classes > c.num_classes:
+            raise ValueError(f"{ds.root} ({dataset}, {split}) has {ds.num_classes} classes, the config num_classes={c.num_classes}")
+        ds.num_classes = int(c.num_classes)   # the model's: the label dtype and the histogram's width (MNIST's configs keep 100)
+        sets.append(ds)
+    train_set, val_set = sets
+    plain_norm = norm if isinstance(norm, str) else [list(norm[0]), list(norm[1])]
+    data = SimpleNamespace(train=train_set, val=val_set, name=dataset, root=train_set.root, normalize=norm,
+                           digest=f"{train_set.digest}-{val_set.digest}")
+    return data, len(train_set), len(val_set), dict(dataset=dataset, dataset_digest=data.digest, normalize=plain_norm)
+
+
 def _setup(c, mixer, model_name, epochs, steps_per_epoch, batch_size, n_train, n_val, out_dir, graph, device_meter, optimizer_name, rule,
-           ema, control_args):
+           ema, control_args, data=None):
     """what every run has before its first batch, from a parsed config and the arguments train() and train_distill() share -> the run's
     record: rank / world / device, seed, lr, the model (built under the seed, broadcast), the two sets, batch_size, epoch_steps (the
     loader steps of one epoch), the step control / meter / optimizer / reducer, the open scalars.jsonl (rank 0), the shuffle generator,
@@ -293,8 +320,20 @@ def _setup(c, mixer, model_name, epochs, steps_per_epoch, batch_size, n_train, n
     model = build_model(c, mixer, device, model_name)
     broadcast_module(model)
     batch_size = batch_size or c.batch_size
-    train_set = SyntheticCifar(n_train, c, device, seed=seed)
-    val_set = SyntheticCifar(n_val, c, device, seed=seed + 1)
+    dataset = None
+    if data is None:
+        train_set = SyntheticCifar(n_train, c, device, seed=seed)
+        val_set = SyntheticCifar(n_val, c, device, seed=seed + 1)
+    else:   # the files were read and checked on the host (_data_args); a measured normalisation is the train split's for both
+        train_set = data.train.upload(device)
+        val_set = data.val.upload(device, measured_from=train_set)
+        dataset = {"name": data.name, "root": data.root, "n_train": n_train, "n_val": n_val, "digest": data.digest,
+                   "mean": list(train_set.mean_values), "std": list(train_set.std_values)}
+        if hasattr(model, "modules"):   # uint8 input: the model's patch gather normalises with the set's values
+            from spectre_vit.hip_ops import PixelNorm
+            for m in model.modules():
+                if hasattr(m, "pixel_norm"):
+                    m.pixel_norm = PixelNorm(train_set.mean_values, train_set.std_values)
     per_pass = (n_train // world) // batch_size
     epoch_steps = min(per_pass, steps_per_epoch) if steps_per_epoch else per_pass
     control = _step_control_args(total_steps=epoch_steps * epochs, **control_args)
@@ -307,7 +346,7 @@ def _setup(c, mixer, model_name, epochs, steps_per_epoch, batch_size, n_train, n
                            optimizer_name=optimizer_name, optimizer=optimizer, reducer=reducer, out_dir=out_dir, log_f=log_f,
                            gen=torch.Generator().manual_seed(seed), global_step=0, history=[], best_acc=0.0, best_ema_acc=0.0,
                            session=None, start=time.perf_counter(), start_epoch=0, elapsed=0.0, checkpoint_every=None, resume=None,
-                           fingerprint=None, snapshot=None, loader=None, step_resume={})
+                           fingerprint=None, snapshot=None, loader=None, step_resume={}, dataset=dataset)
 
 
 def _optimizer_and_reducer(name, rule, model, c, lr, graph, control, ema):
@@ -326,7 +365,8 @@ def _resident_loader(run, train_nhwc, aug, uint8_input):
     from spectre_vit.data import ResidentLoader
     H, W, C = train_nhwc.shape[1:]
     output = _loader_output(aug is not None, uint8_input, C, H, W)
-    return ResidentLoader(train_nhwc, run.train_set.labels, run.batch_size, CIFAR_MEAN[:C], CIFAR_STD[:C], seed=loader_seed(run.seed),
+    mean, std = run.train_set.mean_values, run.train_set.std_values
+    return ResidentLoader(train_nhwc, run.train_set.labels, run.batch_size, mean, std, seed=loader_seed(run.seed),
                           rank=run.rank, world=run.world, steps_per_epoch=run.epoch_steps, output=output,
                           augment=aug if output.startswith("augment") else None)
 
@@ -519,6 +559,8 @@ def _epoch_tail(run, epoch, steps, first_step, train, validate, batch_hook, log)
     if run.ema:   # the same pass on the averaged weights (a session keeps its own copies: leaving the context does not disturb it)
         with run.optimizer.ema_weights():
             rec["Accuracy/ValidationEMA"], rec["Loss/ValidationEMA"], _ = validate(None)
+    if getattr(run, "dataset", None) is not None:   # a run from files (data_root) says which
+        rec["Dataset"] = dict(run.dataset)
     run.history.append(rec)
     if run.rank != 0:
         return
@@ -648,11 +690,12 @@ def _early_distill_step(run, teacher):
     return _step(batches, run_step, [None])
 
 
-def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
+def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=_UNSAID_TRAIN, n_val=_UNSAID_VAL,
           use_amp=True, distill=False, out_dir="runs/spectre_vit", log=print, uint8_input=False, graph=False, model="spectre",
           augment=False, batch_hook=None, graph_eval=False, lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None,
           skip_nonfinite=False, ema_decay=None, ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None,
-          optimizer=None, momentum=0.9, nesterov=True, checkpoint_every=None, resume=None):
+          optimizer=None, momentum=0.9, nesterov=True, checkpoint_every=None, resume=None, data_root=None, dataset=None,
+          normalize=None):
     """graph=True (not with distill): the training step -- zero_grad, forward, loss, backward, AdamW -- is replayed from HIP graphs
     (spectre_vit.graph: one graph in a single process; as a rank of a torch.distributed job two graphs around ONE all-reduce of the
     flat gradient buffer) with the one-launch optimizer (spectre_vit.optim.FusedAdamW: torch.optim.AdamW's rule and state layout).
@@ -711,7 +754,19 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
     write is logged as a {"Checkpoint": ...} line; a non-finite weight or average keeps the old file ({"CheckpointSkipped": ...}).
     resume=True (out_dir/train_state.pt) or a path: the run is built as ever from the SAME arguments (the file's fingerprint is held
     against them, a ValueError names the first differing key), then continues the saved one bit for bit from its saved epoch.
-    Single process only; model_best.pt / model_ema_best.pt stay what they are.  Left unsaid, nothing of a run changes."""
+    Single process only; model_best.pt / model_ema_best.pt stay what they are.  Left unsaid, nothing of a run changes.
+    data_root=DIR (with dataset, normalize): train on the dataset files under DIR instead of the synthetic sets
+    (spectre_vit.datasets.FileDataset: the CIFAR-100 / CIFAR-10 pickles, MNIST idx files or {train,test}.npz that torchvision or the
+    user left there; no download).  dataset=None follows the config's file name (*cifar100*, *mnist*; anything else is refused),
+    validation is the test split, n_train / n_val left unsaid are the whole splits and a number keeps the first samples (above the
+    split's size it is refused).  The files are read and checked on the host before a device is touched: the config's img_size and
+    in_channels must be the files', its num_classes at least the data's.  normalize: "reference" (the reference's constants:
+    cifar100, mnist), "measured" (the train split's mean and population std from the ingest kernel's integer sums; the test split
+    takes them too) or a (mean, std) pair; None is "reference" where there is one, else "measured".  The set's mean / std replace the
+    CIFAR constants in the loader, the augmentation, validation and the model's uint8 patch gather, its resident NHWC copy serves
+    where one was formed per run, and every path above works from files.  The fingerprint gains the dataset's name, digest and
+    normalisation (a synthetic run's checkpoint, or other files', is refused by the first differing key) and the epoch record
+    "Dataset": {name, root, n_train, n_val, digest, mean, std}.  Without data_root n_train / n_val are 4096 / 1024 as ever."""
     _check_device_meter(device_meter, distill)
     _check_device_loader(device_loader, distill)
     if augment and (uint8_input or distill):
@@ -723,16 +778,17 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         raise ValueError("the SpectreBranch spectrum takes fp32 images: the uint8 NHWC input path is not built for it")
     if graph and distill:
         raise ValueError("graph=True replays the plain training step; the distillation step (teacher forward + KD loss) runs eagerly")
+    data, n_train, n_val, data_fp = _data_args(c, config_path, data_root, dataset, normalize, n_train, n_val)
     fingerprint = _fingerprint("train", c, mixer=mixer, model=model, batch_size=batch_size, n_train=n_train, n_val=n_val,
                                steps_per_epoch=steps_per_epoch, epochs=epochs, use_amp=use_amp, graph=graph, augment=augment,
                                uint8_input=uint8_input, device_loader=device_loader, optimizer=optimizer, momentum=momentum,
                                nesterov=nesterov, lr_schedule=lr_schedule, warmup_steps=warmup_steps, eta_min=eta_min,
                                clip_grad_norm=clip_grad_norm, skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps,
-                               ema_decay=ema_decay, ema_warmup=ema_warmup, distill=distill)
+                               ema_decay=ema_decay, ema_warmup=ema_warmup, distill=distill, **data_fp)
     checkpoint_every, resume = _checkpoint_args(checkpoint_every, resume, out_dir, fingerprint)
     run = _setup(c, mixer, model, epochs, steps_per_epoch, batch_size, n_train, n_val, out_dir, graph, device_meter, optimizer_name, rule,
                  ema, dict(lr_schedule=lr_schedule, warmup_steps=warmup_steps, eta_min=eta_min, clip_grad_norm=clip_grad_norm,
-                           skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps))
+                           skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps), data)
     run.checkpoint_every, run.resume, run.fingerprint = checkpoint_every, resume, fingerprint
     amp = use_amp and not distill          # distill: use_amp False, train.py:299
     uint8 = uint8_input and not distill
@@ -743,9 +799,9 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
         criterion = CrossEntropyLoss(**({} if run.meter is None else {"meter": run.meter}))
         aug = train_nhwc = loader = None
         if augment or device_loader:
-            train_nhwc = run.train_set.images.permute(0, 2, 3, 1).contiguous()
+            train_nhwc = run.train_set.nhwc()
         if augment:
-            aug = TrainAugment(CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels], seed=augment_seed(run.seed, run.rank))
+            aug = TrainAugment(run.train_set.mean_values, run.train_set.std_values, seed=augment_seed(run.seed, run.rank))
         if device_loader:
             run.loader = loader = _resident_loader(run, train_nhwc, aug, uint8)
         step = _plain_step(run, criterion, amp, graph, uint8, aug, loader, train_nhwc)
@@ -753,12 +809,13 @@ def train(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_siz
                        batch_hook, device_loader, log)
 
 
-def _teacher_cache(teacher, view, train_nhwc, classes, device, path, resize, crop, rank, world, batch_hook, batch_size, feature_dim=None):
+def _teacher_cache(teacher, view, train_nhwc, classes, device, path, resize, crop, rank, world, batch_hook, batch_size, feature_dim=None,
+                   data_tag=None):
     """train_distill's cached teacher: loaded from `path` when that file exists and was saved for this set size, class count and view;
     filled otherwise (every rank its share of the rows, then exchanged) and saved by rank 0.  -> (cache, the "TeacherCache" record)"""
     from spectre_vit.distillation import TeacherLogitCache
     n = train_nhwc.shape[0]
-    tag = type(teacher).__name__
+    tag = type(teacher).__name__ if data_tag is None else f"{type(teacher).__name__}@{data_tag}"   # files: the set's name and digest
     if path is not None and os.path.exists(path):
         wanted = {} if feature_dim is None else {"feature_dim": feature_dim}   # a file without features is refused by name then
         cache = TeacherLogitCache.load(path, device, n=n, classes=int(classes), resize=int(resize), crop=int(crop), tag=tag, **wanted)
@@ -864,13 +921,13 @@ def _paired_distill_step(run, criterion, use_amp, graph, aug, view, teacher, cac
     return _step(batches, run_step, gstep)
 
 
-def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=4096, n_val=1024,
+def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, batch_size=None, n_train=_UNSAID_TRAIN, n_val=_UNSAID_VAL,
                   use_amp=False, graph=False, augment=True, teacher=None, T=2.0, soft_target_loss_weight=0.25, ce_loss_weight=0.75,
                   resize=256, crop=224, out_dir="runs/spectre_vit_distill", log=print, batch_hook=None, graph_eval=False,
                   lr_schedule=None, warmup_steps=0, eta_min=0.0, clip_grad_norm=None, skip_nonfinite=False, ema_decay=None,
                   ema_warmup=False, device_meter=False, device_loader=False, accumulate_steps=None, optimizer=None, momentum=0.9,
-                  nesterov=True, feature_loss_weight=0.0, checkpoint_every=None, resume=None, cache_teacher=False,
-                  teacher_cache_path=None):
+                  nesterov=True, feature_loss_weight=0.0, checkpoint_every=None, resume=None, data_root=None, dataset=None,
+                  normalize=None, cache_teacher=False, teacher_cache_path=None):
     """The distillation loop of reference train.py:298-396 with its data contract (DistillationDatasetCls, train.py:139-141): every
     batch is ONE shuffled index into the resident uint8 set, seen twice -- the student's view through the training transform chain
     (spectre_vit.augment.TrainAugment; augment=False: ToTensor + Normalize) and the teacher's view through
@@ -912,7 +969,9 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     buffer as the other three.  Not with device_meter=True (the meter's log row has no slot for a fourth term).  Eager, graph=True,
     cache_teacher, device_loader, and as an eager data-parallel rank.
     checkpoint_every, resume: as in train().  The teacher, its view and its cache are no part of the state: a resumed run builds (or
-    loads) them as ever, before the saved state is taken in."""
+    loads) them as ever, before the saved state is taken in.
+    data_root, dataset, normalize: as in train().  The teacher's view takes the set's resident NHWC copy and its mean / std, and the
+    teacher cache's meta tag carries the dataset's name and digest: a cache filled from other data is refused by name."""
     from spectre_vit import _native
     _check_device_meter(device_meter)
     _check_device_loader(device_loader)
@@ -935,6 +994,7 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     if featured and device_meter:
         raise ValueError(f"feature_loss_weight={feature_loss_weight} with device_meter=True: the meter's log row holds loss, soft and CE "
                          "and has no slot for the feature term")
+    data, n_train, n_val, data_fp = _data_args(c, config_path, data_root, dataset, normalize, n_train, n_val)
     fingerprint = _fingerprint("train_distill", c, mixer=mixer, batch_size=batch_size, n_train=n_train, n_val=n_val,
                                steps_per_epoch=steps_per_epoch, epochs=epochs, use_amp=use_amp, graph=graph, augment=augment,
                                device_loader=device_loader, optimizer=optimizer, momentum=momentum, nesterov=nesterov,
@@ -942,14 +1002,14 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
                                skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps, ema_decay=ema_decay,
                                ema_warmup=ema_warmup, teacher=None if teacher is None else type(teacher).__name__, T=T,
                                soft_target_loss_weight=soft_target_loss_weight, ce_loss_weight=ce_loss_weight, resize=resize, crop=crop,
-                               feature_loss_weight=feature_loss_weight, cache_teacher=cache_teacher)
+                               feature_loss_weight=feature_loss_weight, cache_teacher=cache_teacher, **data_fp)
     checkpoint_every, resume = _checkpoint_args(checkpoint_every, resume, out_dir, fingerprint)
     run = _setup(c, mixer, "spectre", epochs, steps_per_epoch, batch_size, n_train, n_val, out_dir, graph, device_meter, optimizer_name, rule,
                  ema, dict(lr_schedule=lr_schedule, warmup_steps=warmup_steps, eta_min=eta_min, clip_grad_norm=clip_grad_norm,
-                           skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps))
+                           skip_nonfinite=skip_nonfinite, accumulate_steps=accumulate_steps), data)
     run.checkpoint_every, run.resume, run.fingerprint = checkpoint_every, resume, fingerprint
-    train_nhwc = run.train_set.images.permute(0, 2, 3, 1).contiguous()
-    mean, std = CIFAR_MEAN[:c.in_channels], CIFAR_STD[:c.in_channels]
+    train_nhwc = run.train_set.nhwc()
+    mean, std = run.train_set.mean_values, run.train_set.std_values
     aug = TrainAugment(mean, std, seed=augment_seed(run.seed, run.rank)) if augment else None
     view = TeacherView(mean, std, resize=resize, crop=crop)
     if teacher is None:   # with the feature term the stand-in's features have the student's width
@@ -968,7 +1028,8 @@ def train_distill(config_path, mixer="permut", epochs=1, steps_per_epoch=None, b
     if cache_teacher:
         # filled in blocks of the training batch: the teacher then sees the batch shape it would see inside the epochs
         cache, cache_rec = _teacher_cache(teacher, view, train_nhwc, c.num_classes, run.device, teacher_cache_path, resize, crop, run.rank,
-                                          run.world, batch_hook, run.batch_size, int(c.embed_dim) if featured else None)
+                                          run.world, batch_hook, run.batch_size, int(c.embed_dim) if featured else None,
+                                          None if data is None else f"{data.name}:{data.train.digest}")
         cache_rec["seconds"] = time.perf_counter() - run.start
         if run.rank == 0:
             run.log_f.write(json.dumps({"TeacherCache": cache_rec}) + "\n")
@@ -1040,6 +1101,13 @@ def build_parser():
     ap.add_argument("--resume", nargs="?", const=True, default=None, metavar="PATH",
                     help="continue the run saved in PATH (left out: OUT/train_state.pt) bit for bit; every other argument as in the "
                          "saved run")
+    ap.add_argument("--data-root", default=None, metavar="DIR",
+                    help="train on the dataset files under DIR (what torchvision leaves in ./data: cifar-100-python/, "
+                         "cifar-10-batches-py/, MNIST/raw/, or {train,test}.npz) instead of the synthetic set; validation is the test split")
+    ap.add_argument("--dataset", default=None, choices=("cifar100", "cifar10", "mnist", "npz"),
+                    help="--data-root: the files' format; left out it follows the config's file name (*cifar100*, *mnist*)")
+    ap.add_argument("--normalize", default=None, choices=("reference", "measured"),
+                    help="--data-root: the reference's constants (cifar100, mnist) or the train split's measured mean and std")
     ap.add_argument("--out", default="runs/spectre_vit")
     return ap
 
@@ -1050,7 +1118,8 @@ def main(argv=None):
                   graph_eval=a.graph_eval, device_meter=a.device_meter, device_loader=a.device_loader, lr_schedule=a.lr_schedule,
                   warmup_steps=a.warmup_steps, eta_min=a.eta_min, clip_grad_norm=a.clip_grad_norm, skip_nonfinite=a.skip_nonfinite,
                   ema_decay=a.ema_decay, ema_warmup=a.ema_warmup, accumulate_steps=a.accumulate_steps, optimizer=a.optimizer,
-                  momentum=a.momentum, nesterov=not a.no_nesterov, checkpoint_every=a.checkpoint_every, resume=a.resume)
+                  momentum=a.momentum, nesterov=not a.no_nesterov, checkpoint_every=a.checkpoint_every, resume=a.resume,
+                  data_root=a.data_root, dataset=a.dataset, normalize=a.normalize)
     if a.distill_paired:
         train_distill(a.config, augment=not a.no_augment, cache_teacher=a.cache_teacher, teacher_cache_path=a.teacher_cache,
                       feature_loss_weight=a.feature_loss_weight, **common)

@@ -303,7 +303,7 @@ class InferenceSession:
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
-# python -m spectre_vit.inference: score the harness's synthetic validation set with a checkpoint
+# python -m spectre_vit.inference: score the harness's synthetic validation set, or a split of dataset files, with a checkpoint
 # ---------------------------------------------------------------------------------------------------------------------------------
 def build_parser():
     import argparse
@@ -315,19 +315,38 @@ def build_parser():
     ap.add_argument("--batch", type=int, default=512)
     ap.add_argument("--n", type=int, default=10000)
     ap.add_argument("--no-amp", action="store_true", help="fp32 kernels instead of bf16 autocast")
+    ap.add_argument("--data-root", default=None, metavar="DIR",
+                    help="score the dataset files under DIR (spectre_vit.datasets) instead of the synthetic set; --n is then ignored")
+    ap.add_argument("--dataset", default=None, choices=("cifar100", "cifar10", "mnist", "npz"),
+                    help="--data-root: the files' format; left out it follows the config's file name")
+    ap.add_argument("--split", default="test", choices=("train", "test"), help="--data-root: the split that is scored")
     return ap
 
 
-def score(config_path, checkpoint, mixer="permut", model="spectre", batch=512, n=10000, use_amp=True):
+def score(config_path, checkpoint, mixer="permut", model="spectre", batch=512, n=10000, use_amp=True, data_root=None, dataset=None,
+          split="test", normalize=None):
+    """data_root: the split of the dataset files under it (spectre_vit.datasets.FileDataset; dataset left out follows the config's file
+    name, normalize as there) is scored, every sample, the ragged last batch included; n is then the split's size"""
     import time
 
     from spectre_vit.configs.parser import parse_config
     from spectre_vit.harness import SyntheticCifar, build_model
     c = parse_config(config_path)
+    files = None
+    if data_root is not None:   # read and checked on the host, before a device is touched
+        from spectre_vit import datasets
+        files = datasets.FileDataset(data_root, dataset or datasets.dataset_of_config(config_path), split, None, normalize)
+        if (files.channels, files.height, files.width) != (c.in_channels, c.img_size, c.img_size) or files.num_classes > c.num_classes:
+            raise ValueError(f"{files.root} ({files.dataset}, {split}) holds {files.channels} x {files.height} x {files.width} images of "
+                             f"{files.num_classes} classes, the config in_channels={c.in_channels}, img_size={c.img_size}, "
+                             f"num_classes={c.num_classes}")
+        files.num_classes, n = int(c.num_classes), len(files)
+    elif dataset is not None or normalize is not None:
+        raise ValueError("dataset / normalize describe the files under data_root: they need data_root")
     device = torch.device("cuda", torch.cuda.current_device())
     net = build_model(c, mixer, device, model)
     net.load_state_dict(torch.load(checkpoint, map_location=device), strict=True)
-    val_set = SyntheticCifar(n, c, device, seed=getattr(c, "random_seed", 42) + 1)
+    val_set = files.upload(device) if files is not None else SyntheticCifar(n, c, device, seed=getattr(c, "random_seed", 42) + 1)
     with InferenceSession(net, batch_sizes=eval_buckets(n, batch), autocast_dtype=torch.bfloat16 if use_amp else None) as s:
         def one_pass():
             s.reset_stats()
@@ -346,7 +365,7 @@ def score(config_path, checkpoint, mixer="permut", model="spectre", batch=512, n
 def main(argv=None):
     import json
     a = build_parser().parse_args(argv)
-    print(json.dumps(score(a.config, a.checkpoint, a.mixer, a.model, a.batch, a.n, not a.no_amp)))
+    print(json.dumps(score(a.config, a.checkpoint, a.mixer, a.model, a.batch, a.n, not a.no_amp, a.data_root, a.dataset, a.split)))
 
 
 if __name__ == "__main__":

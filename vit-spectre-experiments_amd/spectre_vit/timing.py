@@ -124,6 +124,8 @@ _WORK_MODELS = {
     # the same integers: as above, and the image read a second time by the contrast mean's pre-pass (its partial sums are a few floats)
     "spv_loader_fetch_augment_tiled": lambda i: ("loader_fetch_augment_tiled", i[1:5], F32, "hbm",
                                                  i[1] * (16.0 + (8 if i[9] else 1) + 64.0 + i[2] * i[3] * i[4] * 6)),
+    # (label dtype, n, chans, height, width, layout, classes): the payload read and -- unless dst is NULL (pointer 1) -- written once
+    "spv_dataset_ingest": lambda i: ("dataset_ingest", i[1:5], F32, "hbm", 1.0 * i[1] * i[2] * i[3] * i[4] * (1 if (i[-2] >> 1) & 1 else 2)),
     "spv_cast": lambda i: ("cast", i[2:3], i[1], "hbm", 1.0 * i[2] * (_es(i[0]) + _es(i[1]))),
 }
 
