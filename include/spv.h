@@ -594,6 +594,41 @@ int spv_hadamard_cls_fwd(const void* x, const float* gamma, const float* beta, v
 int spv_hadamard_cls_bwd(const void* g1, const float* m0, const float* mean, const float* rstd, const float* gamma, void* dx,
                          float* partials, float scale, int batch, int tokens, int dim, int dtype, void* stream);
 
+/* ---- learnable global filter along the token axis --------------------------------------
+ * For x (batch, tokens, dim) and K = tokens / 2 + 1:
+ *   X = rfft(x, dim=1, norm="ortho");  y = irfft(X * W, n=tokens, dim=1, norm="ortho")
+ * W = `filter` read as (K, dim) complex: fp32 (K, dim, 2), real part first.  irfft ignores the imaginary part of the DC bin and, when
+ * tokens is even, of the Nyquist bin: the kernels read those entries as 0 and their gradient is exactly +0.  fp32 and bf16 x / y;
+ * filter, tables, gradients of the filter and all arithmetic fp32.  Any tokens in 1..2730, any dim >= 1, any element alignment.
+ *   fast         bf16, dim % 64 == 0, tokens <= 80: both token-axis products on the MFMA against DFT tables split into hi + lo bf16, the
+ *                spectrum on chip as hi + lo bf16; one workgroup per (sample, 64 columns), x read once and y written once in 16-byte
+ *                pieces.  x, y (dy, dx) and tables must be 16-byte aligned, else the call is refused.
+ *   generic      everything else: one workgroup per (sample, block of up to 64 columns), fp32 direct sums, the spectrum in LDS.  Any
+ *                alignment of the element type.
+ * spv_gfilter_path: which kernel serves a shape, or why it is refused (the host-pure selector of csrc/spv_gfilter_core.h, which the
+ * entry points switch on); `aligned`: the pointers above sit on 16 bytes.
+ *   tables     spv_gfilter_table_floats(tokens) floats, filled once per token count by spv_gfilter_make_tables.
+ *   workspace  spv_gfilter_workspace_floats floats of fp32 scratch (0 for both paths: NULL is accepted).
+ *   bwd        from x and dy alone (X is recomputed): dx = irfft(rfft(dy) * conj(W_eff)) and dfilter [K][dim][2] =
+ *              c_k * sum_b conj(X) G, c_k = 1 at the DC / Nyquist bins, else 2.  A workgroup sums over the samples it owns into one of
+ *              min(batch, 32) fp32 slabs (`partials`, spv_gfilter_partial_floats floats), folded in the fixed order of every other
+ *              fold of the library: no atomics, equal bits from equal inputs. */
+#define SPV_GFILTER_FAST 1
+#define SPV_GFILTER_GENERIC 2
+#define SPV_GFILTER_REFUSE_EMPTY (-1)       /* tokens < 1 or dim < 1 */
+#define SPV_GFILTER_REFUSE_DTYPE (-2)       /* neither SPV_F32 nor SPV_BF16 */
+#define SPV_GFILTER_REFUSE_ALIGN (-4)       /* a shape of the fast window with a pointer off 16-byte alignment */
+#define SPV_GFILTER_REFUSE_TOKENS (-3)      /* tokens > 2730: the table and one column of the backward no longer fit 64 KiB of LDS */
+int spv_gfilter_path(int dtype, int tokens, int dim, int aligned);
+int64_t spv_gfilter_table_floats(int tokens);
+int spv_gfilter_make_tables(float* tables, int tokens, void* stream);
+int64_t spv_gfilter_workspace_floats(int batch, int tokens, int dim);
+int64_t spv_gfilter_partial_floats(int batch, int tokens, int dim);
+int spv_gfilter_fwd(const void* x, const float* filter, void* y, const float* tables, int batch, int tokens, int dim, int dtype,
+                    float* workspace, void* stream);
+int spv_gfilter_bwd(const void* x, const void* dy, const float* filter, void* dx, float* dfilter, const float* tables, float* partials,
+                    int batch, int tokens, int dim, int dtype, float* workspace, void* stream);
+
 /* ---- patch embedding ---------------------------------------------------------------------------
  * tokens[b,0,:] = cls + pos[0]; tokens[b,1+n,:] = W_full . patch(b,n) + bias + pos[1+n]
  * where patch(b,n) is the (c,p,q)-ordered P x P pixel block.  With W_full = conv weight this is

@@ -135,6 +135,13 @@ SIGNATURES = {
     "spv_hadamard_cls_supported": [c_i, c_i, c_i],
     "spv_hadamard_cls_fwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_i, c_i, c_i, c_i, c_vp],
     "spv_hadamard_cls_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_f, c_i, c_i, c_i, c_i, c_vp],
+    "spv_gfilter_path": [c_i, c_i, c_i, c_i],
+    "spv_gfilter_table_floats": [c_i],
+    "spv_gfilter_make_tables": [c_vp, c_i, c_vp],
+    "spv_gfilter_workspace_floats": [c_i, c_i, c_i],
+    "spv_gfilter_partial_floats": [c_i, c_i, c_i],
+    "spv_gfilter_fwd": [c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_vp],
+    "spv_gfilter_bwd": [c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i, c_i, c_i, c_i, c_vp, c_vp],
     "spv_axpby":[c_vp, c_vp, c_vp, c_f, c_f, c_i64, c_i, c_vp],
     "spv_spectrum_floats": [c_i, c_i],
     "spv_spectrum_log1p": [c_vp, c_vp, c_i, c_i, c_i, c_i, c_i, c_vp],
@@ -186,8 +193,9 @@ _RESTYPES = {"spv_last_error": ctypes.c_char_p, "spv_path_count": ctypes.c_longl
              "spv_eval_head_stats_words": c_i64, "spv_augment_tiled_ws_bytes": ctypes.c_size_t, "spv_train_meter_words": c_i64,
              "spv_cross_entropy_meter_workspace_floats": c_i64, "spv_distill_loss_meter_workspace_floats": c_i64,
              "spv_loader_cursor_bytes": c_i64, "spv_hadamard_workspace_floats": c_i64, "spv_feature_cosine_workspace_floats": c_i64,
-             "spv_dataset_stats_words": c_i64}
-_NO_STATUS = set(_RESTYPES) | {"spv_hadamard_path", "spv_hadamard_ln_supported", "spv_hadamard_cls_supported", "spv_version", "spv_fnet_ln_supported", "spv_fnet_cls_supported", "spv_tail_ln_supported", "spv_tail_up_supported", "spv_small_sl_supported", "spv_tail_bwd_parts", "spv_embed_bwd_groups", "spv_haar_ln_supported", "spv_permut_pool_supported", "spv_spectrum_floats", "spv_augment_supported", "spv_loader_augment_supported", "spv_loader_augment_tiled_supported", "spv_augment_plan", "spv_teacher_view_supported", "spv_token_embed_supported"}
+             "spv_dataset_stats_words": c_i64, "spv_gfilter_table_floats": c_i64, "spv_gfilter_workspace_floats": c_i64,
+             "spv_gfilter_partial_floats": c_i64}
+_NO_STATUS = set(_RESTYPES) | {"spv_gfilter_path", "spv_hadamard_path", "spv_hadamard_ln_supported", "spv_hadamard_cls_supported", "spv_version", "spv_fnet_ln_supported", "spv_fnet_cls_supported", "spv_tail_ln_supported", "spv_tail_up_supported", "spv_small_sl_supported", "spv_tail_bwd_parts", "spv_embed_bwd_groups", "spv_haar_ln_supported", "spv_permut_pool_supported", "spv_spectrum_floats", "spv_augment_supported", "spv_loader_augment_supported", "spv_loader_augment_tiled_supported", "spv_augment_plan", "spv_teacher_view_supported", "spv_token_embed_supported"}
 
 class FoldJob(ctypes.Structure):
     """spv_fold_job (include/spv.h): the fold of a tail backward's partial column sums, handed to spv_gemm_tn_fold"""
@@ -237,7 +245,7 @@ def load():
             fn = getattr(lib, name)  # AttributeError here == header/library mismatch
             fn.argtypes = argtypes
             fn.restype = _RESTYPES.get(name, c_i)
-            if argtypes and argtypes[-1] is c_vp and name not in _NO_STATUS and name != "spv_fnet_make_twiddle":
+            if argtypes and argtypes[-1] is c_vp and name not in _NO_STATUS and name not in ("spv_fnet_make_twiddle", "spv_gfilter_make_tables"):
                 _LAUNCHERS[name] = ([i for i, t in enumerate(argtypes) if t in (c_i, c_i64)],
                                     [i for i, t in enumerate(argtypes[:-1]) if t is c_vp])
         if lib.spv_version() != 1:

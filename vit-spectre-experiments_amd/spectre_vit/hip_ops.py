@@ -770,6 +770,52 @@ class HadamardMixFn(torch.autograd.Function):
         return _hadamard_raw(dy, ctx.normalize), None
 
 
+_gfilter_tables = {}
+
+
+def gfilter_tables(tokens, device):
+    """the fp32 DFT table of spv_gfilter_fwd / _bwd for one token count, built once per device"""
+    key = (tokens, device)
+    t = _gfilter_tables.get(key)
+    if t is None:
+        t = torch.empty((_native.call("spv_gfilter_table_floats", tokens),), dtype=torch.float32, device=device)
+        _native.call("spv_gfilter_make_tables", _p(t), tokens, _stream())
+        _gfilter_tables[key] = t
+    return t
+
+
+class GlobalFilterFn(torch.autograd.Function):
+    """y = irfft(rfft(x, dim=1, ortho) * W, n=N, dim=1, ortho), W = view_as_complex(complex_weight) (K, D, 2) fp32, K = N // 2 + 1.
+    The backward saves nothing but x: one call gives dx and the filter's gradient (fp32, written into the parameter's gradient slot)."""
+
+    @staticmethod
+    def forward(ctx, x, complex_weight, tables=None):
+        _require_gpu(x, complex_weight)
+        B, N, D = x.shape
+        if tuple(complex_weight.shape) != (N // 2 + 1, D, 2) or complex_weight.dtype != torch.float32:
+            raise ValueError(f"GlobalFilterFn: complex_weight must be float32 {(N // 2 + 1, D, 2)} for x {tuple(x.shape)}, "
+                             f"got {complex_weight.dtype} {tuple(complex_weight.shape)}")
+        xc = x.contiguous()
+        w = complex_weight.detach().contiguous()
+        if tables is None:
+            tables = gfilter_tables(N, xc.device)
+        y = torch.empty_like(xc)
+        _native.call("spv_gfilter_fwd", _p(xc), _p(w), _p(y), _p(tables), B, N, D, _dt(xc), 0, _stream())   # no kernel of this version needs a workspace
+        ctx.saved = (xc, w, tables, _sink(complex_weight))
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        xc, w, tables, sink = ctx.saved
+        B, N, D = xc.shape
+        dyc = dy.contiguous()
+        dx = torch.empty_like(xc)
+        dw = _grad_buf(sink, w.shape, xc.device)
+        partials = torch.empty((_native.call("spv_gfilter_partial_floats", B, N, D),), dtype=torch.float32, device=xc.device)
+        _native.call("spv_gfilter_bwd", _p(xc), _p(dyc), _p(w), _p(dx), _p(dw), _p(tables), _p(partials), B, N, D, _dt(xc), 0, _stream())
+        return dx, dw, None
+
+
 class RfftRealFn(torch.autograd.Function):
     """rfft(x, dim=-1).real (reference spectre_vit/modules/spectre.py:9-14)."""
 

@@ -4,7 +4,8 @@ Class names, constructor arguments, forward signatures and state_dict keys follo
 (SURVEY.md 8b); the arithmetic runs in libspv_hip.so.  One labelled extension: ``mixer=`` on
 SpectreViT / SpectreEncoderLayer selects the token mixer ("permut" = the reference's HEAD default
 MHPermutMix, "fft" = FNet Re(fft2), "dwt_embed" / "dwt_token" = Haar DWT, "attention" = self-attention over
-the tokens with nn.MultiheadAttention's parameters, "hadamard" = the 2-D Walsh-Hadamard transform of the reference's hadamar.py) -- the modes the reference's docstring lists
+the tokens with nn.MultiheadAttention's parameters, "hadamard" = the 2-D Walsh-Hadamard transform of the reference's hadamar.py,
+"filter" = a learnable frequency-domain filter along the tokens, GFNet's global filter) -- the modes the reference's docstring lists
 (spectre.py:29-35; its undefined "fft_mh" aside) and BASELINE.json benchmarks.
 """
 import torch
@@ -13,9 +14,9 @@ from torch.nn.modules.transformer import _get_activation_fn, _get_clones
 
 from spectre_vit import hip_ops, shadows
 from spectre_vit.models.spectre.layers import MHPermutMix, SpectreLinear
-from spectre_vit.modules.mixers import FNetMixer, HaarDWTMixer, HadamardMixer, SelfAttentionMixer
+from spectre_vit.modules.mixers import FNetMixer, GlobalFilterMixer, HaarDWTMixer, HadamardMixer, SelfAttentionMixer
 
-MIXERS = ("permut", "fft", "dwt_embed", "dwt_token", "attention", "hadamard")
+MIXERS = ("permut", "fft", "dwt_embed", "dwt_token", "attention", "hadamard", "filter")
 
 
 class Transpose(nn.Module):
@@ -42,6 +43,8 @@ def _make_mixer(mixer, d_model, seq_length, nhead, dwt_levels, dwt_mode="passthr
         return SelfAttentionMixer(d_model, nhead, dropout)
     if mixer == "hadamard":
         return HadamardMixer()
+    if mixer == "filter":
+        return GlobalFilterMixer(seq_length, d_model)
     raise ValueError(f"mixer must be one of {MIXERS}, got {mixer!r}")
 
 

@@ -34,6 +34,36 @@ class HadamardMixer(nn.Module):
         return f"normalize={self.normalize}"
 
 
+class GlobalFilterMixer(nn.Module):
+    """The learnable frequency-domain filter along the token axis (GFNet's global filter).  For x (B, N, D), N = seq_length tokens
+    (the CLS row included) and K = N // 2 + 1:
+
+        X = rfft(x, dim=1, norm="ortho")               (B, K, D) complex
+        y = irfft(X * W, n=N, dim=1, norm="ortho")     (B, N, D) real
+
+    W = view_as_complex(complex_weight); complex_weight is a float32 parameter of shape (K, D, 2), drawn as 0.02 * randn at
+    construction and kept in float32 under autocast.  The operator is a depthwise circular convolution of every embedding column.
+    irfft ignores the imaginary part of the DC bin and, for even N, of the Nyquist bin: y does not depend on those entries and their
+    gradient is exactly zero.  The DFT table of a token count is built once per device (hip_ops.gfilter_tables)."""
+
+    def __init__(self, seq_length: int, d_model: int):
+        super().__init__()
+        if seq_length < 1 or d_model < 1:
+            raise ValueError(f"GlobalFilterMixer: seq_length={seq_length} and d_model={d_model} must be positive")
+        self.seq_length = int(seq_length)
+        self.d_model = int(d_model)
+        self.complex_weight = nn.Parameter(0.02 * torch.randn(self.seq_length // 2 + 1, self.d_model, 2, dtype=torch.float32))
+
+    def forward(self, x):
+        x = hip_ops.cast(x, hip_ops.compute_dtype(x))
+        if x.dim() != 3 or x.shape[1] != self.seq_length or x.shape[2] != self.d_model:
+            raise ValueError(f"GlobalFilterMixer({self.seq_length}, {self.d_model}): got x of shape {tuple(x.shape)}")
+        return hip_ops.GlobalFilterFn.apply(x, self.complex_weight, hip_ops.gfilter_tables(self.seq_length, x.device))
+
+    def extra_repr(self):
+        return f"seq_length={self.seq_length}, d_model={self.d_model}"
+
+
 class HaarDWTMixer(nn.Module):
     """J-level Haar DWT along dim ('dwt_embed') or tokens ('dwt_token'); output bands [a_J | d_J | ... | d_1] (pywt.wavedec's order)
     in place of the transformed axis, pairs a = (x0 + x1) / sqrt2, d = (x0 - x1) / sqrt2 (PyWavelets' documented 'haar').
