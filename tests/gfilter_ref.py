@@ -287,6 +287,8 @@ CASES = (
     + [Case(dt, 70, t, d) for t, d in ((5, 24), (65, 64)) for dt in DTYPES]
     # any alignment of the element type
     + [Case(dt, 3, 7, 12, 8) for dt in DTYPES]
+    # the largest token count the selector accepts: 2 columns per workgroup forward, 1 backward, exactly LDS_FLOATS each
+    + [Case(dt, 2, MAX_TOKENS, 3) for dt in DTYPES]
 )
 assert len(set(CASES)) == len(CASES)
 MISALIGNED_REFUSED = [Case("bf16", 3, 7, 64, 8), Case("bf16", 1, 65, 512, 8)]   # fast shapes, x / dy / y / dx off 16-byte alignment

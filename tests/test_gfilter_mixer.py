@@ -5,7 +5,8 @@ against the header compiled by the host compiler and against the library's host-
 
 The generic kernels compute in float32 whatever the storage dtype.  The fast path (bf16, dim % 64 == 0, tokens <= 80) runs both
 products on the MFMA with hi + lo bf16 tables and a hi + lo bf16 spectrum; gfilter_ref.fast_fwd32 / fast_bwd32 restate every rounding
-of it before the final store and must stay within half of each bf16 bar."""
+of it before the final store and must stay within half of each bf16 bar, and element by element within a quarter of the c of
+tests/mfma_mixer_ref.py."""
 import os
 import re
 import subprocess
@@ -15,6 +16,7 @@ import pytest
 import torch
 
 import gfilter_ref as G
+import mfma_mixer_ref as M
 import spectral_ref as R
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -70,14 +72,20 @@ def _fast(c):
 @pytest.mark.parametrize("case", [c for c in G.CASES if c.batch != 1 and _fast(c)], ids=G.case_id)
 def test_restatement_of_the_fast_paths_arithmetic(case):
     """hi + lo bf16 tables, fp32 accumulation, the spectrum split into hi + lo bf16, hi.hi + lo.hi + hi.lo: on exactly the GPU test's
-    inputs within half of each bf16 bar (the store of y / dx, the bar's 2^-8, is not part of it)"""
+    inputs (the store of y / dx, the bar's 2^-8, is not part of it) within half of each bf16 bar, and, element by element in units of
+    2^-24 S_i (tests/mfma_mixer_ref.py), within a quarter of the c the edge tests hold the kernel to: a restatement that drops a lo
+    part does not meet the second (tests/test_mfma_mixer_ref.py)"""
     x, dy, w = G.inputs(case)
     y32 = G.fast_fwd32(x, w)
     dx32, dw32 = G.fast_bwd32(x, dy, w)
     errs = dict(y=R.err(y32, G.fwd(x, w), 1), dx=R.err(dx32, G.dx(dy, w), 1), dw=R.err(dw32, G.dw(x, dy)))
     print("GFILTER fast restatement", G.case_id(case), errs)
     assert errs["y"] <= G.bar(G.TRANSFORM_BAR, "bf16") / 2 and errs["dx"] <= G.bar(G.GRAD_BAR, "bf16") / 2 and errs["dw"] <= G.GRAD_BAR / 2, errs
-    assert not dw32[G.inert(case.tokens), :, 1].any()
+    assert not dw32[G.inert(case.tokens), :, 1].any() and not np.signbit(dw32[G.inert(case.tokens), :, 1]).any()
+    ref = M.filter_reference(x, dy, w)
+    floors = {k: M.floor_units(v, ref, k) for k, v in dict(y=y32, dx=dx32, dw=dw32).items()}
+    print("GFILTER fast restatement", G.case_id(case), "floors in units of 2^-24 S_i:", " ".join(f"{k}={v:.2f} (c / 4 = {M.C_BAR['fast_' + k] / 4})" for k, v in floors.items()))
+    assert all(v <= M.C_BAR["fast_" + k] / 4 for k, v in floors.items()), floors
 
 
 def test_fast_tables_are_a_hi_lo_split_of_the_float32_table():
@@ -105,6 +113,9 @@ def test_float32_restatement_of_the_generic_kernels(case):
     print("GFILTER fp32 restatement", G.case_id(case), errs)
     assert errs["y"] <= G.TRANSFORM_BAR / 4 and errs["dx"] <= G.GRAD_BAR / 4 and errs["dw"] <= G.GRAD_BAR / 4, errs
     assert not dw32[G.inert(case.tokens), :, 1].any()
+    ref = M.filter_reference(x, dy, w)      # element by element, in units of 2^-24 S_i: within a quarter of the generic path's c
+    floors = {k: M.floor_units(v, ref, k) for k, v in dict(y=y32, dx=dx32, dw=dw32).items()}
+    assert all(v <= M.C_BAR["generic_" + k] / 4 for k, v in floors.items()), floors
 
 
 # ------------------------------------------------------------------------------------------ 3. dispatch
@@ -123,7 +134,8 @@ def test_tables_reach_every_branch_and_both_sides_of_every_edge():
     assert all(G.path(c.dtype, c.tokens, c.dim, False) == G.REFUSE_ALIGN and c.off for c in G.MISALIGNED_REFUSED)
     assert all(G.path(c.dtype, c.tokens, c.dim, False) == G.GENERIC for c in G.CASES if c.off)
     assert {1, 2, 3, 4, 5, 16, 17, 32, 33, 64, 65, 197} <= {c.tokens for c in G.CASES} and {8, 24, 64, 512} <= {c.dim for c in G.CASES}
-    assert {c.batch for c in G.CASES} == {1, 3, 70} and G.slabs(70) == 32 < 70 and G.slabs(3) == 3
+    assert {c.batch for c in G.CASES} == {1, 2, 3, 70} and G.slabs(70) == 32 < 70 and G.slabs(3) == 3
+    assert [c for c in G.CASES if c.batch == 2] == [G.Case(dt, 2, G.MAX_TOKENS, 3) for dt in G.DTYPES]
     # column blocks: the whole dim, 64 of a larger dim (with and without a part block), fewer than 64 because of the LDS
     assert any(p.cols_fwd == c.dim < 64 for c, p in plans.items()) and any(p.cols_fwd == 64 and c.dim % 64 for c, p in plans.items())
     assert any(p.cols_fwd == 64 and c.dim % 64 == 0 and c.dim > 64 for c, p in plans.items())
@@ -134,6 +146,12 @@ def test_tables_reach_every_branch_and_both_sides_of_every_edge():
     # the end of the token window, and the budget it comes from
     assert G.path("fp32", G.MAX_TOKENS, 8) == G.GENERIC and G.path("fp32", G.MAX_TOKENS + 1, 8) == G.REFUSE_TOKENS
     assert G.select("fp32", G.MAX_TOKENS, 8).cols_bwd == 1 and 4 * G.MAX_TOKENS + 4 * G.bins(G.MAX_TOKENS) <= G.LDS_FLOATS
+    # ... which a case launches: 2 columns per workgroup forward, 1 backward, and both ask for exactly the accepted 16384 LDS floats
+    for dt in G.DTYPES:
+        p = plans[G.Case(dt, 2, 2730, 3)]
+        assert G.MAX_TOKENS == 2730 and (p.path, p.bins, p.cols_fwd, p.cols_bwd) == (G.GENERIC, 1366, 2, 1)
+        assert p.cols_fwd * (2730 + 2 * p.bins) + 2 * 2730 == p.cols_bwd * (2 * 2730 + 4 * p.bins) + 2 * 2730 == G.LDS_FLOATS == 16384
+        assert G.LDS_FLOATS * 4 == 65536
     assert set(G.REFUSALS.values()) == {G.REFUSE_EMPTY, G.REFUSE_DTYPE, G.REFUSE_TOKENS}
     for p, c in ((p, c) for c, p in plans.items() if p.path == G.GENERIC):
         assert (p.cols_fwd * (c.tokens + 2 * p.bins) + 2 * c.tokens <= G.LDS_FLOATS
